@@ -5,8 +5,16 @@ two U-Net forwards (uncond + cond, batched as one 2B = 128-sample native forward
 plus the CFG mix and the DDPM update, with on-device Philox noise; the timed steps
 run as replayed hipGraphs (the diff.py:332-344 loop without host round trips).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N  (one rank per GPU)
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps,
+the result line.  --dump-outputs DIR also writes the latents the timed loop left after its
+last step (DIR/latents.npy, float32; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output).  --full adds every other leg to the result
+line: config 4 / 5, the fp32-MFMA, host-noise and 28x28 legs, the end-to-end and sharded
+samples, the training step, the per-kernel roofline (and the DMX_BENCH_BREAKDOWN file) and
+the CPU baseline; the per-leg options below select among them.
 
 Each rank runs its own B=64 shard (weak scaling: samples are independent — no
 per-step collective); frozen weights are broadcast from rank 0 over RCCL once.
@@ -44,6 +52,13 @@ def parse():
     ap.add_argument("--hw", type=int, default=32)
     ap.add_argument("--T", type=int, default=1000)
     ap.add_argument("--guidance", type=float, default=3.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the latents of the last timed step to DIR/latents.npy (float32; rank r of a "
+                         "multi-rank job writes latents_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (config 4 / 5, fp32-MFMA / host-noise / 28x28, "
+                         "end-to-end and sharded samples, training step, roofline, CPU baseline); the options "
+                         "below apply only with --full")
     ap.add_argument("--cpu-steps", type=int, default=5, help="oracle steps timed for cpu_baseline, median (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0: os.cpu_count(), capped by OMP_NUM_THREADS where the host sets the process's share")
@@ -62,7 +77,14 @@ def parse():
                     help="steps of the ShardedCondSampler leg (config 3 path incl. decode + gather; 0 = skip)")
     ap.add_argument("--png-steps", type=int, default=100,
                     help="steps of the generate_steps drop-in (async PNG pipeline) timed for config 5 (0 = skip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone, every other leg off
+        args.config4_steps = args.config5_steps = args.legs_steps = args.train_steps = 0
+        args.sharded_T = args.png_steps = args.cpu_steps = 0
+        args.e2e, args.no_profile = False, True
+        if os.environ.get("DMX_BENCH_BREAKDOWN"):
+            print("[bench] DMX_BENCH_BREAKDOWN is written with --full only", file=sys.stderr)
+    return args
 
 
 def dist_setup(args):
@@ -627,6 +649,14 @@ def config4(nm, x, y, vals, mask, args, tables, seed):
             "tolerance": "latents rel-L2 <= 2e-3 after T=1000, measured 7.1e-4 (tests/test_gpu_f16.py)"}
 
 
+def dump_outputs(path, x, world, rank):
+    """What a caller of the timed loop receives: the latents x after its last step (in place)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    name = "latents.npy" if world == 1 else f"latents_rank{rank}.npy"
+    np.save(os.path.join(path, name), x.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     world, rank, local = dist_setup(args)
@@ -675,6 +705,8 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     assert torch.isfinite(x).all(), "non-finite latents"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, world, rank)
 
     value = world * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3

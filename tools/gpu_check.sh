@@ -1,6 +1,8 @@
 #!/bin/bash
 # One GPU-box pass: smoke -> pytest -m gpu -> bench (+ optional rocprof).  Stops at the
 # first fault / abort / timeout (exit codes other than 0 and pytest's 1 = "tests failed").
+# BENCH / PROF hold bench.py's arguments: with --full among them the run also times the legs beside
+# the headline and writes the per-launch breakdown; without it, the headline alone.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
