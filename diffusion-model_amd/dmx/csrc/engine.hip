@@ -454,7 +454,7 @@ struct Packer {
     c.Bl = static_cast<_Float16*>(l);
     if ((c.taps == 9 && c.phases == 1 && c.cout % 64 == 0 && c.cin % 32 == 0 && c.kpad == 9 * c.cin) ||
         (c.taps == 1 && c.phases == 1)) {
-      // halo-kernel candidate (gemm(): 3x3, Cout % 64, whole 32-channel chunks) or a Linear read
+      // halo-kernel candidate (conv_plan(): 3x3, Cout % 64, whole 32-channel chunks) or a Linear read
       // by the token kernels (tokmlp.h tok_gemm: one coalesced 1 KB load per B fragment)
       HIPCHK(hipMalloc(&h, n * sizeof(_Float16)));
       m->owned.push_back(h);
@@ -462,7 +462,7 @@ struct Packer {
       m->owned.push_back(l);
       c.Fh = static_cast<_Float16*>(h);
       c.Fl = static_cast<_Float16*>(l);
-      if (c.taps == 9 && c.cin % 16 == 0) {  // Winograd candidate (gemm(): wino_ok)
+      if (c.taps == 9 && c.cin % 16 == 0) {  // Winograd candidate (conv_plan(): 16-channel chunks)
         const size_t nu = (size_t)16 * c.cout * c.cin;
         HIPCHK(hipMalloc(&h, nu * sizeof(_Float16)));
         m->owned.push_back(h);
@@ -831,33 +831,6 @@ void Run::tap(const std::string& name, const float* p, size_t count) {
   m->taps.push_back({name, {p, count}});
 }
 
-// Mid-ResBlock activation emitted as fp16 hi/lo planes for the split GEMM.
-static bool split_a_enabled() { return true; }
-
-// Max-pool / up-concat sources also written as f16 planes for the next conv1 (split GEMM A;
-// measured +0.2 %, same-box A/B) — they stay fp32 too, as the residual of that ResBlock.
-// Planes are skipped where conv1 runs a halo / Winograd conv, which splits an fp32 source while
-// staging — the source is written once (fp32, also the block's residual) instead of twice:
-// prep_kernel<3> at 32 x 32 41.5 -> 32.9 us, the convs unchanged, +1.3 % per CFG step over planes
-// for every source (same-box A/B, round 3; the switch was removed in round 6).
-static bool cat_planes_enabled() { return true; }
-
-// The 512-thread ping-pong kernel for the large f16-plane convs (measured +1.3 % over the
-// two-block kernel, same-box A/B).
-static bool pp_enabled() { return true; }
-
-// The halo-staged 3x3 conv (igemm_halo.h) for the large 16x16 / 32x32 convs (the small-batch class;
-// batches of >= 64 samples run Winograd): B staged in LDS per step, 16-wave blocks (4 x 4 waves of
-// 64 x 32 at BN = 128, 8 x 2 of 32 x 32 at BN = 64) — +2.1 % per CFG step over 8-wave blocks, which
-// were +2.4 … +2.7 % over the ping-pong / register-staged kernels it replaced (round 3 A/Bs; the
-// losing layouts were removed in round 6).
-constexpr int HALO_MODE = 4;
-static bool halo_enabled() { return true; }
-// Grids with fewer blocks than this split K: 256 (one block per CU).  Since the low-resolution convs
-// moved to the halo kernels (own split rule), this only decides the implicit GEMMs of small
-// batches; unsplit 256-block grids run their GroupNorm as norm_kernel over many blocks instead of
-// reduce_norm_kernel's one block per sample (+0.25 % per CFG step over 512, 3/3 same-box rounds).
-static int split_below() { return 256; }
 // reduce_norm_kernel runs with at least two float4 per thread (KV >= 2; the 4x4 C = 256 ResBlocks,
 // 1024 float4 per sample, leave the second one idle).  The one-float4 instance (KV = 1) gave
 // run-to-run different outputs while a second process shared the GPU (tools/conc_step.sh +
@@ -867,17 +840,9 @@ static int split_below() { return 256; }
 // scalar loads of data, the producer covers every slab element — DMX_POISON), so the instance is not
 // compiled at all: no knob can select it.
 constexpr int RN_MIN_KV = 2;
-// Split-K slabs of a ResBlock conv go straight into reduce_norm_kernel (slab sum + GroupNorm in one
-// launch), and the mid-ResBlock GroupNorm + GELU is folded into conv2's staging where that pays
-// (DMX_RN_FUSE / DMX_GN_FUSE A/B and bisection switches until round 5: always on since).
-static bool rn_fuse_enabled() { return true; }
-static bool gn_fuse_enabled() { return true; }
 
-// Implicit GEMM: conv3x3 (taps 9), ConvT phases (taps 4, phases 4), conv4x4-s2 (taps 16),
-// linear (taps 1).  Sources are plain NHWC (or the NCHW network input); grids too small to
-// fill the 256 CUs are split along K into deterministic slabs reduced by splitk_reduce_kernel
-// (or, in a ResBlock, by the caller's fused reduce_norm_kernel).
-// Returns the GroupNorm partial rows per sample it wrote (EPI_STATS).
+// What gemm() tells a ResBlock about a split conv: fused = the slabs were left for the caller's
+// reduce_norm_kernel (slab sum + GroupNorm in one launch) instead of splitk_reduce_kernel.
 struct Deferred {
   bool fused = false;
   float* partial = nullptr;
@@ -941,41 +906,10 @@ struct GnLoad {
 // parent batch in different classes and lose config 3's bit-identical shards.
 static int dec_n(const Run& R, int N) { return R.tile_n > 0 ? R.tile_n : N >= 64 ? 128 : N; }
 
-// Output-channel tile of the halo-staged 3x3 conv for this GEMM, or 0 when it does not apply
-// (igemm_halo.h: 256-pixel tiles of whole rows of one sample, W = 16 / 32, 32-channel chunks,
-// >= 256 blocks without split-K, EPI_STATS).
-static int halo_bn(const Run& R, int src_C, int N, int H, int W, const ConvW& cw, int epi, bool plain_or_planes) {
-  const int Md = dec_n(R, N) * H * W;
-  const bool x3 = R.m->prec >= 1 && cw.Bh != nullptr;
-  if (!(halo_enabled() && x3 && epi == EPI_STATS && cw.phases == 1 && cw.taps == 9 && (W == 16 || W == 32) &&
-        (H * W) % 256 == 0 && src_C % 32 == 0 && cw.kpad == 9 * src_C && cw.Fh != nullptr && plain_or_planes))
-    return 0;
-  if (cw.cout % 128 == 0 && (Md / 256) * (cw.cout / 128) >= 256) return 128;
-  if (cw.cout % 64 == 0 && (Md / 256) * (cw.cout / 64) >= 256) return 64;
-  return 0;
-}
-
-// Low-resolution halo conv (8 x 8 / 4 x 4, the small-batch class): the chunk-staged kernel
-// (igemm_halo_cs_kernel) everywhere — +1.5 % per CFG step over implicit GEMM + split-K; the per-tap
-// pipeline and mixed layouts measured in between (round 3 A/Bs; removed in round 6).
-static bool halo_ms_enabled() { return true; }
-
 // GELU form of the exact-fp32 mode (training forward, fp32 reference mode): the erf form, as the
 // reference (the fit's own effect on the training gradients was measured at <= 7.8e-8).
 static int gelu_exact_flag(const Run& R) { return R.m->prec == 0 ? 1 : 0; }
 
-// The Winograd conv (x3 fp32-semantics and fp16 modes, fp32 source, 64-tile x 64-channel blocks,
-// 16-channel chunks) replaces the halo convs for batches of >= 64 samples, with K split over 16-channel
-// chunks where the 64 x 64 blocks do not fill 256 CUs (slabs reduced like the other split convs).
-// (DMX_WINO / DMX_WINO_SPLIT / DMX_WINO_F16 / DMX_WINO_MASK A/B switches until round 5.)
-// Winograd plan of a 3x3 conv given an fp32 source: 0 = not applicable, else the K split count
-// (1 = whole K) and *cps = 16-channel chunks per split.  Blocks: 64 tiles (8 rows of a 32-wide map,
-// one 16 x 16 sample, four 8 x 8 samples or sixteen 4 x 4 samples — the last block of a batch that
-// is not a multiple of 4 / 16 holds fewer) x 64 output channels.  The split count is a function of the conv's shape and of a
-// coarse batch class only: it is planned for a reference batch of 128 samples (the benchmark's CFG
-// batch) when the batch has >= 64 samples, of 2 samples below that (single-sample and small batches
-// keep a full grid).  A batch and its shards in the same class sum every output in the same order
-// (bit-identical results: test_gpu_poison.py's B = 5 vs 3 + 2; a 64-per-rank shard plans as the bench).
 // Winograd geometry of an H x W map (igemm_wino.h): the block width 32 / 16 / 8 / 4 the map fits —
 // 8-row bands of any height at 32, whole samples (H <= width) below; 0 = none.  The reference's 28 x 28
 // latents (diff.py:315-322) run their 28 / 14 / 7 / 3 maps in the 32 / 16 / 8 / 4 geometries.
@@ -984,177 +918,234 @@ static int wino_geom(int H, int W) {
   const int g = W > 8 ? 16 : W > 4 ? 8 : W >= 2 ? 4 : 0;
   return (g != 0 && H <= g) ? g : 0;
 }
-static int wino_blocks(int G, int N, int H) {  // blocks along the pixel axis
+// Winograd blocks along the pixel axis: 64 tiles each (8 rows of a 32-wide map, one 16 x 16 sample,
+// four 8 x 8 samples or sixteen 4 x 4 samples — the last block of a batch that is not a multiple of
+// 4 / 16 holds fewer)
+static int wino_blocks(int G, int N, int H) {
   return G == 32 ? N * cdiv(H, 8) : cdiv(N, G == 8 ? 4 : G == 4 ? 16 : 1);
 }
-static int wino_plan(const Run& R, int src_C, int N, int H, int W, const ConvW& cw, int* cps) {
+
+// Which kernel a conv / linear layer runs on, and with which tiling: decided once, by conv_plan(),
+// from the run's mode, the layer's shape, the kind of source and the batch class — no device pointer
+// enters it and it launches nothing.  gemm() executes the plan; resblock() / unet_trunk() ask the plan
+// of the conv they are about to feed what to write for it (fp32 only, f16 planes, a deferred GroupNorm).
+enum ConvSrc {
+  CONV_SRC_NCHW,    // the network input (fp32 NCHW)
+  CONV_SRC_PLAIN,   // fp32 NHWC
+  CONV_SRC_PLANES,  // fp32 NHWC also available as f16 hi / lo planes (split-GEMM operand A)
+  CONV_SRC_GN,      // raw fp32 conv output, its GroupNorm (+ residual) + GELU applied on load (GnLoad)
+};
+enum ConvPath {
+  CONV_INPUT,    // conv_in_kernel: inc's first conv straight from the NCHW input
+  CONV_WINO,     // wino_kernel (igemm_wino.h)
+  CONV_HALO,     // igemm_halo_kernel: whole image rows, W = 16 / 32
+  CONV_HALO_CS,  // igemm_halo_cs_kernel: chunk-staged, whole 8 x 8 / 4 x 4 samples
+  CONV_PP,       // igemm_pp_kernel: 512-thread ping-pong, 256-row tiles
+  CONV_X3,       // igemm_x3_kernel: split-precision implicit GEMM
+  CONV_F32,      // igemm_f32_kernel: exact-fp32 implicit GEMM
+};
+struct ConvPlan {
+  ConvPath path = CONV_F32;
+  bool x3 = false;   // split-precision operands (fp16 hi + lo planes of the weights)
+  bool x1 = false;   // config-4 fp16: one MFMA on the hi planes
+  int cin_px = 0;    // CONV_INPUT: pixels per block
+  int bm = 0, bn = 0, bk = 0;  // tile (bn: output channels per block of the chosen kernel), K step
+  int splits = 1;    // K splits (> 1: slabs, reduced by splitk_reduce_kernel or the caller's reduce_norm)
+  int ksplit = 0;    // K steps per split (Winograd: 16-channel chunks, chunk-staged halo: 32-channel chunks)
+  int wg = 0;        // CONV_WINO: geometry (wino_geom)
+  int cout = 0;      // the layer's output channels
+  int rgrp = 1;      // pixels per GroupNorm partial row
+  int rrows = 0;     // GroupNorm partial rows per sample (EPI_STATS)
+  bool fused = false;  // the slabs may go straight to the caller's reduce_norm (Deferred::fused)
+
+  // the conv splits its fp32 source while staging it: planes of that source would be written for nothing
+  bool reads_fp32() const { return path == CONV_WINO || path == CONV_HALO || path == CONV_HALO_CS; }
+  // the plan of a plain fp32 source: the same conv would read f16 planes instead (split GEMM A)
+  bool takes_planes() const { return x3 && path != CONV_WINO; }
+  // GroupNorm (gna = 1: + GELU, 2: + residual + GELU) on load pays here.  The halo conv: always (one
+  // norm_kernel launch and the activation's round trip fewer).  Winograd applies it once per 64-channel
+  // output block, i.e. Cout / 64 times per staged element, on the VALU the input transform already
+  // loads (diagnostic build without it: -11 % per step).  Same-box per-conv A/B against a norm_kernel
+  // pass + plain staging: Cout = 64 GN + GELU fused wins (-8 us at 32x32, -6 us at 16x16 split),
+  // Cout = 128 even, Cout >= 256 and every GroupNorm-residual-GELU (which also reads the residual) lose
+  // 10-42 us.  The 4-wide geometry has no GroupNorm-on-load instances (split-K only), so a conv on a
+  // map of width <= 4 never takes it (the launcher would throw mid-forward otherwise).
+  bool gn_load_pays(int gna) const {
+    return path == CONV_HALO || (path == CONV_WINO && gna == 1 && cout <= 64 && wg != 4);
+  }
+};
+
+static ConvPlan conv_plan(const Run& R, const ConvW& cw, ConvSrc src, int N, int H, int W, int epi, int seg) {
+  ConvPlan p;
+  p.cout = cw.cout;
+  const int prec = R.m->prec, C = cw.cin;
+  const int Md = dec_n(R, N) * H * W;  // rows the decisions below are taken for
+  const bool conv3 = cw.taps == 9 && cw.phases == 1;
+  const bool nhwc = src != CONV_SRC_NCHW, planes = src == CONV_SRC_PLANES;
+  // inc's first conv: direct fp32 conv of the NCHW input (kernels.h conv_in_kernel<PX>; 16-pixel blocks
+  // for the 28-wide latents)
+  const int cin_px = W % 32 == 0 ? 32 : (W >= 16 && W <= 32 && (H * W) % 16 == 0) ? 16 : 0;
+  if (src == CONV_SRC_NCHW && epi == EPI_STATS && conv3 && cw.cin == 4 && cw.cout == 64 && cin_px > 0 && seg == 32 &&
+      cw.bias == nullptr && R.m->kind != DMX_VAE) {
+    p.path = CONV_INPUT;
+    p.cin_px = cin_px;
+    p.rrows = H * W / cin_px;  // whole K, no slabs
+    return p;
+  }
+  p.bn = (cw.cout % 128 == 0) ? 128 : 64;
+  const int tiles128 = cdiv(Md, 128) * cdiv(cw.cout, p.bn) * cw.phases;
+  p.bm = tiles128 >= 256 ? 128 : 64;  // 128-row tiles (split K if the grid is then small) from 256 tiles
+  const int blocks = cdiv(Md, p.bm) * cdiv(cw.cout, p.bn) * cw.phases;
+  // (R.a_amax: a training data gradient on the split GEMM with device-side operand scales; R.fwd_x3:
+  // the training forward's weights with device-split planes — whatever the model's precision mode,
+  // only the implicit-GEMM kernels below carry those scales)
+  p.x3 = (prec >= 1 || R.a_amax != nullptr || (R.fwd_x3 && cw.inv_dev != nullptr)) && nhwc && cw.Bh != nullptr;
+  p.x1 = p.x3 && prec == 2;
+  // 512-thread ping-pong kernel (256-row tiles) for the large f16-plane convs (measured +1.3 % over
+  // the two-block kernel, same-box A/B)
+  const bool pp = p.x3 && epi == EPI_STATS && cw.phases == 1 && C >= 32 && planes && (H * W) % 32 == 0 &&
+                  cdiv(Md, 256) * cdiv(cw.cout, p.bn) >= 256;  // 32-row GN partials
+  p.bk = pp ? 32 : p.x3 ? 64 : IG_BK;
+  const int nkt = cw.kpad / p.bk;
+  p.ksplit = nkt;
+
+  // The Winograd conv (x3 fp32-semantics and fp16 modes, fp32 source, 64-tile x 64-channel blocks,
+  // 16-channel chunks) replaces the halo convs for batches of >= 64 samples, with K split over
+  // 16-channel chunks where the 64 x 64 blocks do not fill 256 CUs (slabs reduced like the other split
+  // convs).  The split count is a function of the conv's shape and of a coarse batch class only: it is
+  // planned for a reference batch of 128 samples (the benchmark's CFG batch) when the batch has >= 64
+  // samples, of 2 samples below that (single-sample and small batches keep a full grid).  A batch and
+  // its shards in the same class sum every output in the same order (bit-identical results:
+  // test_gpu_poison.py's B = 5 vs 3 + 2; a 64-per-rank shard plans as the bench).
   // (U-Net only: the VAE decoder keeps its per-sample-tiled direct convs, Run::tile_n)
-  if (R.m->prec < 1 || R.m->kind == DMX_VAE ||
-      R.tile_n > 0 || cw.Uh == nullptr ||
-      cw.phases != 1 || cw.taps != 9)
-    return 0;
   const int G = wino_geom(H, W);
-  if (G == 0) return 0;
-  if (src_C % 16 != 0 || cw.cout % 64 != 0 || (size_t)16 * cw.cout * src_C * 2 >= ((size_t)1 << 31)) return 0;
-  const int nref = dec_n(R, N) >= 64 ? 128 : 2;
-  const int blocks = wino_blocks(G, nref, H) * (cw.cout / 64), nch = src_C / 16;
-  int sp = 1, cp = nch;
-  if (blocks < 256) {
+  if (epi == EPI_STATS && (src == CONV_SRC_PLAIN || src == CONV_SRC_GN) && prec >= 1 && R.m->kind != DMX_VAE &&
+      R.tile_n <= 0 && cw.Uh != nullptr && conv3 && G != 0 && C % 16 == 0 && cw.cout % 64 == 0 &&
+      (size_t)16 * cw.cout * C * 2 < ((size_t)1 << 31)) {
+    const int nref = dec_n(R, N) >= 64 ? 128 : 2;
+    const int wblocks = wino_blocks(G, nref, H) * (cw.cout / 64), nch = C / 16;
+    int sp = 1, cp = nch;
     // (small-batch class: the split Winograd conv lost to the direct kernels — config 5, B = 1 CFG:
     // 1.44 vs 1.31 ms per step, same box)
-    if (nref < 128) return 0;
-    sp = std::max(1, std::min(nch, cdiv(256, blocks)));
-    cp = cdiv(nch, sp);
-    sp = cdiv(nch, cp);
+    bool ok = wblocks >= 256 || nref >= 128;
+    if (ok && wblocks < 256) {
+      sp = std::max(1, std::min(nch, cdiv(256, wblocks)));
+      cp = cdiv(nch, sp);
+      sp = cdiv(nch, cp);
+    }
+    if (G == 4 && sp == 1) ok = false;  // (4 x 4: split-K instances only; sixteen samples per block)
+    if (ok) {
+      p.path = CONV_WINO;
+      p.wg = G;
+      p.bn = 64;
+      p.splits = sp;
+      p.ksplit = cp;
+    }
   }
-  if (G == 4 && sp == 1) return 0;  // (4 x 4: split-K instances only; sixteen samples per block)
-  if (cps != nullptr) *cps = cp;
-  return sp;
-}
-static bool wino_any(const Run& R, int src_C, int N, int H, int W, const ConvW& cw) {
-  return wino_plan(R, src_C, N, H, W, cw, nullptr) > 0;
-}
-// GroupNorm(-residual)-GELU on load into a Winograd conv is applied once per 64-channel output block,
-// i.e. Cout / 64 times per staged element, on the VALU the input transform already loads (diagnostic
-// build without it: -11 % per step).  Same-box per-conv A/B against a norm_kernel pass + plain
-// staging: Cout = 64 GN + GELU fused wins (-8 us at 32x32, -6 us at 16x16 split), Cout = 128 even,
-// Cout >= 256 and every GroupNorm-residual-GELU (which also reads the residual) lose 10-42 us.
-// The 4-wide geometry has no GroupNorm-on-load instances (split-K only), so a conv on a map of width
-// <= 4 never takes it (the launcher would throw mid-forward otherwise).
-static bool wino_gna_pays(const ConvW& cw, int gna, int W) { return gna == 1 && cw.cout <= 64 && wino_geom(1, W) != 4; }
-
-// Low-resolution halo conv (igemm_halo.h, W = 8 / 4 square maps): 256-pixel tiles of whole samples,
-// K split over 32-channel chunks until the grid has >= 256 blocks.  Returns the output-channel tile
-// (0: not applicable) and the split count / chunks per split.
-static int halo_ms_bn(const Run& R, int src_C, int N, int H, int W, const ConvW& cw, int epi, bool plain_or_planes,
-                      int* splits, int* cps) {
-  const int Md = dec_n(R, N) * H * W;
-  const bool x3 = R.m->prec >= 1 && cw.Bh != nullptr;
-  if (!(halo_ms_enabled() && x3 && epi == EPI_STATS && cw.phases == 1 && cw.taps == 9 && H == W &&
-        (W == 8 || W == 4) && src_C % 32 == 0 &&
-        cw.kpad == 9 * src_C && plain_or_planes))
-    return 0;
-  // decisions from Md: a batch not a multiple of 256 / W² samples ends in a partial tile; small
-  // batches all split K into every chunk (the same summation order for a batch and its shards)
-  const int nch = src_C / 32, mt = cdiv(Md, 256);
-  auto plan = [&](int bn, int& sp, int& cp) {
-    const int tiles = mt * (cw.cout / bn);
-    sp = std::max(1, std::min(nch, cdiv(256, tiles)));
-    cp = cdiv(nch, sp);
-    sp = cdiv(nch, cp);
-    return tiles * sp;
-  };
-  int sp = 1, cp = nch, bn = 0;
-  if (cw.cout % 64 == 0) {
-    plan(64, sp, cp);
-    bn = 64;
+  // The halo-staged 3x3 convs (igemm_halo.h) of the small-batch class (batches of >= 64 samples run
+  // Winograd), from an fp32 source or its planes
+  const bool halo = p.path != CONV_WINO && prec >= 1 && cw.Bh != nullptr && epi == EPI_STATS && conv3 && C % 32 == 0 &&
+                    cw.kpad == 9 * C && nhwc;
+  if (halo && (W == 16 || W == 32) && (H * W) % 256 == 0 && cw.Fh != nullptr) {
+    // 256-pixel tiles of whole rows of one sample, the chunk's input halo staged once for all nine
+    // taps, B staged in LDS per step, 16-wave blocks (4 x 4 waves of 64 x 32 at BN = 128, 8 x 2 of
+    // 32 x 32 at BN = 64): where it fills >= 256 blocks without split-K.  +2.1 % per CFG step over
+    // 8-wave blocks, which were +2.4 … +2.7 % over the ping-pong / register-staged kernels it replaced
+    // (round 3 A/Bs; the losing layouts were removed in round 6).
+    const int hbn = (cw.cout % 128 == 0 && (Md / 256) * (cw.cout / 128) >= 256)  ? 128
+                    : (cw.cout % 64 == 0 && (Md / 256) * (cw.cout / 64) >= 256) ? 64
+                                                                                  : 0;
+    if (hbn != 0) {
+      p.path = CONV_HALO;
+      p.bn = hbn;
+    }
   }
-  if (bn == 0 || (W == 4 && sp == 1)) return 0;  // W = 4: EPI_PARTIAL instances only
-  *splits = sp;
-  *cps = cp;
-  return bn;
+  if (halo && p.path != CONV_HALO && H == W && (W == 8 || W == 4) && cw.cout % 64 == 0) {
+    // Low resolution (8 x 8 / 4 x 4): 256-pixel tiles of whole samples x 64 channels on the chunk-staged
+    // kernel, K split over 32-channel chunks until the grid has >= 256 blocks — +1.5 % per CFG step
+    // over implicit GEMM + split-K; the per-tap pipeline and mixed layouts measured in between (round 3
+    // A/Bs; removed in round 6).  Decisions from Md: a batch not a multiple of 256 / W² samples ends in
+    // a partial tile; small batches all split K into every chunk (the same summation order for a batch
+    // and its shards).
+    const int nch = C / 32, tiles = cdiv(Md, 256) * (cw.cout / 64);
+    int sp = std::max(1, std::min(nch, cdiv(256, tiles)));
+    const int cp = cdiv(nch, sp);
+    sp = cdiv(nch, cp);
+    if (!(W == 4 && sp == 1)) {  // W = 4: EPI_PARTIAL instances only
+      p.path = CONV_HALO_CS;
+      p.bn = 64;
+      p.splits = sp;
+      p.ksplit = cp;
+    }
+  }
+  if (p.path == CONV_F32) {  // none of the above: an implicit GEMM
+    p.path = pp ? CONV_PP : p.x3 ? CONV_X3 : CONV_F32;
+    // Grids with fewer than 256 blocks (one per CU) split K.  Since the low-resolution convs moved to
+    // the halo kernels (own split rule), this only decides the implicit GEMMs of small batches;
+    // unsplit 256-block grids run their GroupNorm as norm_kernel over many blocks instead of
+    // reduce_norm_kernel's one block per sample (+0.25 % per CFG step over 512, 3/3 same-box rounds).
+    if (!pp && cw.phases == 1 && blocks < 256 && nkt * p.bk >= 512) {
+      p.splits = std::min(std::min(8, std::max(2, 512 / blocks)), nkt * p.bk / 256);
+      p.ksplit = cdiv(nkt, p.splits);
+      p.splits = cdiv(nkt, p.ksplit);
+    }
+  }
+  p.rgrp = (p.splits == 1 && (H * W) % 32 == 0) ? 32 : 1;
+  // GroupNorm partial rows / sample (Winograd: one per 4 tiles of the geometry, igemm_wino.h)
+  p.rrows = (p.path == CONV_WINO && p.splits == 1)
+                ? wino_blocks(p.wg, 1, H) * 64 / (p.wg == 8 ? 4 : p.wg == 4 ? 16 : 1) / 4
+                : cw.phases * H * W / p.rgrp;
+  // Split-K slabs of a ResBlock conv go straight into reduce_norm_kernel (slab sum + GroupNorm in one
+  // launch; debug taps read the raw conv output)
+  p.fused = p.splits > 1 && epi == EPI_STATS && !R.m->debug && H * W * (cw.cout / 4) <= RN_MAXV * 1024;
+  return p;
 }
 
-static bool halo_ms_bn_any(const Run& R, int src_C, int N, int H, int W, const ConvW& cw) {
-  int sp = 0, cp = 0;
-  return halo_ms_bn(R, src_C, N, H, W, cw, EPI_STATS, true, &sp, &cp) > 0;
+// Sum of a split conv's slabs (+ bias, residual, GroupNorm partials) where no reduce_norm takes them
+static void splitk_reduce(Run& R, const ConvPlan& pl, const float* partial, int M, const ConvW& cw, const float* res,
+                          float* out, float2* rowpart, int seg, int epi) {
+  SplitkParams q{partial, pl.splits, M, cw.cout, cw.bias, res, out, rowpart, seg, epi, gelu_exact_flag(R)};
+  R.begin("splitk_reduce_kernel", 0.0, 4.0 * (double)(pl.splits + 1) * M * cw.cout);
+  splitk_reduce_kernel<<<cdiv(M * (cw.cout / 4), 256), 256, 0, R.st>>>(q);
+  R.end();
+  HIPCHK(hipGetLastError());
 }
 
+// Conv / linear layer as a GEMM: conv3x3 (taps 9), ConvT phases (taps 4, phases 4), conv4x4-s2
+// (taps 16), linear (taps 1).  Sources are plain NHWC (or the NCHW network input); grids too small to
+// fill the 256 CUs are split along K into deterministic slabs reduced by splitk_reduce_kernel
+// (or, in a ResBlock, by the caller's fused reduce_norm_kernel).
+// Returns the GroupNorm partial rows per sample it wrote (EPI_STATS).
 static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, const ConvW& cw, int epi, float* out,
                 const float* res, float2* rowpart, int seg, const _Float16* ash = nullptr,
                 const _Float16* asl = nullptr, Deferred* defer = nullptr, const GnLoad* gn = nullptr) {
   const int M = N * H * W;
-  const int Md = dec_n(R, N) * H * W;  // rows the decisions below are taken for
   if (cw.cout % 32 != 0) throw Error(DMX_E_INTERNAL, "gemm: Cout must be a multiple of 32");
-  const int cin_px = W % 32 == 0 ? 32 : (W >= 16 && W <= 32 && (H * W) % 16 == 0) ? 16 : 0;  // conv_in_kernel<PX>
-  if (src_mode == SRC_NCHW && epi == EPI_STATS && cw.taps == 9 && cw.phases == 1 && cw.cin == 4 && cw.cout == 64 &&
-      cin_px > 0 && seg == 32 && cw.bias == nullptr && R.m->kind != DMX_VAE && gn == nullptr) {
-    // inc's first conv: direct fp32 conv of the NCHW input (kernels.h conv_in_kernel; 16-pixel blocks for
-    // the 28-wide latents)
+  // ---- the plan ----
+  const ConvSrc kind = gn != nullptr               ? CONV_SRC_GN
+                       : src_mode == SRC_NCHW      ? CONV_SRC_NCHW
+                       : ash != nullptr            ? CONV_SRC_PLANES
+                                                   : CONV_SRC_PLAIN;
+  const ConvPlan pl = conv_plan(R, cw, kind, N, H, W, epi, seg);
+  const bool x3 = pl.x3, wino = pl.path == CONV_WINO;
+  const int bm = pl.bm, bn = pl.bn, splits = pl.splits, x1 = pl.x1 ? 1 : 0;
+  if (pl.path == CONV_INPUT) {
     if (res != nullptr) throw Error(DMX_E_INTERNAL, "gemm: the direct input conv takes no residual");
     if (ash != nullptr || asl != nullptr) throw Error(DMX_E_INTERNAL, "gemm: the direct input conv reads fp32 NCHW");
-    if (defer != nullptr) *defer = Deferred{};  // whole K, no slabs
-    if (R.plan) return H * W / cin_px;
-    if (check_args()) {  // (as every other GEMM path; the NCHW input is the caller's tensor, not checked)
-      check_range(R, cw.B, (size_t)cw.phases * cw.npad * cw.kpad * 4, "B");
-      check_range(R, out, (size_t)M * 64 * 4, "out");
-      check_range(R, rowpart, (size_t)N * (H * W / cin_px) * (64 / 32) * sizeof(float2), "rowpart");
-    }
-    ConvInParams q;
-    q.x = s.src0;
-    q.creal = s.C0 ? s.C0 : s.C;
-    q.n_mod = s.n_mod;
-    q.scale = s.scale;
-    q.B = cw.B;
-    q.cin = cw.cin;
-    q.kpad = cw.kpad;
-    q.out = out;
-    q.rowpart = rowpart;
-    q.H = H;
-    q.W = W;
-    R.begin(cin_px == 32 ? "conv_in_kernel<32>" : "conv_in_kernel<16>", 2.0 * M * 64.0 * 9.0 * q.creal,
-            4.0 * ((double)M * 64 + (double)M * q.creal));
-    if (cin_px == 32) conv_in_kernel<32><<<M / 32, 256, 0, R.st>>>(q);
-    else conv_in_kernel<16><<<M / 16, 256, 0, R.st>>>(q);
-    R.end();
-    HIPCHK(hipGetLastError());
-    return H * W / cin_px;
-  }
-  const int bn = (cw.cout % 128 == 0) ? 128 : 64;
-  const int tiles128 = cdiv(Md, 128) * cdiv(cw.cout, bn) * cw.phases;
-  const int bm = tiles128 >= 256 ? 128 : 64;  // 128-row tiles (split K if the grid is then small) from 256 tiles
-  const int blocks = cdiv(Md, bm) * cdiv(cw.cout, bn) * cw.phases;
-  // (R.a_amax: a training data gradient on the split GEMM with device-side operand scales; R.fwd_x3:
-  // the training forward's weights with device-split planes — whatever the model's precision mode,
-  // only the implicit-GEMM kernels below carry those scales)
-  const bool x3 = (R.m->prec >= 1 || R.a_amax != nullptr || (R.fwd_x3 && cw.inv_dev != nullptr)) &&
-                  src_mode == SRC_PLAIN && cw.Bh != nullptr;
-  if (R.a_amax != nullptr && (!x3 || ash != nullptr || epi == EPI_STATS || gn != nullptr || R.m->prec == 2))
+  } else if (R.a_amax != nullptr && (!x3 || ash != nullptr || epi == EPI_STATS || gn != nullptr || R.m->prec == 2)) {
     throw Error(DMX_E_INTERNAL, "gemm: device-scaled operands only on the plain split implicit GEMM");
-  const bool x1 = x3 && R.m->prec == 2;  // config-4 fp16: one MFMA on the hi planes
-  // 512-thread ping-pong kernel (256-row tiles) for the large f16-plane convs
-  const bool pp = pp_enabled() && x3 && epi == EPI_STATS && cw.phases == 1 && s.C >= 32 && ash != nullptr &&
-                  (H * W) % 32 == 0 && cdiv(Md, 256) * cdiv(cw.cout, bn) >= 256;  // 32-row GN partials
-  // halo-staged 3x3 conv (igemm_halo.h): 256-pixel tiles of whole image rows (W = 16 / 32), the
-  // chunk's input halo staged once for all nine taps; where it fills >= 256 blocks without split-K
-  const int hbn = halo_bn(R, s.C, N, H, W, cw, epi, ash != nullptr || src_mode == SRC_PLAIN);
-  int wsp = 0, wcps = 0;
-  if (epi == EPI_STATS && src_mode == SRC_PLAIN && ash == nullptr) wsp = wino_plan(R, s.C, N, H, W, cw, &wcps);
-  const bool wino = wsp > 0;
-  if (gn != nullptr && ((hbn == 0 && !wino) || ash != nullptr || src_mode != SRC_PLAIN))
-    throw Error(DMX_E_INTERNAL, "gemm: GroupNorm-on-load needs the halo / Winograd conv on a plain fp32 source");
-  int ms_splits = 1, ms_cps = 0;
-  const int msbn = (hbn || wino) ? 0
-                       : halo_ms_bn(R, s.C, N, H, W, cw, epi, ash != nullptr || src_mode == SRC_PLAIN, &ms_splits,
-                                    &ms_cps);
-  const int bk = pp ? 32 : x3 ? 64 : IG_BK;
-  const int nkt = cw.kpad / bk;
-  int splits = 1, ksplit = nkt;
-  if (wino) {  // Winograd: K split over 16-channel chunks where 64 x 64 blocks do not fill the chip
-    splits = wsp;
-    ksplit = wcps;
-  } else if (msbn) {  // low-resolution halo conv: K split over channel chunks (ksplit = chunks per split)
-    splits = ms_splits;
-    ksplit = ms_cps;
-  } else if (!hbn && !wino && !pp && cw.phases == 1 && blocks < split_below() && nkt * bk >= 512) {  // split K below 2 blocks / CU
-    splits = std::min(std::min(8, std::max(2, 512 / blocks)), nkt * bk / 256);
-    ksplit = cdiv(nkt, splits);
-    splits = cdiv(nkt, ksplit);
   }
+  if (gn != nullptr && ((pl.path != CONV_HALO && !wino) || ash != nullptr || src_mode != SRC_PLAIN))
+    throw Error(DMX_E_INTERNAL, "gemm: GroupNorm-on-load needs the halo / Winograd conv on a plain fp32 source");
   float* partial = splits > 1 ? R.ws.get<float>((size_t)splits * M * cw.cout) : nullptr;
-  const int rgrp = (splits == 1 && (H * W) % 32 == 0) ? 32 : 1;
-  const int wg = wino ? wino_geom(H, W) : 0;
-  // GroupNorm partial rows / sample (Winograd: one per 4 tiles of the geometry, igemm_wino.h)
-  const int rrows = (wino && splits == 1) ? wino_blocks(wg, 1, H) * 64 / (wg == 8 ? 4 : wg == 4 ? 16 : 1) / 4
-                                          : cw.phases * H * W / rgrp;
   if (defer != nullptr) {
-    defer->fused = splits > 1 && epi == EPI_STATS && !R.m->debug && rn_fuse_enabled() &&
-                   H * W * (cw.cout / 4) <= RN_MAXV * 1024;  // (debug taps read the raw conv output)
+    defer->fused = pl.fused;
     defer->partial = partial;
     defer->splits = splits;
     defer->bias = cw.bias;
   }
-  if (R.plan) return rrows;
+  if (R.plan) return pl.rrows;
+  // ---- the kernel arguments ----
   IgemmParams p;
   std::memset(&p, 0, sizeof(p));
   p.src = s;
@@ -1178,23 +1169,24 @@ static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, con
   p.res = res;
   p.rowpart = rowpart;
   p.seg = seg;
-  p.ksplit = ksplit;
+  p.ksplit = pl.ksplit;
   p.partial = partial;
-  p.rgrp = rgrp;
+  p.rgrp = pl.rgrp;
   p.nphase = cw.phases;
   p.gexact = gelu_exact_flag(R);
   if (s.C != cw.cin) throw Error(DMX_E_INTERNAL, "gemm: source channels != weight channels");
-  if (x3 && cw.cin < bk) throw Error(DMX_E_INTERNAL, "gemm: x3 path needs Cin >= K-step");
+  if (x3 && cw.cin < pl.bk) throw Error(DMX_E_INTERNAL, "gemm: x3 path needs Cin >= K-step");
   if (ash != nullptr && !x3) throw Error(DMX_E_INTERNAL, "gemm: f16-plane operand needs the split GEMM");
   if (src_mode != SRC_PLAIN && src_mode != SRC_NCHW) throw Error(DMX_E_INTERNAL, "gemm: unsupported source");
-  if (check_args()) {
+  const bool slabs_to_caller = splits > 1 && pl.fused && defer != nullptr;  // the caller's reduce_norm sums them
+  if (check_args()) {  // (the NCHW input is the caller's tensor, not checked)
     if (src_mode == SRC_PLAIN)
       check_range(R, s.src0, (size_t)N * p.Hin * p.Win * s.C * 4, "A");
     check_range(R, ash, (size_t)N * p.Hin * p.Win * s.C * 2, "A hi");
     check_range(R, asl, (size_t)N * p.Hin * p.Win * s.C * 2, "A lo");
     check_range(R, cw.B, (size_t)cw.phases * cw.npad * cw.kpad * 4, "B");
     check_range(R, partial, (size_t)splits * M * cw.cout * 4, "partial");
-    if (!(splits > 1 && defer != nullptr && defer->fused))
+    if (!slabs_to_caller)
       check_range(R, out, (size_t)N * p.Hout * p.Wout * cw.cout * 4, "out");
     check_range(R, res, (size_t)N * p.Hout * p.Wout * cw.cout * 4, "res");
   }
@@ -1224,121 +1216,95 @@ static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, con
     xp.a_bytes = (unsigned)ab;
     xp.b_bytes = (unsigned)bb;
   }
-  // labels are the demangled kernel names rocprofv3 reports (profiles/ cross-check)
+  const int gna = gn != nullptr ? (gn->res != nullptr ? 2 : 1) : 0;
+  if (gna) {
+    xp.gn_rowpart = gn->rowpart;
+    xp.gn_cnt = gn->cnt;
+    xp.gn_gamma = gn->gamma;
+    xp.gn_beta = gn->beta;
+    xp.gn_res = gn->res;
+  }
+  // ---- the launch ----  (labels are the demangled kernel names rocprofv3 reports, profiles/ cross-check)
   const int sa = ash != nullptr ? 1 : 0;
   const int creal = (src_mode == SRC_NCHW && s.C0) ? s.C0 : cw.cin;
   const double flops = 2.0 * (double)M * cw.phases * cw.cout * (double)cw.taps * creal;
   const double bytes = 4.0 * ((double)M * cw.phases * cw.cout + (double)N * p.Hin * p.Win * s.C +
-                              (double)cw.phases * cw.cout * cw.taps * cw.cin);
+                              (double)cw.phases * cw.cout * cw.taps * cw.cin) +
+                       (splits > 1 ? 4.0 * splits * M * cw.cout : 0.0);
+  const int e = splits > 1 ? (int)EPI_PARTIAL : epi;  // a split conv writes slabs
   char nm[96];
-  auto name_x3 = [&](int e) {
-    std::snprintf(nm, sizeof nm, "igemm_x3_kernel<%d, %d, %d, 64, 1, %d, %d>", bm, bn, e, sa, x1 ? 1 : 0);
-  };
-  auto name_f32 = [&](int e) {
-    std::snprintf(nm, sizeof nm, "igemm_f32_kernel<%d, %d, %d, %d>", bm, bn, src_mode, e);
-  };
-  if (msbn) {  // low-resolution halo conv: 256-pixel tiles of whole samples (igemm_halo.h MS)
-    const int e = splits > 1 ? (int)EPI_PARTIAL : (int)EPI_STATS;
-    dim3 gm(cdiv(M, 256), cw.cout / msbn, splits);
-    const bool cs = msbn == 64;
-    if (cs) std::snprintf(nm, sizeof nm, "igemm_halo_cs_kernel<%d, %d, %d, %d>", e, sa, x1 ? 1 : 0, W);
-    else std::snprintf(nm, sizeof nm, "igemm_halo_kernel<%d, %d, %d, %d, %d, 0>", msbn, e, sa, x1 ? 1 : 0, W);
-    R.begin(nm, flops, bytes + (splits > 1 ? 4.0 * splits * M * cw.cout : 0.0));
-    if (cs) launch_halo_cs(e, W, sa, x1 ? 1 : 0, xp, gm, R.st);
-    else launch_halo_ms(e, msbn, W, sa, x1 ? 1 : 0, xp, gm, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    if (splits == 1 || (defer != nullptr && defer->fused)) return rrows;
-    SplitkParams q{partial, splits, M, cw.cout, cw.bias, res, out, rowpart, seg, epi, gelu_exact_flag(R)};
-    const int rb = cdiv(M * (cw.cout / 4), 256);
-    R.begin("splitk_reduce_kernel", 0.0, 4.0 * (double)(splits + 1) * M * cw.cout);
-    splitk_reduce_kernel<<<rb, 256, 0, R.st>>>(q);
-    R.end();
-    HIPCHK(hipGetLastError());
-    return rrows;
-  }
-  if (splits > 1 && !wino) {  // (split Winograd convs launch below with their own chunk units)
-    dim3 grid(cdiv(M, bm), cdiv(cw.cout, bn), splits);
-    if (x3) name_x3(EPI_PARTIAL);
-    else name_f32(EPI_PARTIAL);
-    R.begin(nm, flops, bytes + 4.0 * splits * M * cw.cout);
-    if (x3) launch_x3_partial(bm, bn, sa, x1 ? 1 : 0, xp, grid, R.st);
-    else launch_f32(src_mode, EPI_PARTIAL, bm, bn, p, grid, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    if (defer != nullptr && defer->fused) return rrows;  // the caller's reduce_norm_kernel sums the slabs
-    SplitkParams q{partial, splits, M, cw.cout, cw.bias, res, out, rowpart, seg, epi, gelu_exact_flag(R)};
-    const int rb = cdiv(M * (cw.cout / 4), 256);
-    R.begin("splitk_reduce_kernel", 0.0, 4.0 * (double)(splits + 1) * M * cw.cout);
-    splitk_reduce_kernel<<<rb, 256, 0, R.st>>>(q);
-    R.end();
-    HIPCHK(hipGetLastError());
-    return rrows;
-  }
-  if (hbn || wino) {  // halo-staged 3x3 conv, 256-pixel x hbn tiles (igemm_halo.h) / Winograd
-    dim3 gh(M / 256, hbn ? cw.cout / hbn : 1, 1);
-    const int gna = gn != nullptr ? (gn->res != nullptr ? 2 : 1) : 0;
-    if (gna) {
-      xp.gn_rowpart = gn->rowpart;
-      xp.gn_cnt = gn->cnt;
-      xp.gn_gamma = gn->gamma;
-      xp.gn_beta = gn->beta;
-      xp.gn_res = gn->res;
+  switch (pl.path) {
+    case CONV_INPUT: {
+      check_range(R, rowpart, (size_t)N * pl.rrows * (64 / 32) * sizeof(float2), "rowpart");
+      ConvInParams q;
+      q.x = s.src0;
+      q.creal = s.C0 ? s.C0 : s.C;
+      q.n_mod = s.n_mod;
+      q.scale = s.scale;
+      q.B = cw.B;
+      q.cin = cw.cin;
+      q.kpad = cw.kpad;
+      q.out = out;
+      q.rowpart = rowpart;
+      q.H = H;
+      q.W = W;
+      R.begin(pl.cin_px == 32 ? "conv_in_kernel<32>" : "conv_in_kernel<16>", 2.0 * M * 64.0 * 9.0 * q.creal,
+              4.0 * ((double)M * 64 + (double)M * q.creal));
+      if (pl.cin_px == 32) conv_in_kernel<32><<<M / 32, 256, 0, R.st>>>(q);
+      else conv_in_kernel<16><<<M / 16, 256, 0, R.st>>>(q);
+      break;
     }
-    if (wino) {  // Winograd F(2x2, 3x3): 64 tiles (256 pixels) x 64 channels per block (igemm_wino.h)
+    case CONV_WINO:  // Winograd F(2x2, 3x3): 64 tiles (256 pixels) x 64 channels per block (igemm_wino.h)
       xp.Uh = cw.Uh;
       xp.Ul = cw.Ul;
       xp.u_bytes = (unsigned)((size_t)16 * cw.cout * s.C * 2);
       check_range(R, cw.Uh, xp.u_bytes, "U hi");
       check_range(R, cw.Ul, xp.u_bytes, "U lo");
-      const int e = splits > 1 ? (int)EPI_PARTIAL : (int)EPI_STATS;
-      if (x1) std::snprintf(nm, sizeof nm, "wino_kernel<%d, %d, %d, 1>", wg, gna, e);
-      else std::snprintf(nm, sizeof nm, "wino_kernel<%d, %d, %d>", wg, gna, e);
-      R.begin(nm, flops, bytes + (splits > 1 ? 4.0 * splits * M * cw.cout : 0.0));
-      launch_wino(e, wg, gna, x1 ? 1 : 0, xp, dim3(wino_blocks(wg, N, H), cw.cout / 64, splits), R.st);
-      R.end();
-      HIPCHK(hipGetLastError());
-      if (splits == 1 || (defer != nullptr && defer->fused)) return rrows;
-      SplitkParams q{partial, splits, M, cw.cout, cw.bias, res, out, rowpart, seg, epi, gelu_exact_flag(R)};
-      R.begin("splitk_reduce_kernel", 0.0, 4.0 * (double)(splits + 1) * M * cw.cout);
-      splitk_reduce_kernel<<<cdiv(M * (cw.cout / 4), 256), 256, 0, R.st>>>(q);
-      R.end();
-      HIPCHK(hipGetLastError());
-      return rrows;
+      if (x1) std::snprintf(nm, sizeof nm, "wino_kernel<%d, %d, %d, 1>", pl.wg, gna, e);
+      else std::snprintf(nm, sizeof nm, "wino_kernel<%d, %d, %d>", pl.wg, gna, e);
+      R.begin(nm, flops, bytes);
+      launch_wino(e, pl.wg, gna, x1, xp, dim3(wino_blocks(pl.wg, N, H), cw.cout / 64, splits), R.st);
+      break;
+    case CONV_HALO:  // 256-pixel x bn tiles of whole image rows (igemm_halo.h)
+      std::snprintf(nm, sizeof nm, "igemm_halo_kernel<%d, %d, %d, %d, %d, %d>", bn, (int)EPI_STATS, sa, x1, W, gna);
+      R.begin(nm, flops, bytes);
+      launch_halo(bn, W, sa, x1, gna, xp, dim3(M / 256, cw.cout / bn, 1), R.st);
+      break;
+    case CONV_HALO_CS:  // 256-pixel tiles of whole low-resolution samples x 64 channels (igemm_halo.h)
+      std::snprintf(nm, sizeof nm, "igemm_halo_cs_kernel<%d, %d, %d, %d>", e, sa, x1, W);
+      R.begin(nm, flops, bytes);
+      launch_halo_cs(e, W, sa, x1, xp, dim3(cdiv(M, 256), cw.cout / bn, splits), R.st);
+      break;
+    case CONV_PP:  // 512-thread ping-pong kernel, 256 x bn tiles (igemm_pp.h)
+      std::snprintf(nm, sizeof nm, "igemm_pp_kernel<%d, %d, %d, %d>", bn, (int)EPI_STATS, sa, x1);
+      R.begin(nm, flops, bytes);
+      launch_pp(bn, x1, xp, dim3(cdiv(M, 256), cdiv(cw.cout, bn), 1), R.st);  // (sa = 1: CONV_PP needs planes)
+      break;
+    case CONV_X3: {
+      const dim3 grid(cdiv(M, bm), cdiv(cw.cout, bn), splits > 1 ? splits : cw.phases);
+      std::snprintf(nm, sizeof nm, "igemm_x3_kernel<%d, %d, %d, 64, 1, %d, %d>", bm, bn, e, sa, x1);
+      if (e != EPI_PARTIAL && e != EPI_STATS && e != EPI_BIAS && e != EPI_BIAS_GELU && e != EPI_BIAS_RES)
+        throw Error(DMX_E_INTERNAL, "bad epilogue");
+      R.begin(nm, flops, bytes);
+      if (e == EPI_PARTIAL) launch_x3_partial(bm, bn, sa, x1, xp, grid, R.st);
+      else if (e == EPI_STATS) launch_x3_stats(bm, bn, sa, x1, xp, grid, R.st);
+      else launch_x3_epi(e, bm, bn, sa, x1, xp, grid, R.st);
+      break;
     }
-    std::snprintf(nm, sizeof nm, "igemm_halo_kernel<%d, %d, %d, %d, %d, %d>", hbn, (int)EPI_STATS, sa, x1 ? 1 : 0, W,
-                  gna);
-    R.begin(nm, flops, bytes);
-    launch_halo(HALO_MODE, hbn, W, sa, x1 ? 1 : 0, gna, xp, gh, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    return rrows;
-  }
-  if (pp) {  // 512-thread ping-pong kernel, 256 x bn tiles (igemm_pp.h)
-    dim3 gpp(cdiv(M, 256), cdiv(cw.cout, bn), 1);
-    std::snprintf(nm, sizeof nm, "igemm_pp_kernel<%d, %d, %d, %d>", bn, (int)EPI_STATS, sa, x1 ? 1 : 0);
-    R.begin(nm, flops, bytes);
-    launch_pp(bn, sa, x1 ? 1 : 0, xp, gpp, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    return rrows;
-  }
-  dim3 grid(cdiv(M, bm), cdiv(cw.cout, bn), cw.phases);
-  if (x3) name_x3(epi);
-  else name_f32(epi == EPI_STATS ? epi : epi);
-  R.begin(nm, flops, bytes);
-  if (x3) {
-    if (epi == EPI_STATS) launch_x3_stats(bm, bn, sa, x1 ? 1 : 0, xp, grid, R.st);
-    else if (epi == EPI_BIAS || epi == EPI_BIAS_GELU || epi == EPI_BIAS_RES)
-      launch_x3_epi(epi, bm, bn, sa, x1 ? 1 : 0, xp, grid, R.st);
-    else throw Error(DMX_E_INTERNAL, "bad epilogue");
-  } else {
-    if (src_mode == SRC_NCHW && epi != EPI_STATS) throw Error(DMX_E_INTERNAL, "bad epilogue for NCHW source");
-    launch_f32(src_mode, epi, bm, bn, p, grid, R.st);
+    case CONV_F32: {
+      const dim3 grid(cdiv(M, bm), cdiv(cw.cout, bn), splits > 1 ? splits : cw.phases);
+      std::snprintf(nm, sizeof nm, "igemm_f32_kernel<%d, %d, %d, %d>", bm, bn, src_mode, e);
+      if (src_mode == SRC_NCHW && e != EPI_PARTIAL && e != EPI_STATS)
+        throw Error(DMX_E_INTERNAL, "bad epilogue for NCHW source");
+      R.begin(nm, flops, bytes);
+      launch_f32(src_mode, e, bm, bn, p, grid, R.st);
+      break;
+    }
   }
   R.end();
   HIPCHK(hipGetLastError());
-  return rrows;
+  if (splits > 1 && !slabs_to_caller) splitk_reduce(R, pl, partial, M, cw, res, out, rowpart, seg, epi);
+  return pl.rrows;
 }
 
 static void gn_finalize(Run& R, const float2* rowpart, float2* stats, int N, int rrows, int nseg, int G, int C,
@@ -1444,9 +1410,10 @@ static float* resblock(Run& R, const ResW& w, const SrcDesc& in, int mode, int N
   const int seg = 32;
   float* r1 = R.ws.get<float>((size_t)M * w.mid);
   float2* rp1 = R.ws.get<float2>((size_t)M * (w.mid / seg));
-  // conv2 on the Winograd kernel reads the fp32 mid activation (GroupNorm-on-load or materialised)
-  const bool c2_wino = wino_any(R, w.mid, N, H, W, w.c2);
-  const bool planes = R.m->prec >= 1 && split_a_enabled() && w.c2.Bh != nullptr && w.mid >= 64 && !c2_wino;
+  // conv2's plan for the fp32 mid activation: the Winograd kernel reads it as it is (GroupNorm-on-load
+  // or materialised); the other split-precision kernels get it as f16 hi / lo planes
+  const ConvPlan p2 = conv_plan(R, w.c2, CONV_SRC_PLAIN, N, H, W, EPI_STATS, seg);
+  const bool planes = R.m->prec >= 1 && p2.takes_planes() && w.mid >= 64;
   float* a1 = R.ws.get<float>((size_t)M * w.mid);  // fp32 or, with planes, hi|lo f16 halves
   float* r2 = R.ws.get<float>((size_t)M * w.cout);
   float2* rp2 = R.ws.get<float2>((size_t)M * (w.cout / seg));
@@ -1464,12 +1431,12 @@ static float* resblock(Run& R, const ResW& w, const SrcDesc& in, int mode, int N
     n1.out_h = a1h;
     n1.out_l = a1l;
   }
-  // The mid GroupNorm + GELU folded into conv2's halo staging (igemm_halo.h GNA) where conv2 runs
-  // the halo conv and conv1 wrote whole-sample partials (no split-K slabs): no norm_kernel launch,
-  // no hi / lo planes.  DMX_GN_FUSE=0 turns it off (the staged operand is the same either way).
-  const bool fuse1 = gn_fuse_enabled() && !d1.fused && !R.m->debug &&
-                     ((planes && halo_bn(R, w.mid, N, H, W, w.c2, EPI_STATS, true) > 0) ||
-                      (c2_wino && wino_gna_pays(w.c2, 1, W)));
+  // The mid GroupNorm + GELU folded into conv2's staging (igemm_halo.h / igemm_wino.h GNA) where conv2
+  // runs the halo or Winograd conv, that pays (ConvPlan::gn_load_pays) and conv1 wrote whole-sample
+  // partials (no split-K slabs): no norm_kernel launch, no hi / lo planes (the staged operand is the
+  // same either way).
+  const bool fuse1 = !d1.fused && !R.m->debug && p2.gn_load_pays(1) &&
+                     (planes || p2.path == CONV_WINO);
   int rr2;
   if (fuse1) {
     GnLoad g;
@@ -1505,8 +1472,7 @@ static float* resblock(Run& R, const ResW& w, const SrcDesc& in, int mode, int N
   n2.emb_stride = emb_stride;
   n2.emb_off = emb_off;
   n2.n_src = n_out > N ? N : 0;
-  const bool pout = planes_out && R.m->prec >= 1 && split_a_enabled() && !R.m->debug && emb == nullptr &&
-                    n_out == N && w.cout >= 64;
+  const bool pout = planes_out && R.m->prec >= 1 && !R.m->debug && emb == nullptr && n_out == N && w.cout >= 64;
   if (wrote_planes != nullptr) *wrote_planes = pout;
   if (pout) {  // hi | lo halves of the output buffer, as a1
     n2.out = nullptr;
@@ -1776,17 +1742,21 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     R.layer = "down" + std::to_string(i + 1) + ".0";
     const size_t pool_el = (size_t)nb * nh * nw * cc;
     float* pooled = R.ws.get<float>(pool_el);
-    const bool pool_planes = R.m->prec >= 1 && m->down[i].r0.c1.Bh != nullptr && !R.m->debug && cat_planes_enabled() &&
-                             !((halo_bn(R, cc, nb, nh, nw, m->down[i].r0.c1, EPI_STATS, true) > 0 ||
-                                                          halo_ms_bn_any(R, cc, nb, nh, nw, m->down[i].r0.c1))) &&
-                             !wino_any(R, cc, nb, nh, nw, m->down[i].r0.c1);
+    // Max-pool / up-concat sources also written as f16 planes for the next conv1 (split GEMM A;
+    // measured +0.2 %, same-box A/B) — they stay fp32 too, as the residual of that ResBlock.
+    // Planes are skipped where conv1 runs a halo / Winograd conv, which splits an fp32 source while
+    // staging — the source is written once (fp32, also the block's residual) instead of twice:
+    // prep_kernel<3> at 32 x 32 41.5 -> 32.9 us, the convs unchanged, +1.3 % per CFG step over planes
+    // for every source (same-box A/B, round 3).
+    const ConvPlan r0c1 = conv_plan(R, m->down[i].r0.c1, CONV_SRC_PLAIN, nb, nh, nw, EPI_STATS, 32);
+    const ConvPlan r1c1 = conv_plan(R, m->down[i].r1.c1, CONV_SRC_PLAIN, nb, nh, nw, EPI_STATS, 32);
+    const bool pool_planes = R.m->prec >= 1 && m->down[i].r0.c1.Bh != nullptr && !R.m->debug && !r0c1.reads_fp32();
     _Float16* pool_h = pool_planes ? R.ws.get<_Float16>(2 * pool_el) : nullptr;
     _Float16* pool_l = pool_planes ? pool_h + pool_el : nullptr;
     prep<SRC_MAXPOOL>(R, mp, pooled, nb, nh, nw, "prep_kernel<2>", pool_h, pool_l);
     bool hp = false;
     float* h0 = resblock(R, m->down[i].r0, plain_src(pooled, cc), SRC_PLAIN, nb, nh, nw, true, nullptr, 0, 0, 0,
-                         pool_h, pool_l, m->down[i].r1.c1.Bh != nullptr && !wino_any(R, cc, nb, nh, nw, m->down[i].r1.c1),
-                         &hp);
+                         pool_h, pool_l, r1c1.takes_planes(), &hp);
     R.layer = "down" + std::to_string(i + 1) + ".1";
     const _Float16* h0h = hp ? reinterpret_cast<const _Float16*>(h0) : nullptr;
     float* h1 = resblock(R, m->down[i].r1, plain_src(h0, cc), SRC_PLAIN, nb, nh, nw, false, emb, m->hsum,
@@ -1802,8 +1772,8 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
   for (int i = 0; i < m->nbot; ++i) {
     R.layer = "bot" + std::to_string(i + 1);
     bool hp = false;
-    const bool nxt = i + 1 < m->nbot && m->bot[i + 1].c1.Bh != nullptr &&  // the last one feeds the upsample
-                     !wino_any(R, m->bot[i].cout, N, ch, cw, m->bot[i + 1].c1);
+    const bool nxt = i + 1 < m->nbot &&  // the last one feeds the upsample
+                     conv_plan(R, m->bot[i + 1].c1, CONV_SRC_PLAIN, N, ch, cw, EPI_STATS, 32).takes_planes();
     cur = resblock(R, m->bot[i], plain_src(cur, cc), SRC_PLAIN, N, ch, cw, false, nullptr, 0, 0, 0, cur_h, cur_l, nxt,
                    &hp);
     cc = m->bot[i].cout;
@@ -1827,23 +1797,20 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     const size_t cat_el = (size_t)N * sh[si] * sw[si] * u.C;
     float* cat = R.ws.get<float>(cat_el);
     // the concat feeds conv1 (split GEMM: also as f16 planes) and the residual (fp32)
-    const bool cat_planes = R.m->prec >= 1 && m->up[i].r0.c1.Bh != nullptr && !R.m->debug && cat_planes_enabled() &&
-                            !((halo_bn(R, u.C, N, sh[si], sw[si], m->up[i].r0.c1, EPI_STATS, true) > 0 ||
-                                                         halo_ms_bn_any(R, u.C, N, sh[si], sw[si], m->up[i].r0.c1))) &&
-                            !wino_any(R, u.C, N, sh[si], sw[si], m->up[i].r0.c1);
+    // (planes as for the max-pool source above: not where conv1 stages the fp32 source itself)
+    const ConvPlan r0c1 = conv_plan(R, m->up[i].r0.c1, CONV_SRC_PLAIN, N, sh[si], sw[si], EPI_STATS, 32);
+    const ConvPlan r1c1 = conv_plan(R, m->up[i].r1.c1, CONV_SRC_PLAIN, N, sh[si], sw[si], EPI_STATS, 32);
+    const bool cat_planes = R.m->prec >= 1 && m->up[i].r0.c1.Bh != nullptr && !R.m->debug && !r0c1.reads_fp32();
     _Float16* cat_h = cat_planes ? R.ws.get<_Float16>(2 * cat_el) : nullptr;
     _Float16* cat_l = cat_planes ? cat_h + cat_el : nullptr;
     prep<SRC_UPCAT>(R, u, cat, N, sh[si], sw[si], "prep_kernel<3>", cat_h, cat_l);
     bool hp = false;
-    // r0's final GroupNorm + residual + GELU folded into r1's halo conv1 where that conv runs the
-    // halo kernel (igemm_halo.h GNA = 2): one norm_kernel launch and the h0 round trip fewer
+    // r0's final GroupNorm + residual + GELU folded into r1's conv1 where that pays (the halo kernel,
+    // igemm_halo.h GNA = 2): one norm_kernel launch and the h0 round trip fewer
     GnLoad dly;
-    const bool r1_wino = wino_any(R, u.C, N, sh[si], sw[si], m->up[i].r1.c1);
-    const bool try_defer = gn_fuse_enabled() && !R.m->debug && R.m->prec >= 1 &&
-                           (r1_wino ? wino_gna_pays(m->up[i].r1.c1, 2, sw[si])
-                                    : halo_bn(R, u.C, N, sh[si], sw[si], m->up[i].r1.c1, EPI_STATS, true) > 0);
+    const bool try_defer = !R.m->debug && R.m->prec >= 1 && r1c1.gn_load_pays(2);
     float* h0 = resblock(R, m->up[i].r0, plain_src(cat, u.C), SRC_PLAIN, N, sh[si], sw[si], true, nullptr, 0, 0, 0,
-                         cat_h, cat_l, m->up[i].r1.c1.Bh != nullptr && !r1_wino, &hp, try_defer ? &dly : nullptr);
+                         cat_h, cat_l, r1c1.takes_planes(), &hp, try_defer ? &dly : nullptr);
     R.layer = "up" + std::to_string(i + 1) + ".1";
     const _Float16* h0h = hp ? reinterpret_cast<const _Float16*>(h0) : nullptr;
     float* h1 = dly.rowpart != nullptr

@@ -5,7 +5,7 @@
 // v_mfma_f32_32x32x16_f16 per product (al*bh, ah*bl, ah*bh), fp32 accumulate, weights pre-split
 // and pre-scaled.  What differs is how A reaches LDS.  The implicit GEMMs stage A per K-tile =
 // (tap, channel slice), so every input pixel is loaded, (split,) and written to LDS nine times.
-// Here a 512-thread block owns 256 output pixels (TR whole image rows of one sample, W = 16 or
+// Here a 16-wave block owns 256 output pixels (TR whole image rows of one sample, W = 16 or
 // 32) x BN output channels and walks K as (32-channel chunk) x (9 taps): the chunk's input halo
 // — (TR + 2) x (W + 2) pixels, zero outside the image — is staged ONCE as f16 hi / lo planes, and
 // the nine taps read their A fragments from it at a per-tap pixel offset (row r of a fragment is
@@ -22,10 +22,11 @@
 // the barrier ending step s - 1); the next chunk's halo is loaded at the chunk's tap 0 and written
 // to the other A buffer after tap 1 (its readers, the previous chunk, finished before tap 0).
 // LDS (80-byte rows, conflict-free ds_read_b128 as in igemm_x3): A 2 x HP x 40 f16 x 2 planes
-// (108.8 KB at W = 32), B 2 x BN x 40 f16 x 2 planes (41 KB at BN = 128): one block per CU, two
-// waves per SIMD.  Waves: 4 (rows) x 2 (columns), 64 x BN/2 each.
+// (108.8 KB at W = 32), B 2 x BN x 40 f16 x 2 planes (41 KB at BN = 128): one block per CU.
+// Waves: NWM (rows) x NWN (columns), sixteen per block (k_halo.hip).
 //
-// Low resolution (W = 8, 4; square maps): a 256-pixel tile is 256 / W² WHOLE samples.  Their halos
+// Low resolution (W = 8, 4; square maps; igemm_halo_cs_kernel below): a 256-pixel tile is
+// 256 / W² WHOLE samples.  Their halos
 // are stacked in one LDS image with the zero borders shared: row pitch W + 1 (the zero column right
 // of image row y is the zero column left of row y + 1), one zero row before every sample and after
 // the last, i.e. sample s row y sits in halo row 1 + s (W + 1) + y.  Every tap (dy, dx) of every
@@ -54,14 +55,11 @@ template <int BN, int EPI, int SA, int X1, int W, int GNA = 0, int NWN = 2, int 
 __global__ __launch_bounds__(64 * NWM * NWN) void igemm_halo_kernel(const X3Params P) {
   constexpr int NTH = 64 * NWM * NWN;              // threads: NWM (rows) x NWN (columns) waves
   const IgemmParams& p = P.g;
-  constexpr bool MS = W <= 8;                      // multi-sample tiles (H == W), stacked halos
-  constexpr int TR = 256 / W;                      // output image rows per tile (MS: over the samples)
-  constexpr int SPT = MS ? 256 / (W * W) : 1;      // samples per tile
-  constexpr int HWD = MS ? W + 1 : W + 2;          // halo row pitch
-  constexpr int HP = MS ? (1 + SPT * (W + 1)) * HWD + 1 : (TR + 2) * HWD;  // halo pixels
+  constexpr int TR = 256 / W;                      // output image rows per tile
+  constexpr int HWD = W + 2;                       // halo row pitch
+  constexpr int HP = (TR + 2) * HWD;               // halo pixels
   constexpr int CK = 32, RS = CK + 8;              // channels per chunk, f16 per LDS row
-  static_assert(!MS || (W == 4 || W == 8), "multi-sample halo tiles: W = 4 or 8");
-  static_assert(!(MS && GNA), "GroupNorm-on-load needs whole-row tiles of one sample");
+  static_assert(W == 16 || W == 32, "whole-row tiles of one sample");
   static_assert(EPI == EPI_STATS || EPI == EPI_PARTIAL, "halo epilogues");
   constexpr int WM = 256 / NWM, WN = BN / NWN, TM = WM / 32, TN = WN / 32;
   constexpr int PW = SA ? 8 : 4;                   // channels per staged A piece (16 bytes)
@@ -100,17 +98,9 @@ __global__ __launch_bounds__(64 * NWM * NWN) void igemm_halo_kernel(const X3Para
     hpix[i] = (short)h;
     hq[i] = (short)q;
     const int hy = h / HWD, hx = h - hy * HWD;
-    bool ok;
-    int pix;
-    if constexpr (MS) {  // halo row hy = 1 + s (W + 1) + y (y = W: the zero row after sample s)
-      const int s = (hy - 1) / (W + 1), y = hy - 1 - s * (W + 1), x = hx - 1;
-      ok = e < HP * PPR && hy >= 1 && hy < 1 + SPT * (W + 1) && y < W && x >= 0 && nsmp + s < p.M / HW;
-      pix = ((nsmp + s) * W + y) * W + x;
-    } else {
-      const int y = y0 + hy - 1, x = hx - 1;
-      ok = e < HP * PPR && y >= 0 && y < p.H && x >= 0 && x < W;
-      pix = (nsmp * p.H + y) * W + x;
-    }
+    const int y = y0 + hy - 1, x = hx - 1;
+    const bool ok = e < HP * PPR && y >= 0 && y < p.H && x >= 0 && x < W;
+    const int pix = (nsmp * p.H + y) * W + x;
     hoff[i] = ok ? (pix * C + (cbeg * CK + q * PW)) : -1;
   }
   const __amdgpu_buffer_rsrc_t rAh = rsrc_of(SA ? (const void*)P.Ash : (const void*)p.src.src0, P.a_bytes);
@@ -260,13 +250,8 @@ __global__ __launch_bounds__(64 * NWM * NWN) void igemm_halo_kernel(const X3Para
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int r = wm * WM + i * 32 + fp;
-    if constexpr (MS) {  // tile pixel r = sample r / W², row ly, column lx
-      const int s = r / (W * W), ly = (r - s * W * W) / W, lx = r % W;
-      abase[i] = (1 + s * (W + 1) + ly) * HWD + lx + 1;
-    } else {
-      const int ly = r / W, lx = r - ly * W;
-      abase[i] = (ly + 1) * HWD + lx + 1;
-    }
+    const int ly = r / W, lx = r - ly * W;
+    abase[i] = (ly + 1) * HWD + lx + 1;
   }
   auto compute = [&](int abuf, int bbuf, int tap) {
     const int ty = (tap * 11) >> 5;  // tap / 3 for tap in [0, 8]
@@ -395,7 +380,7 @@ __global__ __launch_bounds__(1024) void igemm_halo_cs_kernel(const X3Params P) {
   const int cbeg = EPI == EPI_PARTIAL ? bz * p.ksplit : 0;
   const int nch = EPI == EPI_PARTIAL ? min(p.ksplit, nch_all - cbeg) : nch_all;
 
-  // halo pieces (stacked samples, as igemm_halo_kernel MS): element offset of the piece's first
+  // halo pieces (stacked samples, see the file header): element offset of the piece's first
   // channel in chunk 0 of this block, or -1 (zero)
   int hoff[NPI];
   short hpix[NPI], hq[NPI];
@@ -545,222 +530,6 @@ static __global__ void frag_planes_kernel(const _Float16* bh, const _Float16* bl
     *reinterpret_cast<half8*>(fh + dst) = *reinterpret_cast<const half8*>(bh + i * 8);
     *reinterpret_cast<half8*>(fl + dst) = *reinterpret_cast<const half8*>(bl + i * 8);
   }
-}
-
-// ---------------------------------------------------------------------------
-// Halo conv with B read straight into registers ("B-direct").  The A halo is staged as above;
-// every wave loads its own B fragments for the NEXT (chunk, tap) step from the fragment-ordered
-// planes (P.Fh / P.Fl: one coalesced 1 KB load per fragment, L2-resident weights; the four waves
-// of a column group read the same bytes, mostly L1 hits) while the current step's MFMAs run, so
-// B never touches LDS and the only barrier is the one per 32-channel chunk (halo buffer swap):
-// MFMAs flow across the nine taps of a chunk.  A fragments are read one k16 step ahead, across
-// tap boundaries too.  Same K order as igemm_halo_kernel.
-// ---------------------------------------------------------------------------
-template <int BN, int EPI, int SA, int X1, int W>
-__global__ __launch_bounds__(512) void igemm_halo_bd_kernel(const X3Params P) {
-  const IgemmParams& p = P.g;
-  constexpr int TR = 256 / W;
-  constexpr int HWD = W + 2, HP = (TR + 2) * HWD;
-  constexpr int CK = 32, RS = CK + 8;
-  constexpr int WN = BN / 2, TM = 2, TN = WN / 32;
-  constexpr int PW = SA ? 8 : 4;
-  constexpr int PPR = CK / PW;
-  constexpr int NPI = (HP * PPR + 511) / 512;
-  constexpr int NP = X1 ? 1 : 2;  // B planes
-  static_assert(TN >= 1, "tile");
-
-  constexpr int LA = X1 ? 1 : HP;
-  __shared__ __attribute__((aligned(16))) _Float16 Ah[2][HP][RS];
-  __shared__ __attribute__((aligned(16))) _Float16 Al[2][LA][RS];
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wid >> 1, wn = wid & 1;
-  int mt, nt, bz;
-  xcd_tile(mt, nt, bz);
-  const int m0 = mt * 256, n0 = nt * BN;
-  const int HW = p.H * W;
-  const int C = p.src.C;
-  const int nsmp = m0 / HW, y0 = (m0 - nsmp * HW) / W;
-  constexpr int AES = SA ? 2 : 4;
-
-  // halo pieces of this thread (index e = tid + 512 i): element offset of channel 0 (chunk 0) or -1
-  int hoff[NPI];
-#pragma unroll
-  for (int i = 0; i < NPI; ++i) {
-    const int e = tid + 512 * i;
-    const int h = e / PPR, q = e - h * PPR;
-    const int hy = h / HWD, hx = h - hy * HWD;
-    const int y = y0 + hy - 1, x = hx - 1;
-    const bool ok = e < HP * PPR && y >= 0 && y < p.H && x >= 0 && x < W;
-    hoff[i] = ok ? (((nsmp * p.H + y) * W + x) * C + q * PW) : -1;
-  }
-  const __amdgpu_buffer_rsrc_t rAh = rsrc_of(SA ? (const void*)P.Ash : (const void*)p.src.src0, P.a_bytes);
-  const __amdgpu_buffer_rsrc_t rAl = rsrc_of(SA ? (const void*)P.Asl : (const void*)p.src.src0, P.a_bytes);
-  const __amdgpu_buffer_rsrc_t rFh = rsrc_of(P.Fh, P.b_bytes), rFl = rsrc_of(P.Fl, P.b_bytes);
-
-  // The next chunk's halo is staged in HR rounds of PR pieces per thread (round r: loaded at tap 2r,
-  // written at tap 2r + 1) so only PR pieces are held in registers at a time.
-  constexpr int HR = 4, PR = (NPI + HR - 1) / HR;
-  floatx4 ha4[SA ? 1 : PR];
-  half8 hah[SA ? PR : 1], hal[SA ? PR : 1];
-  auto load_halo = [&](int c, int r) {
-#pragma unroll
-    for (int k = 0; k < PR; ++k) {
-      const int i = r * PR + k;
-      if (i >= NPI) break;
-      const int off = hoff[i] >= 0 ? (hoff[i] + c * CK) * AES : kOOB;
-      if constexpr (SA) {
-        hah[k] = bload_h8(rAh, off, 0);
-        if constexpr (!X1) hal[k] = bload_h8(rAl, off, 0);
-      } else {
-        ha4[k] = bload_f4(rAh, off, 0);
-      }
-    }
-  };
-  auto store_halo = [&](int buf, int r) {
-#pragma unroll
-    for (int k = 0; k < PR; ++k) {
-      const int i = r * PR + k;
-      if (i >= NPI) break;
-      const int e = tid + 512 * i;
-      if (e >= HP * PPR) continue;
-      const int h = e / PPR, q = e - h * PPR;
-      if constexpr (SA) {
-        *reinterpret_cast<half8*>(&Ah[buf][h][q * 8]) = hah[k];
-        if constexpr (!X1) *reinterpret_cast<half8*>(&Al[buf][h][q * 8]) = hal[k];
-      } else if constexpr (X1) {
-        *reinterpret_cast<half4*>(&Ah[buf][h][q * 4]) = __builtin_convertvector(ha4[k], half4);
-      } else {
-        half4 hh, ll;
-        split4(ha4[k], hh, ll);
-        *reinterpret_cast<half4*>(&Ah[buf][h][q * 4]) = hh;
-        *reinterpret_cast<half4*>(&Al[buf][h][q * 4]) = ll;
-      }
-    }
-  };
-  // B fragments of one step: [column tile j][k16 step s][plane]
-  struct BF {
-    half8 v[TN][2][NP];
-  };
-  const int kk16 = p.Kpad / 16;
-  const int voff = lane * 16;
-  auto load_bf = [&](int c, int t, BF& b) {
-    const int kk = (t * C + c * CK) / 16;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int nb = (n0 + wn * WN + j * 32) >> 5;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int soff = (nb * kk16 + kk + s) * 1024;
-        b.v[j][s][0] = bload_h8(rFh, voff, soff);
-        if constexpr (!X1) b.v[j][s][1] = bload_h8(rFl, voff, soff);
-      }
-    }
-  };
-
-  floatx16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int fr = lane & 31, fh = lane >> 5;
-  int abase[TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int r = wm * 64 + i * 32 + fr;
-    const int ly = r / W, lx = r - ly * W;
-    abase[i] = (ly + 1) * HWD + lx + 1;
-  }
-  auto tap_delta = [&](int tap) {
-    const int ty = (tap * 11) >> 5;
-    return (ty - 1) * HWD + (tap - 3 * ty - 1);
-  };
-  // A fragments, two k16 slots
-  half8 ah[2][TM], al[2][TM];
-  auto lda = [&](int abuf, int tap, int s, int d) {
-    const int delta = tap_delta(tap);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int row = abase[i] + delta;
-      ah[d][i] = *reinterpret_cast<const half8*>(&Ah[abuf][row][16 * s + 8 * fh]);
-      if constexpr (!X1) al[d][i] = *reinterpret_cast<const half8*>(&Al[abuf][row][16 * s + 8 * fh]);
-    }
-  };
-  auto mfmas = [&](int d, const BF& b, int s) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (!X1) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[d][i], b.v[j][s][0], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[d][i], b.v[j][s][1], acc[i][j], 0, 0, 0);
-        }
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[d][i], b.v[j][s][0], acc[i][j], 0, 0, 0);
-      }
-  };
-  constexpr int NRA = (X1 ? 1 : 2) * TM, NM = (X1 ? 1 : 3) * TM * TN;
-
-  const int nch = C / CK;
-  const int S = nch * 9;
-  BF b0, b1;
-  load_bf(0, 0, b0);
-#pragma unroll
-  for (int r = 0; r < HR; ++r) {
-    load_halo(0, r);
-    store_halo(0, r);
-  }
-  __syncthreads();
-  lda(0, 0, 0, 0);
-  // one (chunk, tap) step: MFMAs from A buffer c & 1 and `cur`; loads the next step's B into `nxt`
-  auto step = [&](int s, BF& cur, BF& nxt) {
-    const int c = s / 9, t = s - c * 9;
-    const int abuf = c & 1;
-    if (s + 1 < S) load_bf(t == 8 ? c + 1 : c, t == 8 ? 0 : t + 1, nxt);
-    if ((t & 1) == 0 && t < 2 * HR && c + 1 < nch) load_halo(c + 1, t >> 1);
-    lda(abuf, t, 1, 1);  // k16 step 1 of this tap, under step 0's MFMAs
-    mfmas(0, cur, 0);
-    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-    for (int r = 0; r < NRA; ++r) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NRA - 1, 0);
-    if (t < 8) {
-      lda(abuf, t + 1, 0, 0);  // next tap's k16 step 0, under step 1's MFMAs
-      mfmas(1, cur, 1);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#pragma unroll
-      for (int r = 0; r < NRA; ++r) {
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, NM - NRA - 1, 0);
-    } else {
-      mfmas(1, cur, 1);
-    }
-    if ((t & 1) == 1 && t < 2 * HR && c + 1 < nch) store_halo((c + 1) & 1, t >> 1);
-    if (t == 8 && s + 1 < S) {
-      __syncthreads();  // chunk c + 1's halo complete in buffer (c + 1) & 1; buffer c & 1 free
-      lda((c + 1) & 1, 0, 0, 0);
-    }
-  };
-  for (int s = 0; s < S; s += 2) {
-    step(s, b0, b1);
-    if (s + 1 < S) step(s + 1, b1, b0);
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] *= P.inv_scale;
-
-  igemm_epilogue<128, BN, EPI>(p, acc, 0, m0 + (wm >> 1) * 128, n0, wm & 1, wn, fr, fh);
 }
 
 }  // namespace dmx

@@ -21,20 +21,10 @@ void launch_tok_qkv_lds(int C, int tpb, int x1, const TokParams& tp, dim3 gl, hi
 }
 
 void launch_tok_qkv(int C, int nb, int x1, const TokParams& tp, dim3 grid, hipStream_t st) {
-#define TQ(CC, NN) (x1 ? tok_ln_qkv_kernel<CC, NN, 1><<<grid, 256, 0, st>>>(tp) \
-                       : tok_ln_qkv_kernel<CC, NN, 0><<<grid, 256, 0, st>>>(tp))
-  switch (C) {
-    case 64:
-      if (nb == 192) TQ(64, 192);
-      else TQ(64, 64);
-      break;
-    case 128: TQ(128, 128); break;
-    default:
-      if (nb == 64) TQ(256, 64);
-      else TQ(256, 128);
-      break;
-  }
-#undef TQ
+  // (C = 64 / 128 run tok_ln_qkv_lds_kernel; C = 256 takes 64 columns per block, which doubles the grid)
+  if (C != 256 || nb != 64) throw std::runtime_error("launch_tok_qkv: C = 256 in 64-column blocks only");
+  if (x1) tok_ln_qkv_kernel<256, 64, 1><<<grid, 256, 0, st>>>(tp);
+  else tok_ln_qkv_kernel<256, 64, 0><<<grid, 256, 0, st>>>(tp);
 }
 
 void launch_tok_qkv_w(int C, int x1, const TokParams& tp, dim3 grid, hipStream_t st) {
@@ -54,13 +44,12 @@ void launch_tok_out(int C, int tm, int x1, int nw, int lds, int tpb, const TokPa
     else if (tpb == 2) TBL(2);
     else TBL(1);
 #undef TBL
-  } else if (C == 64) TB(64, 64);
-  else if (C == 128 && tm == 64) TB(128, 64);
+  } else if (C == 128 && tm == 64) TB(128, 64);
   else if (C == 128) TB(128, 32);
-  else if (nw == 8) {
+  else if (C == 256 && nw == 8) {
     if (x1) tok_attn_out_kernel<256, 32, 1, 8><<<blocks, 512, 0, st>>>(tp);
     else tok_attn_out_kernel<256, 32, 0, 8><<<blocks, 512, 0, st>>>(tp);
-  } else TB(256, 32);
+  } else throw std::runtime_error("launch_tok_out: C = 64 runs the LDS instances, C = 256 eight waves");
 #undef TB
 }
 

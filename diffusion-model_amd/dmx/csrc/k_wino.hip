@@ -14,7 +14,7 @@ static int g_wstamp_next = 0;  // stamp slot of the next Winograd launch (reset 
 
 template <int W, int EPI, int X1>
 static void go(int gna, const X3Params& p, dim3 grid, hipStream_t st) {
-  // (GNA = 2, the residual GELU(x + GN) on load, is never dispatched: engine.hip wino_gna_pays — it
+  // (GNA = 2, the residual GELU(x + GN) on load, is never dispatched: engine.hip ConvPlan::gn_load_pays — it
   // lost 10-42 us per conv against a norm pass — so its instances are not built)
   if (gna == 1) wino_kernel<W, 1, EPI, X1><<<grid, 512, 0, st>>>(p);
   else if (gna == 0) wino_kernel<W, 0, EPI, X1><<<grid, 512, 0, st>>>(p);

@@ -19,19 +19,17 @@ void launch_x3_stats(int bm, int bn, int sa, int x1, const X3Params& p, dim3 gri
 // and 4 waves otherwise; the 64 x 128 split-K tiles at 4x4 / 8x8 are at parity or slower with 8.)
 void launch_x3_partial(int bm, int bn, int sa, int x1, const X3Params& p, dim3 grid, hipStream_t st);
 void launch_x3_epi(int epi, int bm, int bn, int sa, int x1, const X3Params& p, dim3 grid, hipStream_t st);
-// 512-thread ping-pong split-precision GEMM (igemm_pp.h), EPI_STATS, 256 x bn tiles.
-void launch_pp(int bn, int sa, int x1, const X3Params& p, dim3 grid, hipStream_t st);
+// 512-thread ping-pong split-precision GEMM (igemm_pp.h), EPI_STATS, 256 x bn tiles, A from f16 planes.
+void launch_pp(int bn, int x1, const X3Params& p, dim3 grid, hipStream_t st);
 // halo-staged split-precision 3x3 conv (igemm_halo.h), EPI_STATS, 256-pixel x bn tiles, image
-// width w in {16, 32}; k_halo.hip.
-// mode 1: B fragments read straight from the fragment-ordered planes into registers (one barrier
-// per channel chunk); mode 2: B staged in LDS per step (one barrier per step).
-// gna = 1 (mode 2, sa = 0): GroupNorm + GELU of the raw source applied while staging.
-void launch_halo(int mode, int bn, int w, int sa, int x1, int gna, const X3Params& p, dim3 grid, hipStream_t st);
-// the same kernel on low-resolution maps (w in {8, 4}, H == w): 256-pixel tiles of whole samples;
-// epi EPI_PARTIAL (grid.z = K splits over 32-channel chunks, P.g.ksplit chunks each) or EPI_STATS
-// (w = 8); bn 128 or 64 (w = 4: 64 only); k_halo_ms.hip.
-void launch_halo_ms(int epi, int bn, int w, int sa, int x1, const X3Params& p, dim3 grid, hipStream_t st);
-// chunk-staged variant (igemm_halo_cs_kernel): BN = 64, all nine taps of a chunk's B slice in LDS.
+// width w in {16, 32}, bn in {128, 64}; 16-wave blocks, B staged in LDS per (chunk, tap) step;
+// k_halo.hip.  gna (sa = 0 only) = 1: GroupNorm + GELU of the raw source applied while staging;
+// = 2: GELU(residual + GroupNorm(source)).
+void launch_halo(int bn, int w, int sa, int x1, int gna, const X3Params& p, dim3 grid, hipStream_t st);
+// chunk-staged halo conv of the low-resolution maps (igemm_halo_cs_kernel; w in {8, 4}, H == w):
+// 256-pixel tiles of whole samples x 64 channels, all nine taps of a chunk's B slice in LDS; epi
+// EPI_PARTIAL (grid.z = K splits over 32-channel chunks, P.g.ksplit chunks each) or EPI_STATS
+// (w = 8); k_halo_cs.hip.
 void launch_halo_cs(int epi, int w, int sa, int x1, const X3Params& p, dim3 grid, hipStream_t st);
 // Winograd F(2x2, 3x3) split-precision 3x3 conv (igemm_wino.h), 64 tiles (256 pixels) x 64 channels
 // per block, w in {4, 8, 16, 32} (4: EPI_PARTIAL, gna 0 only), gna as launch_halo, x1 = 1 the fp16

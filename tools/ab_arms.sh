@@ -1,6 +1,8 @@
 #!/bin/bash
 # Same-box interleaved A/B of any number of arms, each an env string (library builds via DMX_LIB):
-#   [ROUNDS=2] tools/ab_arms.sh "DMX_HALO_MS=1" "DMX_HALO_MS=2" "DMX_LIB=libhead.so" ...
+#   [ROUNDS=2] tools/ab_arms.sh "DMX_LIB=libdmx.so" "DMX_LIB=libhead.so" "DMX_LIB=libdmx.so" ...
+# (kernel choices have no environment switches: build each variant with
+#  python diffusion-model_amd/dmx/build.py --out libNAME.so [-- -DDMX_DIAG=1] and select it with DMX_LIB)
 # Prints steps/s per arm and round; the last round also writes a per-launch breakdown of arm i to
 # gpurun_out/bd_arm<i>.json (tools/ab_cmp.py compares two of them).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

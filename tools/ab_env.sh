@@ -1,6 +1,7 @@
 #!/bin/bash
 # Same-box interleaved A/B of env knobs: tools/ab_env.sh "A_ENV" "B_ENV" [rounds]
-# e.g. tools/ab_env.sh "DMX_PP=1" "DMX_PP=0" 2 ; prints steps/s per arm and round.
+# e.g. tools/ab_env.sh "DMX_LIB=libdmx.so" "DMX_LIB=libhead.so" 2 ; prints steps/s per arm and round
+# (library variants: python diffusion-model_amd/dmx/build.py --out libhead.so).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 A="$1"; B="$2"; R=${3:-2}

@@ -1,5 +1,6 @@
 """Diagnostic: one B=64 CFG step (x3) of the synthetic config-2 model, latents written to the
-path given (used to compare builds / env switches bit for bit, e.g. DMX_GN_FUSE=0 vs 1)."""
+path given (used to compare library builds bit for bit: DMX_LIB=libNAME.so, built with
+dmx/build.py --out NAME.so, against the default libdmx.so)."""
 import os
 import sys
 

@@ -1,5 +1,6 @@
 """One U-Net forward of N samples vs the oracle (GPU box): python tools/fwd_check.py [N] [hw] [prec]
-Prints eps / geom rel-L2 — a quick bisection aid for env knobs (DMX_WINO, DMX_WINO_SPLIT, DMX_GN_FUSE)."""
+Prints eps / geom rel-L2 — a quick bisection aid for library variants (DMX_LIB=libNAME.so built with
+dmx/build.py --out, or the -DDMX_DIAG=1 build); the kernel choices have no environment switches."""
 import os
 import sys
 
