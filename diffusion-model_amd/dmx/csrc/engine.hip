@@ -23,6 +23,7 @@
 #include "tokmlp.h"
 #include "eval.h"
 #include "train.h"
+#include "vae_train.h"
 
 namespace dmx {
 
@@ -252,6 +253,7 @@ struct GraphKey {
 };
 
 struct Tape;  // training forward record (train_engine.h)
+struct VaeTape;  // the VAE's (vae_train_engine.h)
 
 }  // namespace dmx
 
@@ -288,6 +290,9 @@ struct dmx_model {
   dmx::ConvW venc[6];
   dmx::Vec veg[6], veb[6];
   float *wmu = nullptr, *bmu = nullptr, *wlv = nullptr, *blv = nullptr;
+  // VAE training (vae_train_engine.h), per stage: the forward weight with device-split planes, and the
+  // data-gradient GEMM weight (none for enc.0 / dec.0)
+  dmx::ConvW venc_t[6], venc_d[6], vdec_t[6], vdec_d[6];
   // workspace + graph
   dmx::Arena ws;
   void* ws_mem = nullptr;
@@ -323,6 +328,7 @@ struct dmx_model {
   // backward pass's workspace
   bool train_ready = false;
   dmx::Tape* tape = nullptr;
+  dmx::VaeTape* vtape = nullptr;
   dmx::Arena tws, bws;
   void *tws_mem = nullptr, *bws_mem = nullptr;
   size_t tws_cap = 0, bws_cap = 0;
@@ -2082,6 +2088,7 @@ static void vae_enc_body(Run& R, const float* x, const float* eps, float* z, flo
 }  // namespace dmx
 
 #include "train_engine.h"
+#include "vae_train_engine.h"
 
 // ===========================================================================
 // C ABI
@@ -2233,6 +2240,7 @@ int dmx_model_destroy(dmx_model* m) {
     if (m->tws_mem) (void)hipFree(m->tws_mem);
     if (m->bws_mem) (void)hipFree(m->bws_mem);
     delete m->tape;
+    delete m->vtape;
     delete m;
   });
 }
@@ -2260,7 +2268,9 @@ int dmx_model_finalize(dmx_model* m, void* stream) {
   });
 }
 
-int64_t dmx_model_workspace_bytes(const dmx_model* m) { return m ? (int64_t)m->ws_cap : -1; }
+int64_t dmx_model_workspace_bytes(const dmx_model* m) {
+  return m ? (int64_t)(m->ws_cap + m->tws_cap + m->bws_cap) : -1;
+}
 
 int dmx_model_refresh(dmx_model* m, void* stream) {
   return guarded([&] {
@@ -2305,6 +2315,48 @@ int dmx_train_backward(dmx_model* m, int64_t tape_id, const float* d_eps, const 
     hipStream_t st = (hipStream_t)stream;
     with_fp32(m, [&] {
       run_arena(m, st, m->bws, m->bws_mem, m->bws_cap, [&](Run& R) { train_bwd_body(R, *m->tape, G, d_eps, d_geom); });
+    });
+  });
+}
+
+int dmx_vae_train_forward(dmx_model* m, const float* x, const float* eps, int n, int h, int w, float* x_recon, float* z,
+                          float* kl, int64_t* tape_id, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr && tape_id != nullptr, "null argument");
+    if (!m->finalized) throw Error(DMX_E_STATE, "model weights not finalized");
+    REQUIRE(m->kind == DMX_VAE, "not a VAE model");
+    REQUIRE(x && eps && x_recon && z && kl, "null tensor");
+    REQUIRE(n >= 1 && h >= 8 && w >= 8 && h % 8 == 0 && w % 8 == 0, "image sides must be multiples of 8");
+    REQUIRE((size_t)n * h * w < ((size_t)1 << 24), "batch too large: n * h * w must stay below 2^24 pixels");
+    hipStream_t st = (hipStream_t)stream;
+    ensure_vae_train(m, st);
+    if (m->vtape == nullptr) m->vtape = new VaeTape();
+    VaeTape& T = *m->vtape;
+    T.id = 0;  // invalid until the forward below has been enqueued
+    with_fp32(m, [&] {
+      run_arena(m, st, m->tws, m->tws_mem, m->tws_cap,
+                [&](Run& R) { vae_train_fwd_body(R, T, x, eps, x_recon, z, kl, n, h, w); });
+    });
+    T.id = ++m->tape_id;
+    *tape_id = T.id;
+  });
+}
+
+int dmx_vae_train_backward(dmx_model* m, int64_t tape_id, const float* d_recon, const float* d_z, const float* d_kl,
+                           float* const* grads, int n_grads, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr && grads != nullptr, "null argument");
+    REQUIRE(m->kind == DMX_VAE, "not a VAE model");
+    REQUIRE(m->vtape != nullptr && m->vtape->id != 0, "no training forward recorded (dmx_vae_train_forward)");
+    REQUIRE(tape_id == m->vtape->id,
+            "stale tape: another dmx_vae_train_forward ran after the one this backward belongs to");
+    REQUIRE(n_grads == (int)m->keys.size(), "grads must hold one pointer per state_dict key");
+    GradMap G;
+    for (int i = 0; i < n_grads; ++i) G.g[m->keys[i].name] = grads[i];
+    hipStream_t st = (hipStream_t)stream;
+    with_fp32(m, [&] {
+      run_arena(m, st, m->bws, m->bws_mem, m->bws_cap,
+                [&](Run& R) { vae_train_bwd_body(R, *m->vtape, G, d_recon, d_z, d_kl); });
     });
   });
 }

@@ -362,10 +362,18 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* x, const float
 // split into `splits` slabs (blockIdx.z) written to part[split][Cout][K]; wgrad_finish_kernel
 // sums the slabs in split order and scatters to the torch layout [Cout][Cin][3][3] / [Cout][Cin].
 // ---------------------------------------------------------------------------
+// GEO (compile-time gather geometry): 0 = conv3x3 pad 1 / Linear as above; 1, 2 = the 16-tap
+// stride-2 layers of the VAE: rows m are the pixels of the small H x W map and A is gathered from the
+// 2H x 2W map at (2y + ky - 1, 2x + kx - 1), k = (4 ky + kx) Cin + ci.
+//   1: Conv2d 4x4 s2 p1 — dy = dY on the small (output) map, x = the layer input on the large map
+//   2: ConvTranspose2d 4x4 s2 p1, the operands' roles swapped — dy = the layer input (small map,
+//      "Cout" = its channels), x = dY on the large map ("Cin" = its channels); dW comes out as
+//      [in][out * 16 taps], which wgrad_finish_kernel scatters to [in][out][4][4].  wgrad_x3_kernel
+//      applies the device-side 2^ea scale to the operand that holds dY: the gathered one here.
 struct WgradParams {
   const float* dy;   // [M][Cout]
-  const float* x;    // [N][H][W][Cin] (NHWC)
-  int N, H, W, Cin, Cout, taps;  // taps 9 (conv3x3) or 1 (linear)
+  const float* x;    // [N][H][W][Cin] (NHWC; GEO 1, 2: [N][2H][2W][Cin])
+  int N, H, W, Cin, Cout, taps;  // taps 9 (conv3x3), 1 (linear) or 16 (GEO 1, 2)
   int M, K;          // M = N*H*W rows, K = taps * Cin
   int rows_per_split;
   float* part;       // [splits][Cout][K]
@@ -377,6 +385,7 @@ struct WgradParams {
   int dy_nparts;
 };
 
+template <int GEO>
 static __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
   constexpr int MK = 16;  // rows per LDS tile
   __shared__ float dys[MK][64 + 4];
@@ -398,12 +407,19 @@ static __global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) 
       if (m < mend && k < p.K) {
         const int tap = k / p.Cin, ci = k - tap * p.Cin;
         const int n = m / HW, rr = m - n * HW, y = rr / p.W, xx = rr - y * p.W;
-        int iy = y, ix = xx;
-        if (p.taps == 9) {
-          iy = y + tap / 3 - 1;
-          ix = xx + tap % 3 - 1;
+        int iy = y, ix = xx, Hi = p.H, Wi = p.W;
+        if constexpr (GEO == 0) {
+          if (p.taps == 9) {
+            iy = y + tap / 3 - 1;
+            ix = xx + tap % 3 - 1;
+          }
+        } else {
+          iy = 2 * y + (tap >> 2) - 1;
+          ix = 2 * xx + (tap & 3) - 1;
+          Hi = 2 * p.H;
+          Wi = 2 * p.W;
         }
-        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) xv = p.x[(((size_t)n * p.H + iy) * p.W + ix) * p.Cin + ci];
+        if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) xv = p.x[(((size_t)n * Hi + iy) * Wi + ix) * p.Cin + ci];
       }
       xs[r][c] = xv;
     }
@@ -442,7 +458,7 @@ DMX_DEV half4 lds_tr16(const _Float16* p) {
   return __builtin_bit_cast(half4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
                                        (__attribute__((address_space(3))) fp16x4_t*)(p)));
 }
-template <int CO>
+template <int CO, int GEO = 0>
 static __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradParams p) {
   constexpr int DP = CO + 32, XP = 160;  // plane row pitches (halves)
   constexpr int MT = CO / 64;            // 32-row m-tiles per wave
@@ -463,7 +479,9 @@ static __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradParams 
   const int k = k0 + xc;
   const bool kvalid = k < p.K;
   const int tap = kvalid ? k / p.Cin : 0, ci = k - tap * p.Cin;
-  const int ty = p.taps == 9 ? tap / 3 - 1 : 0, tx = p.taps == 9 ? tap % 3 - 1 : 0;
+  const int ty = GEO != 0 ? (tap >> 2) - 1 : p.taps == 9 ? tap / 3 - 1 : 0;
+  const int tx = GEO != 0 ? (tap & 3) - 1 : p.taps == 9 ? tap % 3 - 1 : 0;
+  const int Hi = GEO != 0 ? 2 * p.H : p.H, Wi = GEO != 0 ? 2 * p.W : p.W;  // the gathered map
   unsigned mb = 0u;
   for (int i = lane; i < p.dy_nparts; i += 64) mb = max(mb, p.dy_amax[i]);
 #pragma unroll
@@ -493,9 +511,9 @@ static __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradParams 
         if (rr < 0) { --n; rr += HW; } else if (rr >= HW) { ++n; rr -= HW; }
         int y = (int)((float)rr * rw), xx = rr - y * p.W;
         if (xx < 0) { --y; xx += p.W; } else if (xx >= p.W) { ++y; xx -= p.W; }
-        const int iy = y + ty, ix = xx + tx;
-        if (iy >= 0 && iy < p.H && ix >= 0 && ix < p.W)
-          v = *reinterpret_cast<const floatx4*>(p.x + (((size_t)n * p.H + iy) * p.W + ix) * p.Cin + ci);
+        const int iy = (GEO != 0 ? 2 * y : y) + ty, ix = (GEO != 0 ? 2 * xx : xx) + tx;
+        if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
+          v = *reinterpret_cast<const floatx4*>(p.x + (((size_t)n * Hi + iy) * Wi + ix) * p.Cin + ci);
       }
       rx[i] = v;
     }
@@ -507,8 +525,10 @@ static __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradParams 
     for (int i = 0; i < DI; ++i) {
       if (bias) bs += rd[i];
       floatx4 v = rd[i];
+      if constexpr (GEO != 2) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= a_sc;
+        for (int e = 0; e < 4; ++e) v[e] *= a_sc;
+      }
       half4 h, l;
       split4(v, h, l);
       *reinterpret_cast<half4*>(&Dh[b][dr + DR * i][dc]) = h;
@@ -516,8 +536,13 @@ static __global__ __launch_bounds__(256) void wgrad_x3_kernel(const WgradParams 
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      floatx4 v = rx[i];
+      if constexpr (GEO == 2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] *= a_sc;
+      }
       half4 h, l;
-      split4(rx[i], h, l);
+      split4(v, h, l);
       *reinterpret_cast<half4*>(&Xh[b][xr + 8 * i][xc]) = h;
       *reinterpret_cast<half4*>(&Xl[b][xr + 8 * i][xc]) = l;
     }

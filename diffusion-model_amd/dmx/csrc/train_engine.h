@@ -592,9 +592,14 @@ static const unsigned* dy_amax(Run& R, const float* dy, size_t n, int* parts) {
 static bool wgrad_fast(int Cin, int Cout) { return Cin % 64 == 0 && Cout % 64 == 0; }
 
 // weight gradient of a conv3x3 (taps 9) / Linear (taps 1) over NHWC input x and NHWC dY
+// geo 1 / 2 (taps 16, WgradParams): the VAE's Conv2d / ConvTranspose2d 4x4 s2 p1 — rows on the small
+// H x W map, x on the 2H x 2W map; geo 2 swaps the operands' roles (dy = the layer input, x = dY)
 static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, int Cin, int Cout, int taps,
-                  int cin_real, float* grad, float* bias_grad_out = nullptr) {
+                  int cin_real, float* grad, float* bias_grad_out = nullptr, int geo = 0) {
   const int M = N * H * W, K = taps * Cin;
+  const size_t xel = (size_t)M * Cin * (geo != 0 ? 4 : 1);  // elements of the gathered operand
+  if ((geo != 0) != (taps == 16)) throw Error(DMX_E_INTERNAL, "wgrad: 16 taps go with the stride-2 geometries");
+  if (geo == 2 && bias_grad_out != nullptr) throw Error(DMX_E_INTERNAL, "wgrad: no bias sums with swapped operands");
   const bool fast = wgrad_fast(Cin, Cout);
   const int co_t = fast && Cout % 128 == 0 ? 128 : 64;  // wgrad_x3_kernel<128>: X staged once per 128 Cout
   const int bxy = cdiv(Cout, co_t) * cdiv(K, fast ? 128 : 64);
@@ -609,15 +614,28 @@ static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, 
   // bias gradient: column sums of dY, from the fast kernel's k-tile-0 blocks (per split)
   float* bpart = (bias_grad_out != nullptr && fast) ? R.ws.get<float>((size_t)splits * Cout) : nullptr;
   int nparts = 0;
-  const unsigned* amax = fast ? dy_amax(R, dy, (size_t)M * Cout, &nparts) : nullptr;  // (x3 products)
+  // (x3 products: the scale of the operand that holds dY — the gathered one with swapped roles)
+  const unsigned* amax = !fast ? nullptr : geo == 2 ? dy_amax(R, x, xel, &nparts) : dy_amax(R, dy, (size_t)M * Cout, &nparts);
   if (!R.plan) {
     check_range(R, dy, (size_t)M * Cout * 4, "wgrad dY");
-    check_range(R, x, (size_t)M * Cin * 4, "wgrad X");
+    check_range(R, x, xel * 4, "wgrad X");
     WgradParams p{dy, x, N, H, W, Cin, Cout, taps, M, K, rps, part, bpart, amax, nparts};
-    R.begin("wgrad_kernel", 2.0 * M * (double)Cout * K, 4.0 * ((double)M * (Cout + Cin) + (double)splits * Cout * K));
-    if (fast && co_t == 128) wgrad_x3_kernel<128><<<dim3(Cout / 128, cdiv(K, 128), splits), 256, 0, R.st>>>(p);
-    else if (fast) wgrad_x3_kernel<64><<<dim3(Cout / 64, cdiv(K, 128), splits), 256, 0, R.st>>>(p);
-    else wgrad_kernel<<<dim3(cdiv(Cout, 64), cdiv(K, 64), splits), 256, 0, R.st>>>(p);
+    R.begin("wgrad_kernel", 2.0 * M * (double)Cout * K, 4.0 * ((double)M * Cout + (double)xel + (double)splits * Cout * K));
+    const dim3 g128(Cout / 128, cdiv(K, 128), splits), g64(Cout / 64, cdiv(K, 128), splits);
+    const dim3 gf(cdiv(Cout, 64), cdiv(K, 64), splits);
+    if (geo == 0) {
+      if (fast && co_t == 128) wgrad_x3_kernel<128><<<g128, 256, 0, R.st>>>(p);
+      else if (fast) wgrad_x3_kernel<64><<<g64, 256, 0, R.st>>>(p);
+      else wgrad_kernel<0><<<gf, 256, 0, R.st>>>(p);
+    } else if (geo == 1) {
+      if (fast && co_t == 128) wgrad_x3_kernel<128, 1><<<g128, 256, 0, R.st>>>(p);
+      else if (fast) wgrad_x3_kernel<64, 1><<<g64, 256, 0, R.st>>>(p);
+      else wgrad_kernel<1><<<gf, 256, 0, R.st>>>(p);
+    } else {
+      if (fast && co_t == 128) wgrad_x3_kernel<128, 2><<<g128, 256, 0, R.st>>>(p);
+      else if (fast) wgrad_x3_kernel<64, 2><<<g64, 256, 0, R.st>>>(p);
+      else wgrad_kernel<1><<<gf, 256, 0, R.st>>>(p);  // (fp32: no operand scale, the gather alone)
+    }
     R.end();
     HIPCHK(hipGetLastError());
     wgrad_finish_kernel<<<(int)(((size_t)Cout * K + 63) / 64), 256, 0, R.st>>>(part, splits, Cout, Cin, cin_real, taps, grad);

@@ -359,6 +359,41 @@ class NativeModel:
                                           ctypes.c_void_p(_stream(x.device))))
         return z, kl
 
+    # ---- VAE training (include/dmx.h dmx_vae_train_forward / dmx_vae_train_backward) ---------
+    def vae_train_forward(self, x, eps):
+        """VAE.forward's network part with a tape: x (n,3,h,w), eps (n,4,h/8,w/8) = the caller's randn
+        draw -> (x_recon, z, per-sample KL (n,), tape id)."""
+        require_cuda(x, "x")
+        n, c, h, w = x.shape
+        dev = x.device
+        x = x.detach().to(dtype=torch.float32).contiguous()
+        eps = eps.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if c != 3 or h % 8 or w % 8 or tuple(eps.shape) != (n, 4, h // 8, w // 8):
+            raise ValueError(f"vae_train_forward: x must be (n,3,8a,8b) and eps (n,4,a,b); got {tuple(x.shape)}, "
+                             f"{tuple(eps.shape)}")
+        x_recon = torch.empty_like(x)
+        z = torch.empty_like(eps)
+        kl = torch.empty((n,), device=dev, dtype=torch.float32)
+        tid = ctypes.c_int64()
+        with torch.cuda.device(dev):
+            check(self.lib.dmx_vae_train_forward(self.handle, _ptr(x), _ptr(eps), n, h, w, _ptr(x_recon), _ptr(z),
+                                                 _ptr(kl), ctypes.byref(tid), ctypes.c_void_p(_stream(dev))))
+        self._live_train = (x, eps)
+        return x_recon, z, kl, int(tid.value)
+
+    def vae_train_backward(self, tape_id: int, d_recon=None, d_z=None, d_kl=None) -> Dict[str, torch.Tensor]:
+        """dLoss/dparam for every state_dict key, given the cotangents of x_recon, z and the per-sample
+        KL (None = 0)."""
+        dev = self.device
+        grads = {name: torch.empty(shape, device=dev, dtype=torch.float32) for name, shape in self.keys}
+        ptrs = (ctypes.c_void_p * len(self.keys))(*[grads[name].data_ptr() for name, _ in self.keys])
+        cot = [None if d is None else d.to(device=dev, dtype=torch.float32).contiguous() for d in (d_recon, d_z, d_kl)]
+        with torch.cuda.device(dev):
+            check(self.lib.dmx_vae_train_backward(self.handle, int(tape_id), _ptr(cot[0]), _ptr(cot[1]), _ptr(cot[2]),
+                                                  ptrs, len(self.keys), ctypes.c_void_p(_stream(dev))))
+        self._live_bwd = tuple(cot)
+        return grads
+
 
 def _check_state(x: torch.Tensor, what: str) -> None:
     """The step kernels read / write x as contiguous fp32 NCHW on the device."""

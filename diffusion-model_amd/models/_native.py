@@ -11,7 +11,8 @@ device by ``NativeModel.refresh``) and every call after that is a native launch.
 With autograd recording (grad mode on, trainable parameters) the U-Nets run the native
 training forward and backward (``_NativeTrainFn``, include/dmx.h dmx_train_forward /
 dmx_train_backward): ``loss.backward()`` of the reference training loop
-(train_latent_cond.py:148-162) fills every parameter's ``.grad``.
+(train_latent_cond.py:148-162) fills every parameter's ``.grad``.  The VAE does the same through
+``_NativeVaeTrainFn`` (dmx_vae_train_forward / dmx_vae_train_backward) for train_vae.py's step.
 """
 from __future__ import annotations
 
@@ -120,3 +121,24 @@ class _NativeTrainFn(torch.autograd.Function):
                       or (d_eps is None and n.startswith("out.")))
             out.append(None if unused else grads[n])
         return (None, None, None, None, None, None, None, *out)
+
+
+class _NativeVaeTrainFn(torch.autograd.Function):
+    """Native forward with a tape / native backward of VAE.forward's network part (models/vae.py:51-69).
+
+    Inputs after (module, names): x, eps (the randn draw of encode), *parameters (named_parameters
+    order); outputs (x_recon, z, kl_per_sample).  Gradients flow to the parameters only (x and eps take
+    none); an output the loss does not use contributes a zero cotangent."""
+
+    @staticmethod
+    def forward(ctx, module, names, x, eps, *params):
+        nm = module.native()
+        x_recon, z, kl, tape = nm.vae_train_forward(x, eps)
+        ctx.nm, ctx.tape, ctx.names = nm, tape, names
+        ctx.set_materialize_grads(False)
+        return x_recon, z, kl
+
+    @staticmethod
+    def backward(ctx, d_recon, d_z, d_kl):
+        grads = ctx.nm.vae_train_backward(ctx.tape, d_recon, d_z, d_kl)
+        return (None, None, None, None, *[grads[n] for n in ctx.names])

@@ -9,6 +9,11 @@ conv3x3 / conv4x4-stride-2 implicit GEMMs, GroupNorm(8)+GELU, then mu / logvar h
 reparameterisation and the KL term in one tail kernel).  The sampler itself only needs
 the latent shape of a zero dummy, which ``diff.Diffuser`` derives analytically while
 replaying the encoder's RNG draw.
+
+``forward`` with autograd recording (grad mode on, trainable parameters — train_vae.py's
+``_, _, loss, _ = vae(x); loss.backward()``) runs the native training step (dmx_vae_train_forward /
+dmx_vae_train_backward through ``_NativeVaeTrainFn``): ``loss.backward()`` fills every parameter's
+``.grad``.  Under ``torch.no_grad()`` or with frozen parameters it is the inference path above.
 """
 from __future__ import annotations
 
@@ -16,7 +21,7 @@ import torch
 
 from dmx import _lib
 from models._modules import build_vae
-from models._native import NativeBacked
+from models._native import NativeBacked, _NativeVaeTrainFn
 
 
 def latent_hw(h: int, w: int):
@@ -47,7 +52,8 @@ class VAE(NativeBacked):
 
     # ---- native ------------------------------------------------------------------------
     def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """z (B,4,h,w) -> images (B,3,8h,8w) in [0,1] (models/vae.py:64-69)."""
+        """z (B,4,h,w) -> images (B,3,8h,8w) in [0,1] (models/vae.py:64-69).  Inference only: called
+        on its own it builds no autograd graph (training goes through ``forward``)."""
         img, _ = self.native().decode(z, want_img=True, want_u8=False)
         return img
 
@@ -61,7 +67,8 @@ class VAE(NativeBacked):
         implicit GEMMs + GN(8)+GELU, then the mu / logvar heads, reparameterisation and KL in one
         tail kernel).  The randn_like(std) draw is made here with torch on x's device, so the
         global RNG stream advances exactly as in the reference.  Image sides must be multiples
-        of 8 (the three stride-2 convs halve them exactly)."""
+        of 8 (the three stride-2 convs halve them exactly).  Inference only: called on its own it
+        builds no autograd graph (training goes through ``forward``)."""
         n, _, h, w = x.shape
         hl, wl = latent_hw(h, w)
         eps = torch.randn((n, self.z_channels, hl, wl), device=x.device, dtype=torch.float32)
@@ -69,10 +76,29 @@ class VAE(NativeBacked):
         return z, kl.mean()
 
     def forward(self, x):
-        """models/vae.py:71-76, forward only: native encode (same randn_like draw) -> native
-        decode -> recon MSE + 1e-6 * KL, all on x's device.  Returns (x_recon, z, loss,
-        {'recon_mse', 'kl'}).  No autograd graph: VAE training stays out of dmx scope."""
+        """models/vae.py:71-76 -> (x_recon, z, loss, {'recon_mse', 'kl'}), all on x's device: recon MSE +
+        1e-6 * KL over native encode (same randn_like draw) -> native decode.  With autograd
+        recording and trainable parameters the network runs as the native training step
+        (_NativeVaeTrainFn) and the loss is the torch expression over its outputs, so
+        ``loss.backward()`` reaches every parameter; otherwise no graph is built."""
+        if self._dmx_training():
+            return self._dmx_train_forward_vae(x)
         z, kl = self.encode(x)
         x_recon = self.decode(z)
+        recon = torch.nn.functional.mse_loss(x_recon, x.float(), reduction="mean")
+        return x_recon, z, recon + 1e-6 * kl, {"recon_mse": recon.detach(), "kl": kl.detach()}
+
+    def _dmx_train_forward_vae(self, x):
+        if x.requires_grad:
+            raise NotImplementedError("dmx training computes parameter gradients only (x requires grad)")
+        bad = [n for n, p in self.named_parameters() if p.dtype != torch.float32 or not p.is_contiguous()]
+        if bad:
+            raise NotImplementedError(f"dmx training needs contiguous fp32 parameters ({bad[0]})")
+        n, _, h, w = x.shape
+        hl, wl = latent_hw(h, w)
+        eps = torch.randn((n, self.z_channels, hl, wl), device=x.device, dtype=torch.float32)  # encode's draw
+        names = [k for k, _ in self.named_parameters()]
+        x_recon, z, kl_ps = _NativeVaeTrainFn.apply(self, names, x, eps, *self.parameters())
+        kl = kl_ps.mean()
         recon = torch.nn.functional.mse_loss(x_recon, x.float(), reduction="mean")
         return x_recon, z, recon + 1e-6 * kl, {"recon_mse": recon.detach(), "kl": kl.detach()}

@@ -40,7 +40,7 @@ extern "C" {
 #define DMX_UNET_COND_GEOM 1 /* models/unet_cond_geom.py:26 UnetCondWithGeomHead */
 #define DMX_UNET_COND 2      /* models/unet_cond.py:102    UnetCond               */
 #define DMX_UNET 3           /* models/unet.py:101          Unet (unconditional)  */
-#define DMX_VAE 4            /* models/vae.py:6             VAE (decoder only)    */
+#define DMX_VAE 4            /* models/vae.py:6             VAE                   */
 
 typedef struct dmx_ctx dmx_ctx;
 typedef struct dmx_model dmx_model;
@@ -192,6 +192,23 @@ int dmx_train_forward(dmx_model* m, const float* x, const int64_t* t, const int6
 int dmx_train_backward(dmx_model* m, int64_t tape_id, const float* d_eps, const float* d_geom, float* const* grads,
                        int n_grads, void* stream);
 
+/* ---- VAE training step (replaces the forward + loss.backward() of VAE.forward in train_vae.py,
+ * models/vae.py:51-76; widths 3 / 4 / 64, image sides multiples of 8) -------------------------------
+ * dmx_vae_train_forward: what dmx_vae_encode followed by dmx_vae_decode computes, with fp32 semantics
+ * (x3 split GEMMs with device-side weight scales whatever the model's precision, as
+ * dmx_train_forward), recording a tape owned by the model (raw conv outputs, GroupNorm(8) statistics
+ * per (sample, group), activations, mu, logvar, the sigmoid output; one tape per model: a later forward
+ * replaces it).  x: (n,3,h,w); eps: (n,4,h/8,w/8) = the caller's randn draw; x_recon: (n,3,h,w) out;
+ * z: (n,4,h/8,w/8) out; kl: (n,) per-sample KL out.  n * h * w < 2^24.
+ * dmx_vae_train_backward: d_recon (n,3,h,w), d_z (n,4,h/8,w/8), d_kl (n,) — the cotangents of the
+ * three outputs, any of them NULL = zero; writes dLoss/dparam for every state_dict key into grads[i]
+ * (dmx_model_cfg_key order).  No gradient for x.  Every reduction runs in a fixed order: the same
+ * step twice gives bit-identical gradients. */
+int dmx_vae_train_forward(dmx_model* m, const float* x, const float* eps, int n, int h, int w, float* x_recon, float* z,
+                          float* kl, int64_t* tape_id, void* stream);
+int dmx_vae_train_backward(dmx_model* m, int64_t tape_id, const float* d_recon, const float* d_z, const float* d_kl,
+                           float* const* grads, int n_grads, void* stream);
+
 /* ---- measurement: one eager step with a HIP event pair around every launch -----------
  * Fills up to `cap` records (kernel name as rocprofv3 shows it, layer label, algorithmic
  * FLOPs and HBM bytes of that launch, and its event-timed duration in ms). */
@@ -225,7 +242,8 @@ int dmx_attn_core_backward(const float* qkv, const float* o, const float* dout, 
  * copied or -1; host == NULL resets the table and the launch counter.  tools/wino_stamps.py reads them. */
 int dmx_diag_wino_stamps(unsigned long long* host, int cap);
 
-/* Bytes of device workspace currently held by a model (diagnostics). */
+/* Bytes of device workspace currently held by a model (diagnostics): the inference workspace plus,
+ * once a training step ran, the tape and the backward workspace. */
 int64_t dmx_model_workspace_bytes(const dmx_model* m);
 
 #ifdef __cplusplus
