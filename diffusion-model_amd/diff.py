@@ -17,6 +17,10 @@ What changes is where the work happens:
       index); the T loop then runs as replayed hipGraphs with no host round trip.
 * Schedule tables are built on the host with the reference's fp32 torch ops, so
   the per-t coefficients are bit-identical to the reference CPU path.
+* Few-step sampling (not in the reference): ``sample_latent_cond(..., sampler="ddim",
+  steps=S, eta=...)`` runs S strided DDIM steps through the same native step and graph
+  loop (``ddim_timesteps`` / ``ddim_tables`` / ``ddim_step``); the defaults leave the
+  DDPM path untouched.
 """
 from __future__ import annotations
 
@@ -129,6 +133,55 @@ class Diffuser:
             sd = torch.sqrt((1 - a) * (1 - abp) / (1 - ab))
             self._tables[key] = tuple(v.contiguous().to(device) for v in (c1, c2, sd))
         return self._tables[key]
+
+    # ---- strided (DDIM) schedule: one row per position p = 1..S, index p-1 ---------------------
+    def ddim_timesteps(self, steps: int) -> List[int]:
+        """The S = `steps` timesteps of the strided sampler, ascending: tau_i = ceil(i T / S), i = 1..S
+        (tau_S = T; S = T gives 1..T)."""
+        T, S = int(self.num_timesteps), int(steps)
+        if not 1 <= S <= T:
+            raise ValueError(f"steps must be in [1, {T}] (got {steps})")
+        return [(i * T + S - 1) // S for i in range(1, S + 1)]
+
+    def ddim_tables(self, steps: int, eta: float = 0.0, device="cpu"):
+        """(t_map, k_e, k_a, k_s, k_d, k_n) of the DDIM step (Song et al. 2021, eq. 12) from
+        t = tau_p to s = tau_{p-1} (tau_0 = 0, alpha_bar 1), per position p at index p-1:
+        k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_s = sqrt(ab[s]),
+        k_n = sigma = eta sqrt((1-ab[s])/(1-ab[t])) sqrt(1-ab[t]/ab[s]), k_d = sqrt(max(1-ab[s]-sigma^2, 0)),
+        so that x0 = (x - k_e eps)/k_a and x' = k_s x0 + k_d eps + k_n noise.  Computed in float64 from
+        the fp32 alpha_bars and rounded to fp32 once; cached per (steps, eta, device)."""
+        eta = float(eta)
+        if not 0.0 <= eta <= 1.0:
+            raise ValueError(f"eta must be in [0, 1] (got {eta})")
+        key = (int(steps), eta, str(device))
+        cache = self.__dict__.setdefault("_ddim_tables", {})
+        if key not in cache:
+            tau = self.ddim_timesteps(steps)
+            ab = torch.cat([torch.ones(1, dtype=torch.float64), self._host[1].double()])  # ab[0] := 1
+            t = torch.tensor(tau, dtype=torch.long)
+            s = torch.tensor([0] + tau[:-1], dtype=torch.long)
+            ab_t, ab_s = ab[t], ab[s]
+            sigma = eta * torch.sqrt((1 - ab_s) / (1 - ab_t)) * torch.sqrt(1 - ab_t / ab_s)
+            k_d = torch.sqrt(torch.clamp(1 - ab_s - sigma * sigma, min=0.0))
+            tabs = (torch.sqrt(1 - ab_t), torch.sqrt(ab_t), torch.sqrt(ab_s), k_d, sigma)
+            cache[key] = (t.contiguous().to(device),) + tuple(v.float().contiguous().to(device) for v in tabs)
+        return cache[key]
+
+    @staticmethod
+    def _check_sampler(sampler, steps, eta, T):
+        """Argument rules of the samplers' (sampler, steps, eta) keywords -> True for the strided path."""
+        if sampler == "ddpm":
+            if steps is not None:
+                raise ValueError('sampler="ddpm" walks all timesteps and takes no `steps`; strided ancestral '
+                                 'sampling is sampler="ddim", eta=1.0')
+            return False
+        if sampler != "ddim":
+            raise ValueError(f'sampler must be "ddpm" or "ddim" (got {sampler!r})')
+        if steps is None or not 1 <= int(steps) <= int(T):
+            raise ValueError(f'sampler="ddim" needs steps in [1, {T}] (got {steps})')
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError(f"eta must be in [0, 1] (got {eta})")
+        return True
 
     # ---- RNG -------------------------------------------------------------------------------
     _NOISE_RING = 3
@@ -250,6 +303,48 @@ class Diffuser:
             raise TypeError(f"unsupported operand type(s) for *: 'Tensor' and '{type(eps).__name__}'")
         return _engine.ddpm_update(x, eps, None, 0.0, t, tables, noise, seed=self._seed() if noise is None else 0)
 
+    def ddim_step(self, model, x, pos, steps, eta=0.0, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
+                  cond_mask=None):
+        """One strided DDIM step at position(s) `pos` ((B,) in [1, steps]) of the `steps`-position
+        schedule: from timestep tau_pos to tau_{pos-1} (ddim_tables).  CFG when guidance_scale > 0 and y
+        is given, otherwise one conditional forward (y defaults to null_label)."""
+        S = len(self.ddim_timesteps(steps))
+        assert (pos >= 1).all() and (pos <= S).all()  # (reads pos back: a device sync, as denoise_cond)
+        return self._ddim_step(model, x, pos, self.ddim_tables(steps, eta, x.device), float(eta) > 0, y,
+                               guidance_scale, null_label, cond_vals, cond_mask)
+
+    def _ddim_step(self, model, x, pos, sched, noisy, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
+                   cond_mask=None):
+        """ddim_step after its checks; `noisy`: the schedule has noise (eta > 0).  Host-noise mode then
+        draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws."""
+        cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
+        g = float(guidance_scale) if cfg else 0.0
+        pos = pos.to(device=x.device, dtype=torch.long)
+        with torch.no_grad():
+            if y is None:
+                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
+            if _native_kind(model) in (1, 2) and x.is_cuda:
+                noise = self._step_noise(x) if noisy else None
+                x_in = x.float().contiguous()
+                out = torch.empty_like(x_in)
+                use = cond_vals is not None and cond_mask is not None
+                model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
+                                    cond_mask if use else None, g, None, noise,
+                                    seed=self._seed() if noisy and noise is None else 0, sched=sched)
+                return out
+
+            t = sched[0][pos - 1]
+
+            def eps_of(labels):
+                e = model(x, t, labels, cond_vals=cond_vals, cond_mask=cond_mask)
+                return e[0] if isinstance(e, (tuple, list)) else e
+
+            eu = eps_of(torch.full_like(y, null_label) if cfg else y)
+            ec = eps_of(y) if cfg else None
+        noise = self._step_noise(x) if noisy else None
+        return _engine.ddim_update(x, eu, ec, g, pos, sched, noise,
+                                   seed=self._seed() if noisy and noise is None else 0)
+
     # ---- loops --------------------------------------------------------------------------------
     def sample(self, model, x_shape=(20, 3, 80, 80)):
         """Pixel-space sampler (diff.py:66-85)."""
@@ -293,14 +388,15 @@ class Diffuser:
         nm = model.native()
         return nm if nm.precision != "fp32" else None
 
-    def _guarded_host_loop(self, model, x, run, on_replay=None):
-        """T steps in chunks of GUARD_CHUNK.  After each chunk the model's range flag is read
-        (dmx_model_range_check); if an operand left the f16 range of the split-precision modes
+    def _guarded_host_loop(self, model, x, run, on_replay=None, total=None, draws=True):
+        """T steps (or `total` positions of a strided schedule) in chunks of GUARD_CHUNK.  After each
+        chunk the model's range flag is read (dmx_model_range_check); if an operand left the f16 range of the split-precision modes
         the chunk is replayed from its start — same x, same CPU-generator state, hence the same
-        draws — in exact-fp32 MFMA mode.  `run(i_from, i_to, x)` advances t = i_from .. i_to + 1."""
-        T = self.num_timesteps
+        draws — in exact-fp32 MFMA mode.  `run(i_from, i_to, x)` advances t = i_from .. i_to + 1.
+        draws=False: the steps draw no noise (DDIM with eta = 0), so nothing is prefetched."""
+        T = self.num_timesteps if total is None else int(total)
         nm = self._guard_target(model) if x.is_cuda else None
-        prefetch = x.is_cuda and self.noise_source == "host" and _native_kind(model) != 0
+        prefetch = draws and x.is_cuda and self.noise_source == "host" and _native_kind(model) != 0
         i = T
         while i >= 1:
             j = max(i - self.GUARD_CHUNK, 0)
@@ -457,8 +553,17 @@ class Diffuser:
         cond_mask=None,
         key_order: Optional[List[str]] = None,
         class_keys: Optional[Dict[int, List[str]]] = None,
+        sampler: str = "ddpm",
+        steps: Optional[int] = None,
+        eta: float = 0.0,
     ):
-        """Class + numeric-condition latent sampler (diff.py:174-369)."""
+        """Class + numeric-condition latent sampler (diff.py:174-369).
+
+        sampler="ddim", steps=S (1 <= S <= num_timesteps), eta in [0, 1]: S strided DDIM steps over
+        ddim_timesteps(S) instead of all T (eta = 0 deterministic, eta = 1 strided ancestral sampling).
+        Draw order in host-noise mode with eta > 0 is the DDPM sampler's (optional encode draw, x_T, one
+        global draw per step); eta = 0 draws nothing after x_T."""
+        ddim = (int(steps), float(eta)) if self._check_sampler(sampler, steps, eta, self.num_timesteps) else None
         device = self.device
         items = self._norm_counts(class_counts)
         y_list: List[int] = []
@@ -476,16 +581,19 @@ class Diffuser:
             C, Hlat, Wlat = z_shape
 
         x = self._randn((B, C, Hlat, Wlat), device)
-        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress)
+        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, ddim)
         if vae is None:
             return x
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         return self._decode(vae, x, to_pil)
 
-    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress):
-        """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop)."""
-        T = self.num_timesteps
+    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, ddim=None):
+        """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
+        ddim = (S, eta): the strided loop instead — the counter walks the S positions of
+        ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and replay."""
+        T = self.num_timesteps if ddim is None else ddim[0]
+        sched = self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None
         native = _native_kind(model) in (1, 2) and x.is_cuda and guidance_scale and guidance_scale > 0
         bar = tqdm(total=T, desc="Sampling (cond+numeric)") if progress else None
         if native and self.noise_source == "device":
@@ -493,7 +601,8 @@ class Diffuser:
             nm = model.native()
             x = x.contiguous().clone()
             t_dev = torch.full((1,), T, device=x.device, dtype=torch.long)
-            tables = self.coef_tables(x.device, clamp_prev=True)
+            tables = self.coef_tables(x.device, clamp_prev=True) if sched is None else None
+            skw = dict(sched=sched) if sched is not None else {}  # (the DDPM calls stay as they were)
             seed = self._seed()
             v, m = vals.float().contiguous(), msk.float().contiguous()
             guard = self._guard_target(model)
@@ -503,13 +612,13 @@ class Diffuser:
                     k = min(self.GUARD_CHUNK, T - done)
                     x0 = x.clone() if guard is not None else None
                     nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k, seed=seed,
-                                   use_graph=self.use_graph)
+                                   use_graph=self.use_graph, **skw)
                     if guard is not None and guard.range_tripped():
                         x.copy_(x0)
                         t_dev.fill_(T - done)
                         with guard.precision_override("fp32"):
                             nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k,
-                                           seed=seed, use_graph=self.use_graph)
+                                           seed=seed, use_graph=self.use_graph, **skw)
                         guard.range_tripped()
                         self.range_fallbacks += 1
                     done += k
@@ -522,13 +631,17 @@ class Diffuser:
         def run(i_from, i_to, x):
             for i in range(i_from, i_to, -1):  # i in [1, T]: denoise_cond's assert holds by construction
                 t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
-                x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk)
+                if sched is None:
+                    x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk)
+                else:  # t holds the position
+                    x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, guidance_scale, null_label, vals,
+                                        msk)
                 if bar is not None:
                     bar.update(1)
             return x
 
         with torch.no_grad():
-            x = self._guarded_host_loop(model, x, run)
+            x = self._guarded_host_loop(model, x, run, total=T, draws=ddim is None or ddim[1] > 0)
         if bar is not None:
             bar.close()
         return x

@@ -248,6 +248,7 @@ struct Arena {
 
 struct GraphKey {
   dmx_step_args a;
+  dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
@@ -1668,6 +1669,8 @@ struct FwdIn {
   int64_t* t_next = nullptr;  // multi-step graphs: where the embedding kernel stores t - 1
   bool cond_cached = false;   // multi-step graphs, steps after the first: the cond-MLP rows are
                               // already in the workspace (t-independent, same address every step)
+  const int64_t* t_map = nullptr;  // strided sampling: t holds positions in [1, n_pos] and the
+  int n_pos = 0;                   // timestep is t_map[position - 1] (null: t holds timesteps)
 };
 
 // UnetCond trunk (models/unet_cond_geom.py:52-76): returns the (N,H,W,64) feature
@@ -1686,6 +1689,8 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     e.t_next = in.t_stride == 0 ? in.t_next : nullptr;
     e.t_mod = in.n_x < N ? in.n_x : 0;
     e.tmax = m->ctx->tmax;
+    e.t_map = in.t_map;
+    e.n_pos = in.n_pos;
     e.y = m->kind == DMX_UNET ? nullptr : in.y;
     e.y_null_first = in.y_null_first;
     e.y_null = in.y_null;
@@ -1935,14 +1940,32 @@ static void run_planned(dmx_model* m, hipStream_t st, F&& body) {
   }
 }
 
+// The strided form of the tail: positions in [1, S], one table row per position.
+static void set_sched(StepTailParams& p, const dmx_ddim_sched& sc) {
+  p.tmax = sc.S;
+  p.t_map = sc.t_map;
+  p.k_e = sc.k_e;
+  p.k_a = sc.k_a;
+  p.k_s = sc.k_s;
+  p.k_d = sc.k_d;
+  p.k_n = sc.k_n;
+}
+
 // t_next (multi-step sample-loop graphs): the step's t - 1 is stored there by the embedding kernel.
-static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false) {
+// sc (strided sampling, include/dmx.h dmx_ddim_sched): a.t holds positions, the tail applies the
+// DDIM update from sc's tables and a.c1 / c2 / sd / T are not read.
+static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false,
+                      const dmx_ddim_sched* sc = nullptr) {
   dmx_model* m = R.m;
   const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
   const int N = cfg ? 2 * a.n : a.n;
   FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
   in.t_next = t_next;
   in.cond_cached = cond_cached;
+  if (sc != nullptr) {
+    in.t_map = sc->t_map;
+    in.n_pos = sc->S;
+  }
   float* feat = unet_trunk(R, in, N, a.h, a.w);
   if (R.plan) return;
   StepTailParams p;
@@ -1959,33 +1982,52 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
   p.x_out = a.x_out;
   p.t = a.t;
   p.t_stride = a.t_stride;
-  p.tmax = a.T;
-  p.c1 = a.c1;
-  p.c2 = a.c2;
-  p.sd = a.sd;
   p.noise = a.noise;
   p.seed = a.seed;
   p.sample_offset = a.sample_offset;
   p.range_flag = m->range_flag;
-  R.layer = "out+cfg+ddpm";
+  const bool ddim = sc != nullptr;
+  if (ddim) {
+    set_sched(p, *sc);
+  } else {
+    p.tmax = a.T;
+    p.c1 = a.c1;
+    p.c2 = a.c2;
+    p.sd = a.sd;
+  }
+  R.layer = ddim ? "out+cfg+ddim" : "out+cfg+ddpm";
   if (p.Co == 4 && p.feat != nullptr) {
     dim3 grid(cdiv(p.HW, 16), a.n);
     R.begin("step_tail4_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    step_tail4_kernel<<<grid, 256, 0, R.st>>>(p);
+    if (ddim) step_tail4_kernel<true><<<grid, 256, 0, R.st>>>(p);
+    else step_tail4_kernel<false><<<grid, 256, 0, R.st>>>(p);
   } else {
     dim3 grid(cdiv(p.HW, 256), a.n);
     R.begin("step_tail_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    step_tail_kernel<<<grid, 256, 0, R.st>>>(p);
+    if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
+    else step_tail_kernel<false><<<grid, 256, 0, R.st>>>(p);
   }
   R.end();
   HIPCHK(hipGetLastError());
 }
 
-static void validate_step(dmx_model* m, const dmx_step_args* a) {
+static void validate_sched(const dmx_ddim_sched* sc) {
+  REQUIRE(sc != nullptr, "null schedule");
+  REQUIRE(sc->S >= 1, "schedule needs S >= 1 positions");
+  REQUIRE(sc->t_map && sc->k_e && sc->k_a && sc->k_s && sc->k_d && sc->k_n, "null table in schedule");
+}
+
+// sc != null: the strided calls (a->c1 / c2 / sd / T are ignored there)
+static void validate_step(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc = nullptr) {
   REQUIRE(a != nullptr, "null step args");
   check_shapes(m, a->n, a->h, a->w);
-  REQUIRE(a->x_in && a->x_out && a->t && a->c1 && a->c2 && a->sd, "null tensor in step args");
-  REQUIRE(a->T >= 1, "T must be >= 1");
+  REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
+  if (sc != nullptr) {
+    validate_sched(sc);
+  } else {
+    REQUIRE(a->c1 && a->c2 && a->sd, "null tensor in step args");
+    REQUIRE(a->T >= 1, "T must be >= 1");
+  }
   REQUIRE(m->in_ch <= 4, "in_ch must be <= 4");
   if (m->kind != DMX_UNET && a->guidance > 0.f) REQUIRE(a->y != nullptr, "CFG needs y");
   if (m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND)
@@ -2458,12 +2500,25 @@ int dmx_step(dmx_model* m, const dmx_step_args* a, void* stream) {
   });
 }
 
-static constexpr int kGraphSteps = 8;
-
-int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
+int dmx_step_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, void* stream) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
-    validate_step(m, a);
+    validate_sched(sched);
+    validate_step(m, a, sched);
+    ensure_planes(m, (hipStream_t)stream);
+    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, sched); });
+  });
+}
+
+static constexpr int kGraphSteps = 8;
+
+// dmx_sample_loop (sc == null) and dmx_sample_loop_ddim: the scalar a->t counts down by one per
+// step either way — timesteps in the first, positions of the schedule in the second.
+static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc, int steps, int use_graph,
+                            void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr, "null model");
+    validate_step(m, a, sc);
     REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
     REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
     REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
@@ -2473,7 +2528,7 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
     int64_t* tdev = const_cast<int64_t*>(a->t);
     if (!use_graph) {
       for (int i = 0; i < steps; ++i) {
-        run_planned(m, st, [&](Run& R) { step_body(R, *a); });
+        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc); });
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
         HIPCHK(hipGetLastError());
       }
@@ -2482,6 +2537,20 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
     GraphKey key;
     std::memset(&key, 0, sizeof(key));
     std::memcpy(&key.a, a, sizeof(dmx_step_args));
+    if (sc != nullptr) {
+      // the strided graphs read the schedule instead of c1 / c2 / sd / T: those leave the key, the
+      // schedule (member by member: the key is compared bytewise, padding must stay zero) enters
+      // it, and S >= 1 keeps every strided key apart from the DDPM keys (sched all zero)
+      key.a.c1 = key.a.c2 = key.a.sd = nullptr;
+      key.a.T = 0;
+      key.sched.t_map = sc->t_map;
+      key.sched.k_e = sc->k_e;
+      key.sched.k_a = sc->k_a;
+      key.sched.k_s = sc->k_s;
+      key.sched.k_d = sc->k_d;
+      key.sched.k_n = sc->k_n;
+      key.sched.S = sc->S;
+    }
     key.table_gen = m->ctx->table_gen;
     if (!(m->has_graph && key == m->gkey)) {
       drop_graph(m);
@@ -2491,7 +2560,7 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
       m->ws.plan = true;
       {
         Run P{m, st, true, m->ws};
-        step_body(P, *a);
+        step_body(P, *a, nullptr, false, sc);
       }
       ensure_ws(m);
       poison(m->ws_mem, m->ws.off, st);
@@ -2501,7 +2570,7 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       try {
         Run R{m, st, false, m->ws};
-        step_body(R, *a);
+        step_body(R, *a, nullptr, false, sc);
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
       } catch (...) {
         hipGraph_t g;
@@ -2527,7 +2596,7 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
           Run R{m, st, false, m->ws};
           dmx_step_args ak = *a;
           ak.t = (k & 1) ? tscr : tdev;
-          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0);  // cond MLP rows from step 0 of the graph
+          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc);  // cond MLP rows from step 0 of the graph
         }
       } catch (...) {
         hipGraph_t g;
@@ -2548,6 +2617,16 @@ int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_gra
     for (; i + kGraphSteps <= steps; i += kGraphSteps) HIPCHK(hipGraphLaunch(m->gexec_k, st));
     for (; i < steps; ++i) HIPCHK(hipGraphLaunch(m->gexec, st));
   });
+}
+
+int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
+  return sample_loop_impl(m, a, nullptr, steps, use_graph, stream);
+}
+
+int dmx_sample_loop_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, int steps,
+                         int use_graph, void* stream) {
+  const int rc = guarded([&] { validate_sched(sched); });
+  return rc != DMX_OK ? rc : sample_loop_impl(m, a, sched, steps, use_graph, stream);
 }
 
 int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* recs, int cap, int* n_out,
@@ -2617,7 +2696,37 @@ int dmx_ddpm_update(const float* x, float* x_out, const float* eu, const float* 
     p.seed = seed;
     p.sample_offset = sample_offset;
     dim3 grid(cdiv(p.HW, 256), n);
-    step_tail_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    step_tail_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_ddim_update(const float* x, float* x_out, const float* eu, const float* ec, float guidance,
+                    const int64_t* pos, int pos_stride, const dmx_ddim_sched* sched, const float* noise,
+                    uint64_t seed, int64_t sample_offset, int n, int c, int h, int w, void* stream) {
+  return guarded([&] {
+    REQUIRE(x && x_out && eu && pos, "null tensor");
+    validate_sched(sched);
+    REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1, "bad shape");
+    StepTailParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.Co = c;
+    p.B = n;
+    p.HW = h * w;
+    p.cfg = ec != nullptr ? 1 : 0;
+    p.guidance = guidance;
+    p.eps_u = eu;
+    p.eps_c = ec;
+    p.x = x;
+    p.x_out = x_out;
+    p.t = pos;
+    p.t_stride = pos_stride;
+    set_sched(p, *sched);
+    p.noise = noise;
+    p.seed = seed;
+    p.sample_offset = sample_offset;
+    dim3 grid(cdiv(p.HW, 256), n);
+    step_tail_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
     HIPCHK(hipGetLastError());
   });
 }

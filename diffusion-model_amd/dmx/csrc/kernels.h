@@ -40,6 +40,8 @@ struct EmbedParams {
   float* out;                  // [n][hsum]
   int64_t* t_next;             // sample-loop graphs (scalar t): block (0, 0) stores t - 1 here
   const float* cnd;            // [cond_rows][256] cond_mlp outputs (cond_emb_kernel), or null: inline
+  const int64_t* t_map;        // strided sampling: p.t holds positions in [1, n_pos], the network
+  int n_pos;                   // timestep is t_map[position - 1]; null => p.t holds timesteps
 };
 
 // cond_mlp([vals, mask]) (models/unet_cond.py:125-129, 187-190) once per DISTINCT condition row: the
@@ -76,6 +78,7 @@ static __global__ __launch_bounds__(256) void embed_kernel(const EmbedParams p) 
   int64_t t = p.t[(size_t)(p.t_mod ? n % p.t_mod : n) * p.t_stride];
   // the next step's t in the other buffer of a multi-step graph (this step's readers keep p.t)
   if (p.t_next != nullptr && n == 0 && blockIdx.y == 0 && k == 0) *p.t_next = t - 1;
+  if (p.t_map != nullptr) t = p.t_map[(t < 1 ? 1 : (t > p.n_pos ? p.n_pos : t)) - 1];
   t = t < 1 ? 1 : (t > p.tmax ? p.tmax : t);
   float v = p.pos_table[(size_t)(t - 1) * 256 + k];
   if (p.y != nullptr) {
@@ -756,6 +759,10 @@ struct StepTailParams {
   const float* noise;                                 // NCHW or null => Philox
   uint64_t seed; int64_t sample_offset;
   int* range_flag;                                    // set to 1 when eps is not finite (or null)
+  // strided (DDIM) form, the <true> instantiations: t holds positions in [1, tmax], row p - 1 of
+  // the tables belongs to position p and t_map[p - 1] is its network timestep (the noise key)
+  const int64_t* t_map;
+  const float* k_e; const float* k_a; const float* k_s; const float* k_d; const float* k_n;
 };
 
 // Range guard of the split-precision modes: an operand beyond the f16 range (|v| >= 65520)
@@ -777,7 +784,16 @@ DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float 
   const float mu = rnd(x - rnd(c1 * eps)) / c2;
   return mu + rnd(nz * sd);
 }
+// Strided DDIM update (Song et al. 2021, eq. 12) from position p (timestep t) to p - 1 (timestep s):
+//   x0 = (x - k_e*eps) / k_a;  x' = k_s*x0 + k_d*eps + k_n*nz
+// with k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_s = sqrt(ab[s]), k_n = sigma, k_d = sqrt(1-ab[s]-sigma^2)
+// tabulated per position on the host; one rounding per op in torch's evaluation order.
+DMX_DEV float ddim_elem(float x, float eps, float ke, float ka, float ks, float kd, float kn, float nz) {
+  const float x0 = rnd(x - rnd(ke * eps)) / ka;
+  return rnd(rnd(ks * x0) + rnd(kd * eps)) + rnd(kn * nz);
+}
 
+template <bool DDIM>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int n = blockIdx.y;
@@ -812,21 +828,33 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
       ec[c] = p.cfg ? p.eps_c[((size_t)n * Co + c) * p.HW + pix] : 0.f;
     }
   }
+  // t is a position in the strided form: the noise is keyed by its network timestep and skipped
+  // where sigma is 0 (eta = 0, and position 1 always); DDPM: no noise at t = 1
+  float kn = 0.f;
+  if (DDIM) kn = p.k_n[t - 1];
+  const bool noisy = DDIM ? kn != 0.f : t != 1;
   float nz[4] = {0.f, 0.f, 0.f, 0.f};
-  if (t != 1) {
+  if (noisy) {
     if (p.noise != nullptr) {
       for (int c = 0; c < Co; ++c) nz[c] = p.noise[((size_t)n * Co + c) * p.HW + pix];
     } else {
-      const floatx4 r = normal4(p.seed, (uint64_t)t, ((uint64_t)(n + p.sample_offset) * p.HW + pix));
+      const uint64_t key = DDIM ? (uint64_t)p.t_map[t - 1] : (uint64_t)t;
+      const floatx4 r = normal4(p.seed, key, ((uint64_t)(n + p.sample_offset) * p.HW + pix));
       for (int c = 0; c < Co && c < 4; ++c) nz[c] = r[c];
     }
   }
-  const float c1 = p.c1[t - 1], c2 = p.c2[t - 1], sd = p.sd[t - 1];
+  float c1 = 0.f, c2 = 0.f, sd = 0.f, ke = 0.f, ka = 0.f, ks = 0.f, kd = 0.f;
+  if (DDIM) {
+    ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_s[t - 1], kd = p.k_d[t - 1];
+  } else {
+    c1 = p.c1[t - 1], c2 = p.c2[t - 1], sd = p.sd[t - 1];
+  }
   for (int c = 0; c < Co; ++c) {
     const float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
     flag_nonfinite(p.range_flag, eps);
     const size_t idx = ((size_t)n * Co + c) * p.HW + pix;
-    p.x_out[idx] = ddpm_elem(p.x[idx], eps, c1, c2, sd, nz[c]);
+    p.x_out[idx] = DDIM ? ddim_elem(p.x[idx], eps, ke, ka, ks, kd, kn, nz[c])
+                        : ddpm_elem(p.x[idx], eps, c1, c2, sd, nz[c]);
   }
 }
 
@@ -847,6 +875,7 @@ DMX_DEV float group_sum16(float s) {  // sum over aligned 16-lane rows (DPP), sa
   return s;
 }
 
+template <bool DDIM>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -873,19 +902,25 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
   const int c = sub;
   const float u = sub == 0 ? eu[0] : sub == 1 ? eu[1] : sub == 2 ? eu[2] : eu[3];
   const float v = sub == 0 ? ec[0] : sub == 1 ? ec[1] : sub == 2 ? ec[2] : ec[3];
-  float nz = 0.f;
+  float nz = 0.f, kn = 0.f;
+  if (DDIM) kn = p.k_n[t - 1];
+  const bool noisy = DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
   const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
-  if (t != 1) {
+  if (noisy) {
     if (p.noise != nullptr) {
       nz = p.noise[idx];
     } else {
-      const floatx4 r = normal4(p.seed, (uint64_t)t, ((uint64_t)(n + p.sample_offset) * p.HW + pix));
+      const uint64_t key = DDIM ? (uint64_t)p.t_map[t - 1] : (uint64_t)t;
+      const floatx4 r = normal4(p.seed, key, ((uint64_t)(n + p.sample_offset) * p.HW + pix));
       nz = c == 0 ? r[0] : c == 1 ? r[1] : c == 2 ? r[2] : r[3];
     }
   }
   const float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
   flag_nonfinite(p.range_flag, eps);
-  p.x_out[idx] = ddpm_elem(p.x[idx], eps, p.c1[t - 1], p.c2[t - 1], p.sd[t - 1], nz);
+  if (DDIM)
+    p.x_out[idx] = ddim_elem(p.x[idx], eps, p.k_e[t - 1], p.k_a[t - 1], p.k_s[t - 1], p.k_d[t - 1], kn, nz);
+  else
+    p.x_out[idx] = ddpm_elem(p.x[idx], eps, p.c1[t - 1], p.c2[t - 1], p.sd[t - 1], nz);
 }
 
 // conv1x1 64 -> Co + bias into NCHW (models/unet_cond.py:153, the `out` layer).

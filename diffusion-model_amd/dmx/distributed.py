@@ -168,7 +168,8 @@ class ShardedCondSampler:
         self._prefetch = _diff()._NoisePrefetch
 
     def sample(self, class_counts, z_shape=None, guidance_scale: float = 3.0, null_label: int = 0, cond=None,
-               cond_mask=None, decode: bool = True, dummy_input_hw=(224, 224)) -> Optional[torch.Tensor]:
+               cond_mask=None, decode: bool = True, dummy_input_hw=(224, 224), sampler: str = "ddpm",
+               steps: Optional[int] = None, eta: float = 0.0) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -184,9 +185,14 @@ class ShardedCondSampler:
         split-precision range guard: after each chunk every rank's range flag is OR-ed across
         ranks (one 4-byte all-reduce per chunk) and, if any rank saw a non-finite output, EVERY
         rank replays the chunk from its start in exact-fp32 mode (same x, same CPU-generator
-        state / Philox seed) — exactly what the single process does for the whole batch."""
+        state / Philox seed) — exactly what the single process does for the whole batch.
+
+        sampler / steps / eta as in Diffuser.sample_latent_cond: sampler="ddim" walks the `steps`
+        positions of the strided schedule instead of the T timesteps (same chunks, guard and draw
+        order; with eta = 0 no rank draws per-step noise)."""
         ws, rank = world()
         d = self.d
+        ddim = d._check_sampler(sampler, steps, eta, d.num_timesteps)
         items = d._norm_counts(class_counts)
         y_list: List[int] = []
         for cls, num in items:
@@ -204,8 +210,11 @@ class ShardedCondSampler:
         C, H, W = z_shape
         nm = self.model.native() if e > s else None
         guard = d._guard_target(self.model) if nm is not None else None
-        tables = d.coef_tables(dev, clamp_prev=True)
-        T = d.num_timesteps
+        tables = d.coef_tables(dev, clamp_prev=True) if not ddim else None
+        sched = d.ddim_tables(steps, eta, dev) if ddim else None
+        T = int(steps) if ddim else d.num_timesteps  # the loop counter: timesteps, or positions
+        draws = not ddim or float(eta) > 0  # DDIM with eta = 0 draws no per-step noise
+        skw = dict(sched=sched) if ddim else {}  # (the DDPM calls stay exactly as they were)
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
         if d.noise_source == "device":
             seed = torch.tensor([d._seed()], dtype=torch.long)  # drawn after x_T, as _run_cond_loop does
@@ -220,21 +229,24 @@ class ShardedCondSampler:
                 if xs.shape[0] > 0:
                     t_dev.fill_(i_from)
                     nm.sample_loop(xs, t_dev, y, null_label, v, m, float(guidance_scale), tables, i_from - i_to,
-                                   seed=seed, sample_offset=s, use_graph=d.use_graph)
+                                   seed=seed, sample_offset=s, use_graph=d.use_graph, **skw)
                 return xs
         else:
             def run(i_from, i_to, xs):
                 """One global CPU-generator draw per step (this shard's rows kept), made one step
                 ahead on a helper thread into pinned buffers (diff._NoisePrefetch: same generator,
                 same order), so the host draw of the global tensor overlaps the GPU step."""
-                pf = self._prefetch((B, C, H, W), i_from - i_to, rows=(s, e)) if dev.type == "cuda" else None
+                pf = (self._prefetch((B, C, H, W), i_from - i_to, rows=(s, e))
+                      if dev.type == "cuda" and draws else None)
                 try:
                     for i in range(i_from, i_to, -1):
-                        noise = pf.next(dev) if pf is not None else host_noise_slice((B, C, H, W), s, e, dev)
+                        noise = (None if not draws else pf.next(dev) if pf is not None
+                                 else host_noise_slice((B, C, H, W), s, e, dev))
                         if xs.shape[0] > 0:  # an empty shard (B < world size) only keeps the draw order
                             out = torch.empty_like(xs)
                             tt = torch.full((xs.shape[0],), i, dtype=torch.long, device=dev)
-                            nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale), tables, noise)
+                            nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale), tables, noise,
+                                    **skw)
                             xs = out
                 finally:
                     if pf is not None:

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import StepArgs, check
+from ._lib import DdimSched, StepArgs, check
 
 TIME_DIM = 256
 
@@ -255,7 +255,6 @@ class NativeModel:
 
     def _args(self, x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
               sample_offset) -> StepArgs:
-        c1, c2, sd = tables
         n, _, h, w = x_in.shape
         a = StepArgs()
         a.x_in, a.x_out = x_in.data_ptr(), x_out.data_ptr()
@@ -265,23 +264,47 @@ class NativeModel:
         a.vals = vals.data_ptr() if vals is not None else None
         a.mask = mask.data_ptr() if mask is not None else None
         a.guidance = float(guidance)
-        a.c1, a.c2, a.sd, a.T = c1.data_ptr(), c2.data_ptr(), sd.data_ptr(), int(c1.numel())
+        if tables is not None:  # (None: the strided calls, which read their schedule instead)
+            c1, c2, sd = tables
+            a.c1, a.c2, a.sd, a.T = c1.data_ptr(), c2.data_ptr(), sd.data_ptr(), int(c1.numel())
         a.noise = noise.data_ptr() if noise is not None else None
         a.seed, a.sample_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset)
         a.n, a.h, a.w = n, h, w
         return a
 
+    def _sched(self, sched, device) -> DdimSched:
+        """dmx_ddim_sched of a (t_map, k_e, k_a, k_s, k_d, k_n) tuple (Diffuser.ddim_tables) on `device`;
+        makes sure the time table reaches the schedule's last timestep.  That timestep is read back
+        once per schedule: the tuple is kept (alive, so its identity stays valid) with the value."""
+        sc = _sched_struct(sched, device)
+        last = getattr(self, "_sched_last", None)
+        if last is None or last[0] is not sched[0]:
+            last = self._sched_last = (sched[0], int(sched[0][-1].item()))
+        self.ctx.ensure_time_table(last[1])
+        return sc
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1):
-        """One denoising step: CFG (2n batched forward) when guidance > 0 and y given."""
-        self.ctx.ensure_time_table(int(tables[0].numel()))
+             sample_offset=0, t_stride=1, sched=None):
+        """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
+
+        sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
+        positions in [1, S] and `tables` is not read (may be None)."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        if sched is not None:
+            sc = self._sched(sched, x_in.device)
+            tables = None
+        else:
+            self.ctx.ensure_time_table(int(tables[0].numel()))
         t, y, vals, mask, noise = self._norm_inputs(x_in, t, y, vals, mask, noise)
         a = self._args(x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
                        sample_offset)
         with torch.cuda.device(x_in.device):
-            check(self.lib.dmx_step(self.handle, ctypes.byref(a), ctypes.c_void_p(_stream(x_in.device))))
+            st = ctypes.c_void_p(_stream(x_in.device))
+            if sched is not None:
+                check(self.lib.dmx_step_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
+            else:
+                check(self.lib.dmx_step(self.handle, ctypes.byref(a), st))
 
     def step_profile(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
                      t_stride=1, cap=1024):
@@ -303,12 +326,19 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True):
+                    use_graph=True, sched=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
-        needs a non-default stream) ordered against the current stream."""
-        self.ctx.ensure_time_table(int(tables[0].numel()))
+        needs a non-default stream) ordered against the current stream.
+
+        sched (the 6-tuple of Diffuser.ddim_tables): strided DDIM steps; t_dev then holds the
+        position in [1, S] and `tables` is not read (may be None)."""
         _check_state(x, "x")
+        if sched is not None:
+            sc = self._sched(sched, x.device)
+            tables = None
+        else:
+            self.ctx.ensure_time_table(int(tables[0].numel()))
         if t_dev.dtype != torch.long or not t_dev.is_contiguous() or t_dev.device != x.device:
             raise ValueError("sample_loop: t_dev must be a contiguous int64 device scalar on x's device "
                              "(it is decremented in place)")
@@ -317,12 +347,16 @@ class NativeModel:
         cur = torch.cuda.current_stream(x.device)
         side = self.side_stream()
         side.wait_stream(cur)
-        for keep in (x, t_dev, y, vals, mask) + tuple(tables):
+        for keep in (x, t_dev, y, vals, mask) + tuple(sched if sched is not None else tables):
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            check(self.lib.dmx_sample_loop(self.handle, ctypes.byref(a), int(steps), int(use_graph),
-                                           ctypes.c_void_p(side.cuda_stream)))
+            if sched is not None:
+                check(self.lib.dmx_sample_loop_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
+                                                    int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            else:
+                check(self.lib.dmx_sample_loop(self.handle, ctypes.byref(a), int(steps), int(use_graph),
+                                               ctypes.c_void_p(side.cuda_stream)))
         cur.wait_stream(side)
 
     # ---- VAE -----------------------------------------------------------------------------
@@ -427,5 +461,48 @@ def ddpm_update(x, eu, ec, guidance, t, tables, noise=None, seed=0, sample_offse
     with torch.cuda.device(dev):
         check(lib.dmx_ddpm_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(t_c),
                                   1, _ptr(c1), _ptr(c2), _ptr(sd), int(c1.numel()), _ptr(nz_c), int(seed),
+                                  int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+    return out
+
+
+def _sched_struct(sched, device) -> DdimSched:
+    """The C view of a (t_map, k_e, k_a, k_s, k_d, k_n) schedule: int64 / fp32 contiguous tensors of one
+    length S on `device` (Diffuser.ddim_tables builds them so; nothing is converted here, the kernels
+    read the caller's tensors)."""
+    if len(sched) != 6:
+        raise ValueError("sched must be the 6-tuple (t_map, k_e, k_a, k_s, k_d, k_n) of Diffuser.ddim_tables")
+    S = int(sched[0].numel())
+    for i, v in enumerate(sched):
+        want = torch.long if i == 0 else torch.float32
+        if v.dtype != want or v.dim() != 1 or v.numel() != S or not v.is_contiguous() or v.device != device:
+            raise ValueError(f"sched[{i}] must be a contiguous 1-D {want} tensor of {S} entries on {device}")
+    if S < 1:
+        raise ValueError("sched is empty")
+    return DdimSched(*[v.data_ptr() for v in sched], S)
+
+
+def ddim_update(x, eu, ec, guidance, pos, sched, noise=None, seed=0, sample_offset=0):
+    """Standalone strided DDIM update (include/dmx.h dmx_ddim_update) for duck-typed models: returns x'.
+    pos: (n,) positions in [1, S]; sched: the 6-tuple of Diffuser.ddim_tables on x's device.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(x, "x")
+    dev = x.device
+    sc = _sched_struct(sched, dev)
+    x_c = x.to(dtype=torch.float32).contiguous()
+    n, c, h, w = x_c.shape
+    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
+    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
+    nz_c = noise.to(device=dev, dtype=torch.float32).contiguous() if noise is not None else None
+    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
+    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond"), (nz_c, "noise")):
+        if e is not None and tuple(e.shape) != tuple(x_c.shape):
+            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
+    if p_c.numel() != n:
+        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
+    out = torch.empty_like(x_c)
+    with torch.cuda.device(dev):
+        check(lib.dmx_ddim_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
+                                  ctypes.byref(sc), _ptr(nz_c), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                   int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(dev))))
     return out

@@ -148,6 +148,39 @@ int dmx_ddpm_update(const float* x, float* x_out, const float* eu, const float* 
                     const float* noise, uint64_t seed, int64_t sample_offset, int n, int c, int h, int w,
                     void* stream);
 
+/* ---- strided (few-step) sampling: DDIM steps over a sub-sequence of the T timesteps -------
+ * (Song et al. 2021; no reference counterpart — the reference samplers walk all T steps.)
+ * A schedule of S positions: position p in [1, S] stands for the network timestep
+ * t = t_map[p-1] (ascending, t_map[S-1] = T) and its step goes to s = t_map[p-2] (s = 0, with
+ * alpha_bar 1, below position 1).  Row p-1 of the five fp32 tables holds
+ *   k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_s = sqrt(ab[s]), k_n = sigma(eta), k_d = sqrt(1-ab[s]-sigma^2)
+ * and the update is  eps = eu + g*(ec-eu);  x0 = (x - k_e*eps)/k_a;  x' = k_s*x0 + k_d*eps + k_n*noise,
+ * one IEEE rounding per operation in that order.  Noise is neither read nor drawn where k_n == 0;
+ * Philox noise is keyed by (seed, t, global sample index) — the timestep, not the position.
+ * All seven members are device pointers / counts owned by the caller. */
+typedef struct dmx_ddim_sched {
+  const int64_t* t_map; /* [S] int64 */
+  const float* k_e;     /* [S] each */
+  const float* k_a;
+  const float* k_s;
+  const float* k_d;
+  const float* k_n;
+  int S;
+} dmx_ddim_sched;
+
+/* dmx_step / dmx_sample_loop in the strided form: a->t holds POSITIONS in [1, S] (the loop
+ * decrements the position scalar); a->c1, c2, sd and T are ignored and may be NULL / 0.
+ * Everything else is as in the DDPM calls.  A captured graph belongs to one schedule (pointers
+ * and S): another schedule, or the DDPM loop, on the same model captures anew. */
+int dmx_step_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, void* stream);
+int dmx_sample_loop_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, int steps,
+                         int use_graph, void* stream);
+/* Standalone strided update for duck-typed foreign models (ec NULL => eps = eu); pos: device
+ * int64 positions, pos_stride 0 => one value for every sample. */
+int dmx_ddim_update(const float* x, float* x_out, const float* eu, const float* ec, float guidance,
+                    const int64_t* pos, int pos_stride, const dmx_ddim_sched* sched, const float* noise,
+                    uint64_t seed, int64_t sample_offset, int n, int c, int h, int w, void* stream);
+
 /* ---- VAE decode (replaces VAE.decode, vae.py:64-69, plus Diffuser.reverse_to_img's
  * x*255 -> clamp -> uint8, diff.py:58-62) ---------------------------------------------
  * z: (n,4,h,w); img: (n,3,8h,8w) fp32 or NULL; u8: (n,8h,8w,3) uint8 (HWC) or NULL. */

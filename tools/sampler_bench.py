@@ -1,0 +1,143 @@
+"""Strided (DDIM) sampling against the full DDPM walk on one MI355X: prints one JSON line.
+
+  python tools/sampler_bench.py [--rounds 5]
+
+Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
+
+1. ms per step of the graph loops.  The strided loop (S = 50 of T = 1000, eta = 1 so that it draws
+   noise as the DDPM step does) and the DDPM loop alternate in one process, the DDPM leg twice per round
+   (legs ddpm_a, ddim, ddpm_b), so the spread between two measurements of the SAME loop is known.  A model
+   holds the graphs of one loop at a time: every leg first runs 8 steps untimed (capture), then 48 steps
+   (six launches of the 8-step graph) between two device events.  Reported: the median over the rounds.
+2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
+   (ddpm, T = 1000) and (ddim, S = 50, eta = 0): the first call (it captures the graphs) and the best of
+   the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
+   from the steady ones by the sampler's own start-up only.
+
+There is no fallback: without a GPU this fails."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(REPO, "diffusion-model_amd"), REPO):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+B, HW, T, S, GUIDANCE = 64, 32, 1000, 50, 3.0
+WARM, TIMED = 8, 48
+
+
+def make_inputs(dev, seed=0):
+    """bench.py's synthetic inputs: x_T ~ N(0,1), y cycles 1,2,3, cond U[0,1) masked to the class keys."""
+    from diff import CLASS_KEYS, KEY_ORDER
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((B, 4, HW, HW), generator=g)
+    y = torch.tensor([1 + i % 3 for i in range(B)], dtype=torch.long)
+    mask = torch.zeros((B, 12))
+    for i in range(B):
+        for k in CLASS_KEYS[int(y[i])]:
+            mask[i, KEY_ORDER.index(k)] = 1.0
+    vals = torch.rand((B, 12), generator=g) * mask
+    return x.to(dev), y.to(dev), vals.to(dev), mask.to(dev)
+
+
+def loop_legs(nm, d, dev, rounds):
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    tables = d.coef_tables(dev, True)
+    sched = d.ddim_tables(S, 1.0, dev)
+
+    def leg(ddim):
+        start = S if ddim else T
+        kw = dict(seed=1234, sched=sched) if ddim else dict(seed=1234)
+        tab = None if ddim else tables
+        x.copy_(x0)
+        t_dev.fill_(start)
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tab, WARM, **kw)  # captures this loop's graphs
+        x.copy_(x0)
+        t_dev.fill_(start)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tab, TIMED, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == start - TIMED and bool(torch.isfinite(x).all())
+        return e0.elapsed_time(e1) / TIMED
+
+    ms = {"ddpm_a": [], "ddim": [], "ddpm_b": []}
+    leg(False)  # workspace, split planes, time table
+    for _ in range(rounds):
+        ms["ddpm_a"].append(leg(False))
+        ms["ddim"].append(leg(True))
+        ms["ddpm_b"].append(leg(False))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"ms_per_step_ddpm_a": round(med["ddpm_a"], 4), "ms_per_step_ddpm_b": round(med["ddpm_b"], 4),
+            "ms_per_step_ddim": round(med["ddim"], 4),
+            "ddpm_spread_ms": round(abs(med["ddpm_a"] - med["ddpm_b"]), 4),
+            "ddim_minus_ddpm_mean_ms": round(med["ddim"] - 0.5 * (med["ddpm_a"] + med["ddpm_b"]), 4),
+            "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
+
+
+def end_to_end(model, dev):
+    import diff
+    from dmx import synth
+    from models.vae import VAE
+    vae = VAE()
+    vae.load_state_dict(synth.vae_weights(1))
+    vae = vae.to(dev).eval()
+    _, y, vals, mask = make_inputs(dev, seed=11)
+    counts = [(c, int((y == c).sum())) for c in (1, 2, 3)]
+    order = torch.argsort(y, stable=True)  # the sampler lays out classes in count order
+    vals, mask = vals[order].contiguous(), mask[order].contiguous()
+    kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
+              cond_mask=mask)
+    d = diff.Diffuser(T, device=dev)
+    d.noise_source = "device"
+    d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
+    out = {}
+    for name, extra, calls in (("ddim_S50_eta0", dict(sampler="ddim", steps=S, eta=0.0), 4), ("ddpm_T1000", {}, 2)):
+        secs = []
+        for _ in range(calls):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            imgs = d.sample_latent_cond(model, counts, **kw, **extra)
+            secs.append(time.perf_counter() - t0)
+            assert len(imgs) == B and imgs[0].size == (8 * HW, 8 * HW)
+        out[name] = {"first_call_s": round(secs[0], 4), "first_call_images_per_s": round(B / secs[0], 2),
+                     "steady_s": round(min(secs[1:]), 4), "steady_images_per_s": round(B / min(secs[1:]), 2),
+                     "calls_s": [round(v, 4) for v in secs]}
+    out["range_fallbacks"] = d.range_fallbacks
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sampler_bench needs an MI355X: no GPU visible, and there is no fallback")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    import diff
+    from dmx import synth
+    from models.unet_cond_geom import UnetCondWithGeomHead
+    model = UnetCondWithGeomHead()
+    model.load_state_dict(synth.unet_cond_geom_weights(0))
+    model.to(dev).eval()
+    res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
+           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
+           "loops": loop_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds),
+           "end_to_end": end_to_end(model, dev)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
