@@ -20,7 +20,8 @@ What changes is where the work happens:
 * Few-step sampling (not in the reference): ``sample_latent_cond(..., sampler="ddim",
   steps=S, eta=...)`` runs S strided DDIM steps through the same native step and graph
   loop (``ddim_timesteps`` / ``ddim_tables`` / ``ddim_step``); the defaults leave the
-  DDPM path untouched.
+  DDPM path untouched.  ``sampler="dpmpp_2m"`` runs DPM-Solver++(2M) over timesteps uniform in
+  log-SNR through the same step and loop (``dpm_timesteps`` / ``dpm_tables`` / ``dpm_step``).
 """
 from __future__ import annotations
 
@@ -167,6 +168,87 @@ class Diffuser:
             cache[key] = (t.contiguous().to(device),) + tuple(v.float().contiguous().to(device) for v in tabs)
         return cache[key]
 
+    # ---- DPM-Solver++(2M) schedule (Lu et al. 2022, Alg. 2): one row per position, as above -------
+    DPM_SPACINGS = ("logsnr", "uniform")
+
+    def dpm_timesteps(self, steps: int, spacing: str = "logsnr") -> List[int]:
+        """The S = `steps` ascending timesteps of the DPM-Solver++ sampler, tau_S = T.
+        "uniform": ddim_timesteps(S).  "logsnr": uniform in lam[t] = 0.5 ln(ab[t] / (1 - ab[t])) between
+        lam[1] and lam[T] — each grid point goes to the nearest timestep (ties to the smaller), then a
+        forward pass makes the list strictly ascending from tau_1 and a backward pass fits it under
+        tau_S = T.  S = 1 gives [T] and S = T gives 1..T."""
+        if spacing not in self.DPM_SPACINGS:
+            raise ValueError(f'spacing must be "logsnr" or "uniform" (got {spacing!r})')
+        T, S = int(self.num_timesteps), int(steps)
+        if not 1 <= S <= T:
+            raise ValueError(f"steps must be in [1, {T}] (got {steps})")
+        if spacing == "uniform":
+            return self.ddim_timesteps(S)
+        if S == 1:
+            return [T]
+        ab = self._host[1].double()
+        lam = 0.5 * torch.log(ab / (1 - ab))  # lam[t] at index t - 1, strictly decreasing
+        grid = lam[0] + torch.arange(S, dtype=torch.float64) / (S - 1) * (lam[T - 1] - lam[0])
+        # argmin returns the first minimum: ties go to the smaller t
+        tau = [int(torch.argmin(torch.abs(lam - g))) + 1 for g in grid]
+        for i in range(1, S):
+            tau[i] = max(tau[i], tau[i - 1] + 1)
+        tau[S - 1] = T
+        for i in range(S - 2, -1, -1):
+            tau[i] = min(tau[i], tau[i + 1] - 1)
+        return tau
+
+    def dpm_tables(self, steps: int, spacing: str = "logsnr", device="cpu"):
+        """(t_map, k_e, k_a, k_x, k_c, k_p) of the DPM-Solver++(2M) step from t = tau_p to s = tau_{p-1}
+        (tau_0 = 0, alpha_bar 1), u = tau_{p+1} being the step before, per position p at index p-1:
+        k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_x = sqrt(1-ab[s]) / sqrt(1-ab[t]),
+        m = sqrt(ab[s]) - k_x sqrt(ab[t]) (= -alpha_s expm1(-h), h = lam[s] - lam[t]); first-order rows
+        (p = S and p = 1): k_c = m, k_p = 0; otherwise r = (lam[t] - lam[u]) / (lam[s] - lam[t]),
+        k_c = m (1 + 1/(2r)), k_p = -m / (2r); so that x0 = (x - k_e eps)/k_a and
+        x' = k_x x + k_c x0 + k_p hist.  Computed in float64 from the fp32 alpha_bars and rounded to fp32
+        once; cached per (steps, spacing, device).  The result is an engine.DpmSchedule (a tuple)."""
+        key = (int(steps), str(spacing), str(device))
+        cache = self.__dict__.setdefault("_dpm_tables", {})
+        if key not in cache:
+            tau = self.dpm_timesteps(steps, spacing)
+            S = len(tau)
+            ab = torch.cat([torch.ones(1, dtype=torch.float64), self._host[1].double()])  # ab[0] := 1
+            t = torch.tensor(tau, dtype=torch.long)
+            s = torch.tensor([0] + tau[:-1], dtype=torch.long)
+            ab_t, ab_s = ab[t], ab[s]
+            k_e, k_a = torch.sqrt(1 - ab_t), torch.sqrt(ab_t)
+            k_x = torch.sqrt(1 - ab_s) / k_e
+            m = torch.sqrt(ab_s) - k_x * k_a
+            k_c, k_p = m.clone(), torch.zeros_like(m)
+            if S > 2:  # second-order rows 1 < p < S (indices 1 .. S-2)
+                lam = 0.5 * torch.log(ab[1:] / (1 - ab[1:]))  # lam[t] at index t - 1
+                mid = slice(1, S - 1)
+                lt, ls, lu = lam[t[mid] - 1], lam[s[mid] - 1], lam[t[2:] - 1]
+                r = (lt - lu) / (ls - lt)
+                k_c[mid] = m[mid] * (1 + 1 / (2 * r))
+                k_p[mid] = -m[mid] / (2 * r)
+            tabs = (k_e, k_a, k_x, k_c, k_p)
+            cache[key] = _engine.DpmSchedule((t.contiguous().to(device),)
+                                             + tuple(v.float().contiguous().to(device) for v in tabs))
+        return cache[key]
+
+    @classmethod
+    def _sampler_mode(cls, sampler, steps, eta, spacing, T):
+        """Argument rules of the samplers' (sampler, steps, eta, spacing) keywords ->
+        None (DDPM), ("ddim", S, eta) or ("dpm", S, spacing)."""
+        if sampler != "dpmpp_2m":
+            if spacing is not None:
+                raise ValueError(f'`spacing` belongs to sampler="dpmpp_2m" (got sampler={sampler!r})')
+            return ("ddim", int(steps), float(eta)) if cls._check_sampler(sampler, steps, eta, T) else None
+        if steps is None or not 1 <= int(steps) <= int(T):
+            raise ValueError(f'sampler="dpmpp_2m" needs steps in [1, {T}] (got {steps})')
+        if float(eta) != 0.0:
+            raise ValueError(f'sampler="dpmpp_2m" is deterministic: eta must be 0 (got {eta})')
+        spacing = "logsnr" if spacing is None else spacing
+        if spacing not in cls.DPM_SPACINGS:
+            raise ValueError(f'spacing must be None, "logsnr" or "uniform" (got {spacing!r})')
+        return ("dpm", int(steps), spacing)
+
     @staticmethod
     def _check_sampler(sampler, steps, eta, T):
         """Argument rules of the samplers' (sampler, steps, eta) keywords -> True for the strided path."""
@@ -176,7 +258,7 @@ class Diffuser:
                                  'sampling is sampler="ddim", eta=1.0')
             return False
         if sampler != "ddim":
-            raise ValueError(f'sampler must be "ddpm" or "ddim" (got {sampler!r})')
+            raise ValueError(f'sampler must be "ddpm", "ddim" or "dpmpp_2m" (got {sampler!r})')
         if steps is None or not 1 <= int(steps) <= int(T):
             raise ValueError(f'sampler="ddim" needs steps in [1, {T}] (got {steps})')
         if not 0.0 <= float(eta) <= 1.0:
@@ -344,6 +426,44 @@ class Diffuser:
         noise = self._step_noise(x) if noisy else None
         return _engine.ddim_update(x, eu, ec, g, pos, sched, noise,
                                    seed=self._seed() if noisy and noise is None else 0)
+
+    def dpm_step(self, model, x, pos, hist, steps, spacing="logsnr", y=None, guidance_scale=0.0, null_label=0,
+                 cond_vals=None, cond_mask=None):
+        """One DPM-Solver++(2M) step at position(s) `pos` ((B,) in [1, steps]) of the `steps`-position
+        schedule of dpm_tables(steps, spacing): returns x' and leaves this step's x0 in `hist` (fp32,
+        x's shape, updated in place).  Below position `steps`, hist must hold the x0 that the step at
+        pos + 1 left; positions `steps` and 1 do not read it.  Draws nothing.  CFG as in ddim_step."""
+        S = len(self.dpm_timesteps(steps, spacing))
+        assert (pos >= 1).all() and (pos <= S).all()  # (reads pos back: a device sync, as denoise_cond)
+        return self._dpm_step(model, x, pos, self.dpm_tables(steps, spacing, x.device), hist, y, guidance_scale,
+                              null_label, cond_vals, cond_mask)
+
+    def _dpm_step(self, model, x, pos, sched, hist, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
+                  cond_mask=None):
+        """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update."""
+        cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
+        g = float(guidance_scale) if cfg else 0.0
+        pos = pos.to(device=x.device, dtype=torch.long)
+        with torch.no_grad():
+            if y is None:
+                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
+            if _native_kind(model) in (1, 2) and x.is_cuda:
+                x_in = x.float().contiguous()
+                out = torch.empty_like(x_in)
+                use = cond_vals is not None and cond_mask is not None
+                model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
+                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist)
+                return out
+
+            t = sched[0][pos - 1]
+
+            def eps_of(labels):
+                e = model(x, t, labels, cond_vals=cond_vals, cond_mask=cond_mask)
+                return e[0] if isinstance(e, (tuple, list)) else e
+
+            eu = eps_of(torch.full_like(y, null_label) if cfg else y)
+            ec = eps_of(y) if cfg else None
+        return _engine.dpm_update(x, eu, ec, g, pos, sched, hist)
 
     # ---- loops --------------------------------------------------------------------------------
     def sample(self, model, x_shape=(20, 3, 80, 80)):
@@ -556,14 +676,19 @@ class Diffuser:
         sampler: str = "ddpm",
         steps: Optional[int] = None,
         eta: float = 0.0,
+        spacing: Optional[str] = None,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
         sampler="ddim", steps=S (1 <= S <= num_timesteps), eta in [0, 1]: S strided DDIM steps over
         ddim_timesteps(S) instead of all T (eta = 0 deterministic, eta = 1 strided ancestral sampling).
         Draw order in host-noise mode with eta > 0 is the DDPM sampler's (optional encode draw, x_T, one
-        global draw per step); eta = 0 draws nothing after x_T."""
-        ddim = (int(steps), float(eta)) if self._check_sampler(sampler, steps, eta, self.num_timesteps) else None
+        global draw per step); eta = 0 draws nothing after x_T.
+
+        sampler="dpmpp_2m", steps=S, spacing=None / "logsnr" (the default) or "uniform": S steps of
+        DPM-Solver++(2M) over dpm_timesteps(S, spacing).  Deterministic (eta must be 0): only x_T is
+        drawn.  `spacing` belongs to this sampler alone."""
+        mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         device = self.device
         items = self._norm_counts(class_counts)
         y_list: List[int] = []
@@ -581,19 +706,24 @@ class Diffuser:
             C, Hlat, Wlat = z_shape
 
         x = self._randn((B, C, Hlat, Wlat), device)
-        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, ddim)
+        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode)
         if vae is None:
             return x
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         return self._decode(vae, x, to_pil)
 
-    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, ddim=None):
+    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None):
         """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
-        ddim = (S, eta): the strided loop instead — the counter walks the S positions of
-        ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and replay."""
-        T = self.num_timesteps if ddim is None else ddim[0]
-        sched = self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None
+        mode = ("ddim", S, eta) (_sampler_mode): the strided loop instead — the counter walks the S
+        positions of ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and
+        replay.  mode = ("dpm", S, spacing): likewise over dpm_tables(S, spacing); the solver's history
+        buffer lives here, and a replayed chunk restarts from the history it started with."""
+        ddim = mode[1:] if mode is not None and mode[0] == "ddim" else None
+        dpm = mode is not None and mode[0] == "dpm"
+        T = self.num_timesteps if mode is None else mode[1]
+        sched = (self.dpm_tables(mode[1], mode[2], x.device) if dpm
+                 else self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None)
         native = _native_kind(model) in (1, 2) and x.is_cuda and guidance_scale and guidance_scale > 0
         bar = tqdm(total=T, desc="Sampling (cond+numeric)") if progress else None
         if native and self.noise_source == "device":
@@ -603,7 +733,10 @@ class Diffuser:
             t_dev = torch.full((1,), T, device=x.device, dtype=torch.long)
             tables = self.coef_tables(x.device, clamp_prev=True) if sched is None else None
             skw = dict(sched=sched) if sched is not None else {}  # (the DDPM calls stay as they were)
-            seed = self._seed()
+            hist = None
+            if dpm:  # position S does not read it: no initial value needed
+                hist = skw["hist"] = torch.empty_like(x, dtype=torch.float32)
+            seed = 0 if dpm else self._seed()  # the DPM solver draws nothing
             v, m = vals.float().contiguous(), msk.float().contiguous()
             guard = self._guard_target(model)
             done = 0
@@ -611,10 +744,13 @@ class Diffuser:
                 while done < T:
                     k = min(self.GUARD_CHUNK, T - done)
                     x0 = x.clone() if guard is not None else None
+                    h0 = hist.clone() if guard is not None and dpm else None
                     nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k, seed=seed,
                                    use_graph=self.use_graph, **skw)
                     if guard is not None and guard.range_tripped():
                         x.copy_(x0)
+                        if dpm:
+                            hist.copy_(h0)
                         t_dev.fill_(T - done)
                         with guard.precision_override("fp32"):
                             nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k,
@@ -628,12 +764,23 @@ class Diffuser:
                 bar.close()
             return x
 
+        hist = torch.empty_like(x, dtype=torch.float32) if dpm else None
+        snap = [None]  # hist at the start of the running chunk (guarded models only)
+        guarded = dpm and x.is_cuda and self._guard_target(model) is not None
+
+        def restore_hist():
+            hist.copy_(snap[0])
+
         def run(i_from, i_to, x):
+            if guarded:
+                snap[0] = hist.clone()
             for i in range(i_from, i_to, -1):  # i in [1, T]: denoise_cond's assert holds by construction
                 t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
                 if sched is None:
                     x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk)
-                else:  # t holds the position
+                elif dpm:  # t holds the position
+                    x = self._dpm_step(model, x, t, sched, hist, y, guidance_scale, null_label, vals, msk)
+                else:
                     x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, guidance_scale, null_label, vals,
                                         msk)
                 if bar is not None:
@@ -641,7 +788,8 @@ class Diffuser:
             return x
 
         with torch.no_grad():
-            x = self._guarded_host_loop(model, x, run, total=T, draws=ddim is None or ddim[1] > 0)
+            x = self._guarded_host_loop(model, x, run, on_replay=restore_hist if guarded else None, total=T,
+                                        draws=mode is None or (ddim is not None and ddim[1] > 0))
         if bar is not None:
             bar.close()
         return x

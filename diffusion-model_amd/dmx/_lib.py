@@ -53,6 +53,13 @@ class DdimSched(ctypes.Structure):
                 ("k_s", ctypes.c_void_p), ("k_d", ctypes.c_void_p), ("k_n", ctypes.c_void_p), ("S", ctypes.c_int)]
 
 
+class DpmSched(ctypes.Structure):
+    """dmx_dpm_sched (include/dmx.h): per-position tables of a DPM-Solver++(2M) schedule and its history buffer."""
+    _fields_ = [("t_map", ctypes.c_void_p), ("k_e", ctypes.c_void_p), ("k_a", ctypes.c_void_p),
+                ("k_x", ctypes.c_void_p), ("k_c", ctypes.c_void_p), ("k_p", ctypes.c_void_p),
+                ("hist", ctypes.c_void_p), ("S", ctypes.c_int)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -106,6 +113,9 @@ SIGNATURES = [
     ("dmx_sample_loop_ddim", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), _I, _I, _P]),
     ("dmx_ddim_update", _I, [_P, _P, _P, _P, ctypes.c_float, _P, _I, ctypes.POINTER(DdimSched), _P, ctypes.c_uint64,
                              _I64, _I, _I, _I, _I, _P]),
+    ("dmx_step_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _P]),
+    ("dmx_sample_loop_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _I, _I, _P]),
+    ("dmx_dpm_update", _I, [_P, _P, _P, _P, ctypes.c_float, _P, _I, ctypes.POINTER(DpmSched), _I, _I, _I, _I, _P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),
     ("dmx_eval_metrics", _I, [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P]),

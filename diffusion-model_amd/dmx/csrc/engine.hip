@@ -249,6 +249,7 @@ struct Arena {
 struct GraphKey {
   dmx_step_args a;
   dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
+  dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
@@ -1951,11 +1952,24 @@ static void set_sched(StepTailParams& p, const dmx_ddim_sched& sc) {
   p.k_n = sc.k_n;
 }
 
+// The DPM-Solver++(2M) form: positions as above, its own three tables and the history buffer.
+static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
+  p.tmax = dp.S;
+  p.t_map = dp.t_map;
+  p.k_e = dp.k_e;
+  p.k_a = dp.k_a;
+  p.k_x = dp.k_x;
+  p.k_c = dp.k_c;
+  p.k_p = dp.k_p;
+  p.hist = dp.hist;
+}
+
 // t_next (multi-step sample-loop graphs): the step's t - 1 is stored there by the embedding kernel.
 // sc (strided sampling, include/dmx.h dmx_ddim_sched): a.t holds positions, the tail applies the
 // DDIM update from sc's tables and a.c1 / c2 / sd / T are not read.
+// dp (include/dmx.h dmx_dpm_sched; at most one of sc / dp): the same with the DPM-Solver++(2M) update.
 static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false,
-                      const dmx_ddim_sched* sc = nullptr) {
+                      const dmx_ddim_sched* sc = nullptr, const dmx_dpm_sched* dp = nullptr) {
   dmx_model* m = R.m;
   const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
   const int N = cfg ? 2 * a.n : a.n;
@@ -1965,6 +1979,9 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
   if (sc != nullptr) {
     in.t_map = sc->t_map;
     in.n_pos = sc->S;
+  } else if (dp != nullptr) {
+    in.t_map = dp->t_map;
+    in.n_pos = dp->S;
   }
   float* feat = unet_trunk(R, in, N, a.h, a.w);
   if (R.plan) return;
@@ -1986,8 +2003,10 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
   p.seed = a.seed;
   p.sample_offset = a.sample_offset;
   p.range_flag = m->range_flag;
-  const bool ddim = sc != nullptr;
-  if (ddim) {
+  const bool ddim = sc != nullptr, dpm = dp != nullptr;
+  if (dpm) {
+    set_sched(p, *dp);
+  } else if (ddim) {
     set_sched(p, *sc);
   } else {
     p.tmax = a.T;
@@ -1995,16 +2014,18 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
     p.c2 = a.c2;
     p.sd = a.sd;
   }
-  R.layer = ddim ? "out+cfg+ddim" : "out+cfg+ddpm";
+  R.layer = dpm ? "out+cfg+dpm" : ddim ? "out+cfg+ddim" : "out+cfg+ddpm";
   if (p.Co == 4 && p.feat != nullptr) {
     dim3 grid(cdiv(p.HW, 16), a.n);
     R.begin("step_tail4_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    if (ddim) step_tail4_kernel<true><<<grid, 256, 0, R.st>>>(p);
+    if (dpm) step_tail4_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
+    else if (ddim) step_tail4_kernel<true><<<grid, 256, 0, R.st>>>(p);
     else step_tail4_kernel<false><<<grid, 256, 0, R.st>>>(p);
   } else {
     dim3 grid(cdiv(p.HW, 256), a.n);
     R.begin("step_tail_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
+    if (dpm) step_tail_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
+    else if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
     else step_tail_kernel<false><<<grid, 256, 0, R.st>>>(p);
   }
   R.end();
@@ -2017,12 +2038,24 @@ static void validate_sched(const dmx_ddim_sched* sc) {
   REQUIRE(sc->t_map && sc->k_e && sc->k_a && sc->k_s && sc->k_d && sc->k_n, "null table in schedule");
 }
 
-// sc != null: the strided calls (a->c1 / c2 / sd / T are ignored there)
-static void validate_step(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc = nullptr) {
+static void validate_sched(const dmx_dpm_sched* dp) {
+  REQUIRE(dp != nullptr, "null schedule");
+  REQUIRE(dp->S >= 1, "schedule needs S >= 1 positions");
+  REQUIRE(dp->t_map && dp->k_e && dp->k_a && dp->k_x && dp->k_c && dp->k_p, "null table in schedule");
+  REQUIRE(dp->hist != nullptr, "DPM schedule needs a history buffer");
+}
+
+// sc / dp != null: the strided calls (a->c1 / c2 / sd / T are ignored there)
+static void validate_step(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc = nullptr,
+                          const dmx_dpm_sched* dp = nullptr) {
   REQUIRE(a != nullptr, "null step args");
   check_shapes(m, a->n, a->h, a->w);
   REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
-  if (sc != nullptr) {
+  if (dp != nullptr) {
+    validate_sched(dp);
+    REQUIRE(a->noise == nullptr, "the DPM solver takes no noise (noise must be NULL)");
+    REQUIRE(dp->hist != a->x_in && dp->hist != a->x_out, "hist must not alias x");
+  } else if (sc != nullptr) {
     validate_sched(sc);
   } else {
     REQUIRE(a->c1 && a->c2 && a->sd, "null tensor in step args");
@@ -2510,15 +2543,27 @@ int dmx_step_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc
   });
 }
 
+int dmx_step_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr, "null model");
+    validate_sched(sched);
+    validate_step(m, a, nullptr, sched);
+    ensure_planes(m, (hipStream_t)stream);
+    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, nullptr, sched); });
+  });
+}
+
 static constexpr int kGraphSteps = 8;
 
 // dmx_sample_loop (sc == null) and dmx_sample_loop_ddim: the scalar a->t counts down by one per
 // step either way — timesteps in the first, positions of the schedule in the second.
+// dmx_sample_loop_dpm (dp != null, sc == null): positions again; the history buffer is updated in
+// place by every step, so it needs no ping-pong inside the multi-step graph.
 static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc, int steps, int use_graph,
-                            void* stream) {
+                            void* stream, const dmx_dpm_sched* dp = nullptr) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
-    validate_step(m, a, sc);
+    validate_step(m, a, sc, dp);
     REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
     REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
     REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
@@ -2528,7 +2573,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
     int64_t* tdev = const_cast<int64_t*>(a->t);
     if (!use_graph) {
       for (int i = 0; i < steps; ++i) {
-        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc); });
+        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp); });
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
         HIPCHK(hipGetLastError());
       }
@@ -2550,6 +2595,20 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       key.sched.k_d = sc->k_d;
       key.sched.k_n = sc->k_n;
       key.sched.S = sc->S;
+    } else if (dp != nullptr) {
+      // likewise for the DPM graphs, which also read and write the history buffer; S >= 1 keeps
+      // their keys apart from the DDPM and DDIM keys (dpm all zero)
+      key.a.c1 = key.a.c2 = key.a.sd = nullptr;
+      key.a.T = 0;
+      key.a.seed = 0;  // (not read: the solver draws nothing)
+      key.dpm.t_map = dp->t_map;
+      key.dpm.k_e = dp->k_e;
+      key.dpm.k_a = dp->k_a;
+      key.dpm.k_x = dp->k_x;
+      key.dpm.k_c = dp->k_c;
+      key.dpm.k_p = dp->k_p;
+      key.dpm.hist = dp->hist;
+      key.dpm.S = dp->S;
     }
     key.table_gen = m->ctx->table_gen;
     if (!(m->has_graph && key == m->gkey)) {
@@ -2560,7 +2619,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       m->ws.plan = true;
       {
         Run P{m, st, true, m->ws};
-        step_body(P, *a, nullptr, false, sc);
+        step_body(P, *a, nullptr, false, sc, dp);
       }
       ensure_ws(m);
       poison(m->ws_mem, m->ws.off, st);
@@ -2570,7 +2629,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       try {
         Run R{m, st, false, m->ws};
-        step_body(R, *a, nullptr, false, sc);
+        step_body(R, *a, nullptr, false, sc, dp);
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
       } catch (...) {
         hipGraph_t g;
@@ -2596,7 +2655,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
           Run R{m, st, false, m->ws};
           dmx_step_args ak = *a;
           ak.t = (k & 1) ? tscr : tdev;
-          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc);  // cond MLP rows from step 0 of the graph
+          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp);  // cond MLP rows from step 0 of the graph
         }
       } catch (...) {
         hipGraph_t g;
@@ -2627,6 +2686,12 @@ int dmx_sample_loop_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sc
                          int use_graph, void* stream) {
   const int rc = guarded([&] { validate_sched(sched); });
   return rc != DMX_OK ? rc : sample_loop_impl(m, a, sched, steps, use_graph, stream);
+}
+
+int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, int steps,
+                        int use_graph, void* stream) {
+  const int rc = guarded([&] { validate_sched(sched); });
+  return rc != DMX_OK ? rc : sample_loop_impl(m, a, nullptr, steps, use_graph, stream, sched);
 }
 
 int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* recs, int cap, int* n_out,
@@ -2727,6 +2792,34 @@ int dmx_ddim_update(const float* x, float* x_out, const float* eu, const float* 
     p.sample_offset = sample_offset;
     dim3 grid(cdiv(p.HW, 256), n);
     step_tail_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* ec, float guidance,
+                   const int64_t* pos, int pos_stride, const dmx_dpm_sched* sched, int n, int c, int h, int w,
+                   void* stream) {
+  return guarded([&] {
+    REQUIRE(x && x_out && eu && pos, "null tensor");
+    validate_sched(sched);
+    REQUIRE(sched->hist != x && sched->hist != x_out, "hist must not alias x");
+    REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1, "bad shape");
+    StepTailParams p;
+    std::memset(&p, 0, sizeof(p));
+    p.Co = c;
+    p.B = n;
+    p.HW = h * w;
+    p.cfg = ec != nullptr ? 1 : 0;
+    p.guidance = guidance;
+    p.eps_u = eu;
+    p.eps_c = ec;
+    p.x = x;
+    p.x_out = x_out;
+    p.t = pos;
+    p.t_stride = pos_stride;
+    set_sched(p, *sched);
+    dim3 grid(cdiv(p.HW, 256), n);
+    step_tail_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
     HIPCHK(hipGetLastError());
   });
 }

@@ -763,6 +763,10 @@ struct StepTailParams {
   // the tables belongs to position p and t_map[p - 1] is its network timestep (the noise key)
   const int64_t* t_map;
   const float* k_e; const float* k_a; const float* k_s; const float* k_d; const float* k_n;
+  // DPM-Solver++(2M) form, the <false, true> instantiations: positions and t_map / k_e / k_a as in
+  // the DDIM form, k_x / k_c / k_p per position, hist (x's shape) read where k_p != 0 and written
+  const float* k_x; const float* k_c; const float* k_p;
+  float* hist;
 };
 
 // Range guard of the split-precision modes: an operand beyond the f16 range (|v| >= 65520)
@@ -792,8 +796,22 @@ DMX_DEV float ddim_elem(float x, float eps, float ke, float ka, float ks, float 
   const float x0 = rnd(x - rnd(ke * eps)) / ka;
   return rnd(rnd(ks * x0) + rnd(kd * eps)) + rnd(kn * nz);
 }
+// DPM-Solver++(2M) update (Lu et al. 2022, Alg. 2, data prediction) from position p (timestep t) to
+// p - 1 (timestep s), the previous step having come from u:
+//   x0 = (x - k_e*eps) / k_a;  x' = k_x*x + k_c*x0 + k_p*hist;  hist <- x0
+// with k_x = sigma_s/sigma_t, m = alpha_s - k_x*alpha_t, r = (lam_t - lam_u)/(lam_s - lam_t),
+// k_c = m (1 + 1/(2r)), k_p = -m/(2r) (first-order rows: k_c = m, k_p = 0) tabulated per position on
+// the host; one rounding per op.  hist is read only where k_p != 0: the first step of a schedule may
+// start from an uninitialised buffer.  Each element of hist is read and written by the same lane.
+DMX_DEV float dpm_elem(float x, float eps, float ke, float ka, float kx, float kc, float kp, float* hist) {
+  const float x0 = rnd(x - rnd(ke * eps)) / ka;
+  const float y = rnd(kx * x) + rnd(kc * x0);
+  const float out = kp != 0.f ? y + rnd(kp * *hist) : y;
+  *hist = x0;
+  return out;
+}
 
-template <bool DDIM>
+template <bool DDIM, bool DPM = false>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int n = blockIdx.y;
@@ -832,7 +850,7 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
   // where sigma is 0 (eta = 0, and position 1 always); DDPM: no noise at t = 1
   float kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
-  const bool noisy = DDIM ? kn != 0.f : t != 1;
+  const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // the DPM solver takes no noise
   float nz[4] = {0.f, 0.f, 0.f, 0.f};
   if (noisy) {
     if (p.noise != nullptr) {
@@ -844,7 +862,9 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
     }
   }
   float c1 = 0.f, c2 = 0.f, sd = 0.f, ke = 0.f, ka = 0.f, ks = 0.f, kd = 0.f;
-  if (DDIM) {
+  if (DPM) {  // (ks / kd / kn carry k_x / k_c / k_p)
+    ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_x[t - 1], kd = p.k_c[t - 1], kn = p.k_p[t - 1];
+  } else if (DDIM) {
     ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_s[t - 1], kd = p.k_d[t - 1];
   } else {
     c1 = p.c1[t - 1], c2 = p.c2[t - 1], sd = p.sd[t - 1];
@@ -853,8 +873,11 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
     const float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
     flag_nonfinite(p.range_flag, eps);
     const size_t idx = ((size_t)n * Co + c) * p.HW + pix;
-    p.x_out[idx] = DDIM ? ddim_elem(p.x[idx], eps, ke, ka, ks, kd, kn, nz[c])
-                        : ddpm_elem(p.x[idx], eps, c1, c2, sd, nz[c]);
+    if (DPM)
+      p.x_out[idx] = dpm_elem(p.x[idx], eps, ke, ka, ks, kd, kn, p.hist + idx);
+    else
+      p.x_out[idx] = DDIM ? ddim_elem(p.x[idx], eps, ke, ka, ks, kd, kn, nz[c])
+                          : ddpm_elem(p.x[idx], eps, c1, c2, sd, nz[c]);
   }
 }
 
@@ -875,7 +898,7 @@ DMX_DEV float group_sum16(float s) {  // sum over aligned 16-lane rows (DPP), sa
   return s;
 }
 
-template <bool DDIM>
+template <bool DDIM, bool DPM = false>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -904,7 +927,7 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
   const float v = sub == 0 ? ec[0] : sub == 1 ? ec[1] : sub == 2 ? ec[2] : ec[3];
   float nz = 0.f, kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
-  const bool noisy = DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
+  const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
   const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
   if (noisy) {
     if (p.noise != nullptr) {
@@ -917,7 +940,10 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
   }
   const float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
   flag_nonfinite(p.range_flag, eps);
-  if (DDIM)
+  if (DPM)
+    p.x_out[idx] = dpm_elem(p.x[idx], eps, p.k_e[t - 1], p.k_a[t - 1], p.k_x[t - 1], p.k_c[t - 1], p.k_p[t - 1],
+                            p.hist + idx);
+  else if (DDIM)
     p.x_out[idx] = ddim_elem(p.x[idx], eps, p.k_e[t - 1], p.k_a[t - 1], p.k_s[t - 1], p.k_d[t - 1], kn, nz);
   else
     p.x_out[idx] = ddpm_elem(p.x[idx], eps, p.c1[t - 1], p.c2[t - 1], p.sd[t - 1], nz);

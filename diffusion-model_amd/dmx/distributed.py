@@ -169,7 +169,8 @@ class ShardedCondSampler:
 
     def sample(self, class_counts, z_shape=None, guidance_scale: float = 3.0, null_label: int = 0, cond=None,
                cond_mask=None, decode: bool = True, dummy_input_hw=(224, 224), sampler: str = "ddpm",
-               steps: Optional[int] = None, eta: float = 0.0) -> Optional[torch.Tensor]:
+               steps: Optional[int] = None, eta: float = 0.0,
+               spacing: Optional[str] = None) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -189,10 +190,15 @@ class ShardedCondSampler:
 
         sampler / steps / eta as in Diffuser.sample_latent_cond: sampler="ddim" walks the `steps`
         positions of the strided schedule instead of the T timesteps (same chunks, guard and draw
-        order; with eta = 0 no rank draws per-step noise)."""
+        order; with eta = 0 no rank draws per-step noise).  sampler="dpmpp_2m" with `spacing` walks
+        the positions of the DPM-Solver++(2M) schedule: no rank draws anything after x_T (no seed
+        either), and the solver's history buffer is shard-local (no collective); a replayed chunk
+        restarts from the history it started with."""
         ws, rank = world()
         d = self.d
-        ddim = d._check_sampler(sampler, steps, eta, d.num_timesteps)
+        mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
+        ddim = mode is not None and mode[0] == "ddim"
+        dpm = mode is not None and mode[0] == "dpm"
         items = d._norm_counts(class_counts)
         y_list: List[int] = []
         for cls, num in items:
@@ -210,15 +216,19 @@ class ShardedCondSampler:
         C, H, W = z_shape
         nm = self.model.native() if e > s else None
         guard = d._guard_target(self.model) if nm is not None else None
-        tables = d.coef_tables(dev, clamp_prev=True) if not ddim else None
-        sched = d.ddim_tables(steps, eta, dev) if ddim else None
-        T = int(steps) if ddim else d.num_timesteps  # the loop counter: timesteps, or positions
-        draws = not ddim or float(eta) > 0  # DDIM with eta = 0 draws no per-step noise
-        skw = dict(sched=sched) if ddim else {}  # (the DDPM calls stay exactly as they were)
+        tables = d.coef_tables(dev, clamp_prev=True) if mode is None else None
+        sched = d.dpm_tables(mode[1], mode[2], dev) if dpm else d.ddim_tables(steps, eta, dev) if ddim else None
+        T = int(steps) if mode is not None else d.num_timesteps  # the loop counter: timesteps, or positions
+        draws = mode is None or (ddim and float(eta) > 0)  # DDIM with eta = 0 and DPM draw no per-step noise
+        skw = dict(sched=sched) if mode is not None else {}  # (the DDPM calls stay exactly as they were)
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
+        hist = None
+        if dpm:  # this shard's rows; position S does not read it, so it needs no initial value
+            hist = skw["hist"] = torch.empty_like(x)
         if d.noise_source == "device":
-            seed = torch.tensor([d._seed()], dtype=torch.long)  # drawn after x_T, as _run_cond_loop does
-            if ws > 1:
+            # drawn after x_T, as _run_cond_loop does (the DPM solver draws nothing: no seed)
+            seed = torch.tensor([0 if dpm else d._seed()], dtype=torch.long)
+            if ws > 1 and not dpm:
                 if dist.get_backend() != "gloo":
                     seed = seed.to(dev)
                 dist.broadcast(seed, src=0)
@@ -258,11 +268,14 @@ class ShardedCondSampler:
             while i >= 1:
                 j = max(i - d.GUARD_CHUNK, 0)
                 x0, rng = x.clone(), torch.get_rng_state()
+                h0 = hist.clone() if dpm else None
                 x = run(i, j, x)
                 tripped = guard.range_tripped() if guard is not None else False
                 if any_rank(tripped, dev):
                     torch.set_rng_state(rng)
                     x = x0
+                    if dpm:
+                        hist.copy_(h0)
                     if guard is not None:
                         with guard.precision_override("fp32"):
                             x = run(i, j, x)

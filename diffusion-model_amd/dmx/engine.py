@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimSched, StepArgs, check
+from ._lib import DdimSched, DpmSched, StepArgs, check
 
 TIME_DIM = 256
 
@@ -272,11 +272,17 @@ class NativeModel:
         a.n, a.h, a.w = n, h, w
         return a
 
-    def _sched(self, sched, device) -> DdimSched:
-        """dmx_ddim_sched of a (t_map, k_e, k_a, k_s, k_d, k_n) tuple (Diffuser.ddim_tables) on `device`;
+    def _sched(self, sched, device, hist=None, x=None):
+        """dmx_ddim_sched of a (t_map, k_e, k_a, k_s, k_d, k_n) tuple (Diffuser.ddim_tables) on `device`,
+        or dmx_dpm_sched of a DpmSchedule (Diffuser.dpm_tables) with its history buffer `hist` (x's shape);
         makes sure the time table reaches the schedule's last timestep.  That timestep is read back
         once per schedule: the tuple is kept (alive, so its identity stays valid) with the value."""
-        sc = _sched_struct(sched, device)
+        if isinstance(sched, DpmSchedule):
+            sc = _dpm_struct(sched, device, hist, x)
+        else:
+            if hist is not None:
+                raise ValueError("hist belongs to a DPM schedule (Diffuser.dpm_tables)")
+            sc = _sched_struct(sched, device)
         last = getattr(self, "_sched_last", None)
         if last is None or last[0] is not sched[0]:
             last = self._sched_last = (sched[0], int(sched[0][-1].item()))
@@ -284,15 +290,18 @@ class NativeModel:
         return sc
 
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None):
+             sample_offset=0, t_stride=1, sched=None, hist=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
-        positions in [1, S] and `tables` is not read (may be None)."""
+        positions in [1, S] and `tables` is not read (may be None).
+        sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place): one
+        DPM-Solver++(2M) step; `noise` must be None and `seed` is not read."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        dpm = isinstance(sched, DpmSchedule)
         if sched is not None:
-            sc = self._sched(sched, x_in.device)
+            sc = self._sched(sched, x_in.device, hist, x_in)
             tables = None
         else:
             self.ctx.ensure_time_table(int(tables[0].numel()))
@@ -301,7 +310,9 @@ class NativeModel:
                        sample_offset)
         with torch.cuda.device(x_in.device):
             st = ctypes.c_void_p(_stream(x_in.device))
-            if sched is not None:
+            if dpm:
+                check(self.lib.dmx_step_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
+            elif sched is not None:
                 check(self.lib.dmx_step_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
             else:
                 check(self.lib.dmx_step(self.handle, ctypes.byref(a), st))
@@ -326,16 +337,19 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None):
+                    use_graph=True, sched=None, hist=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
 
         sched (the 6-tuple of Diffuser.ddim_tables): strided DDIM steps; t_dev then holds the
-        position in [1, S] and `tables` is not read (may be None)."""
+        position in [1, S] and `tables` is not read (may be None).
+        sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place):
+        DPM-Solver++(2M) steps, which draw nothing (`seed` is not read)."""
         _check_state(x, "x")
+        dpm = isinstance(sched, DpmSchedule)
         if sched is not None:
-            sc = self._sched(sched, x.device)
+            sc = self._sched(sched, x.device, hist, x)
             tables = None
         else:
             self.ctx.ensure_time_table(int(tables[0].numel()))
@@ -347,11 +361,14 @@ class NativeModel:
         cur = torch.cuda.current_stream(x.device)
         side = self.side_stream()
         side.wait_stream(cur)
-        for keep in (x, t_dev, y, vals, mask) + tuple(sched if sched is not None else tables):
+        for keep in (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables):
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if sched is not None:
+            if dpm:
+                check(self.lib.dmx_sample_loop_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
+                                                   int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            elif sched is not None:
                 check(self.lib.dmx_sample_loop_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
                                                     int(use_graph), ctypes.c_void_p(side.cuda_stream)))
             else:
@@ -505,4 +522,63 @@ def ddim_update(x, eu, ec, guidance, pos, sched, noise=None, seed=0, sample_offs
         check(lib.dmx_ddim_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
                                   ctypes.byref(sc), _ptr(nz_c), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                   int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+    return out
+
+
+class DpmSchedule(tuple):
+    """The (t_map, k_e, k_a, k_x, k_c, k_p) tables of a DPM-Solver++(2M) schedule (Diffuser.dpm_tables).
+    The type is what tells it from a DDIM schedule, which stays a plain 6-tuple."""
+    __slots__ = ()
+
+
+def _dpm_struct(sched, device, hist, x) -> DpmSched:
+    """The C view of a DpmSchedule and its history buffer: tables as in _sched_struct, hist a
+    contiguous fp32 tensor of x's shape on `device` that does not share x's storage."""
+    if not isinstance(sched, DpmSchedule) or len(sched) != 6:
+        raise ValueError("sched must be the DpmSchedule (t_map, k_e, k_a, k_x, k_c, k_p) of Diffuser.dpm_tables")
+    S = int(sched[0].numel())
+    for i, v in enumerate(sched):
+        want = torch.long if i == 0 else torch.float32
+        if v.dtype != want or v.dim() != 1 or v.numel() != S or not v.is_contiguous() or v.device != device:
+            raise ValueError(f"sched[{i}] must be a contiguous 1-D {want} tensor of {S} entries on {device}")
+    if S < 1:
+        raise ValueError("sched is empty")
+    if hist is None:
+        raise ValueError("a DPM schedule needs hist (the history buffer, x's shape)")
+    if (hist.dtype != torch.float32 or not hist.is_contiguous() or hist.device != device
+            or tuple(hist.shape) != tuple(x.shape)):
+        raise ValueError(f"hist must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {device}")
+    if hist.data_ptr() == x.data_ptr():
+        raise ValueError("hist must not alias x")
+    return DpmSched(*[v.data_ptr() for v in sched], hist.data_ptr(), S)
+
+
+def dpm_update(x, eu, ec, guidance, pos, sched, hist, out=None):
+    """Standalone DPM-Solver++(2M) update (include/dmx.h dmx_dpm_update) for duck-typed models: returns
+    x' and updates hist in place.  pos: (n,) positions in [1, S]; sched: the DpmSchedule of
+    Diffuser.dpm_tables on x's device; hist: fp32, x's shape, read where k_p != 0 and always written.
+    out: where x' goes (fp32, contiguous, x's shape; may be x itself), a new tensor by default.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(x, "x")
+    dev = x.device
+    x_c = x.to(dtype=torch.float32).contiguous()
+    sc = _dpm_struct(sched, dev, hist, x_c)
+    n, c, h, w = x_c.shape
+    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
+    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
+    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
+    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond")):
+        if e is not None and tuple(e.shape) != tuple(x_c.shape):
+            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
+    if p_c.numel() != n:
+        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
+    if out is None:
+        out = torch.empty_like(x_c)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev
+          or tuple(out.shape) != tuple(x_c.shape) or out.data_ptr() == hist.data_ptr()):
+        raise ValueError(f"out must be a contiguous fp32 tensor of shape {tuple(x_c.shape)} on {dev}, not hist")
+    with torch.cuda.device(dev):
+        check(lib.dmx_dpm_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
+                                 ctypes.byref(sc), n, c, h, w, ctypes.c_void_p(_stream(dev))))
     return out

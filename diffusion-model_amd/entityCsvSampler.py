@@ -52,12 +52,14 @@ class EntityCsvSampler:
                 torch.from_numpy(mask[start:end]).float().to(self.device))
 
     def sample(self, csv_path: str, count: Optional[int] = None, start: int = 0, guidance_scale: float = 3.0,
-               sampler: str = "ddpm", steps: Optional[int] = None, eta: float = 0.0):
-        """entityCsvSampler.py:50-80; sampler / steps / eta as in Diffuser.sample_latent_cond."""
+               sampler: str = "ddpm", steps: Optional[int] = None, eta: float = 0.0,
+               spacing: Optional[str] = None):
+        """entityCsvSampler.py:50-80; sampler / steps / eta / spacing as in Diffuser.sample_latent_cond."""
         vals, mask = self._rows(csv_path, count, start)
         return self.diffuser.sample_latent_cond(model=self.model, class_counts=(self.class_id, vals.shape[0]),
                                                 vae=self.vae, guidance_scale=guidance_scale, cond=vals,
-                                                cond_mask=mask, sampler=sampler, steps=steps, eta=eta)
+                                                cond_mask=mask, sampler=sampler, steps=steps, eta=eta,
+                                                spacing=spacing)
 
     def load_cond(self, csv_path: str, count: Optional[int] = None, start: int = 0):
         """entityCsvSampler.py:82-98."""

@@ -181,6 +181,42 @@ int dmx_ddim_update(const float* x, float* x_out, const float* eu, const float* 
                     const int64_t* pos, int pos_stride, const dmx_ddim_sched* sched, const float* noise,
                     uint64_t seed, int64_t sample_offset, int n, int c, int h, int w, void* stream);
 
+/* ---- DPM-Solver++(2M) over a schedule of S positions (Lu et al. 2022, Alg. 2: second-order
+ * multistep, data prediction; no reference counterpart).  Positions, t_map, k_e and k_a are as in
+ * dmx_ddim_sched.  With t = t_map[p-1], s = t_map[p-2] (0 below position 1), u = t_map[p] and
+ * lam = log(alpha/sigma), row p-1 of the other fp32 tables holds
+ *   k_x = sigma_s/sigma_t,  m = alpha_s - k_x*alpha_t,  r = (lam_t - lam_u)/(lam_s - lam_t),
+ *   k_c = m*(1 + 1/(2r)), k_p = -m/(2r)   (first-order rows p = S and p = 1: k_c = m, k_p = 0)
+ * and the update is  eps = eu + g*(ec-eu);  x0 = (x - k_e*eps)/k_a;  y = k_x*x + k_c*x0;
+ * x' = k_p != 0 ? y + k_p*hist : y;  hist <- x0, one IEEE rounding per operation in that order.
+ * hist has x's shape (n,C,h,w), must not alias x, is read only where k_p != 0 and is always
+ * written: position S may start from an uninitialised buffer, and a caller entering below
+ * position S must supply the x0 of position p + 1.  No noise is read or drawn at any position.
+ * All members are device pointers / counts owned by the caller. */
+typedef struct dmx_dpm_sched {
+  const int64_t* t_map; /* [S] int64 */
+  const float* k_e;     /* [S] each */
+  const float* k_a;
+  const float* k_x;
+  const float* k_c;
+  const float* k_p;
+  float* hist; /* (n,C,h,w), read + written */
+  int S;
+} dmx_dpm_sched;
+
+/* dmx_step / dmx_sample_loop with the DPM-Solver++(2M) update: a->t holds POSITIONS in [1, S],
+ * a->noise must be NULL and a->c1, c2, sd, T and seed are not read.  A captured graph belongs to
+ * one schedule (table pointers, hist and S): another schedule or history buffer, a DDIM loop or
+ * the DDPM loop on the same model captures anew. */
+int dmx_step_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, void* stream);
+int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, int steps,
+                        int use_graph, void* stream);
+/* Standalone update for duck-typed foreign models (ec NULL => eps = eu); pos: device int64
+ * positions, pos_stride 0 => one value for every sample.  x_out may alias x. */
+int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* ec, float guidance,
+                   const int64_t* pos, int pos_stride, const dmx_dpm_sched* sched, int n, int c, int h, int w,
+                   void* stream);
+
 /* ---- VAE decode (replaces VAE.decode, vae.py:64-69, plus Diffuser.reverse_to_img's
  * x*255 -> clamp -> uint8, diff.py:58-62) ---------------------------------------------
  * z: (n,4,h,w); img: (n,3,8h,8w) fp32 or NULL; u8: (n,8h,8w,3) uint8 (HWC) or NULL. */

@@ -1,16 +1,19 @@
-"""Strided (DDIM) sampling against the full DDPM walk on one MI355X: prints one JSON line.
+"""Few-step sampling (strided DDIM, DPM-Solver++(2M)) against the full DDPM walk on one MI355X: prints
+one JSON line.
 
   python tools/sampler_bench.py [--rounds 5]
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
 1. ms per step of the graph loops.  The strided loop (S = 50 of T = 1000, eta = 1 so that it draws
-   noise as the DDPM step does) and the DDPM loop alternate in one process, the DDPM leg twice per round
-   (legs ddpm_a, ddim, ddpm_b), so the spread between two measurements of the SAME loop is known.  A model
+   noise as the DDPM step does), the DPM-Solver++(2M) loop (S = 50, log-SNR spacing; it draws nothing and
+   reads and writes its history buffer) and the DDPM loop alternate in one process, the DDPM leg twice per
+   round (legs ddpm_a, ddim, dpmpp_2m, ddpm_b), so the spread between two measurements of the SAME loop is
+   known and the few-step legs are judged against it, not against a preset figure.  A model
    holds the graphs of one loop at a time: every leg first runs 8 steps untimed (capture), then 48 steps
    (six launches of the 8-step graph) between two device events.  Reported: the median over the rounds.
 2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
-   (ddpm, T = 1000) and (ddim, S = 50, eta = 0): the first call (it captures the graphs) and the best of
+   (ddpm, T = 1000), (ddim, S = 50, eta = 0) and (dpmpp_2m, S = 20, log-SNR spacing): the first call (it captures the graphs) and the best of
    the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
    from the steady ones by the sampler's own start-up only.
 
@@ -53,11 +56,13 @@ def loop_legs(nm, d, dev, rounds):
     t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
     tables = d.coef_tables(dev, True)
     sched = d.ddim_tables(S, 1.0, dev)
+    dpm_sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
 
-    def leg(ddim):
-        start = S if ddim else T
-        kw = dict(seed=1234, sched=sched) if ddim else dict(seed=1234)
-        tab = None if ddim else tables
+    def leg(kind):
+        start = T if kind == "ddpm" else S  # (the few-step legs start at position S: no history needed)
+        kw = {"ddpm": dict(seed=1234), "ddim": dict(seed=1234, sched=sched),
+              "dpm": dict(sched=dpm_sched, hist=hist)}[kind]
+        tab = tables if kind == "ddpm" else None
         x.copy_(x0)
         t_dev.fill_(start)
         nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tab, WARM, **kw)  # captures this loop's graphs
@@ -72,17 +77,21 @@ def loop_legs(nm, d, dev, rounds):
         assert int(t_dev.item()) == start - TIMED and bool(torch.isfinite(x).all())
         return e0.elapsed_time(e1) / TIMED
 
-    ms = {"ddpm_a": [], "ddim": [], "ddpm_b": []}
-    leg(False)  # workspace, split planes, time table
+    ms = {"ddpm_a": [], "ddim": [], "dpmpp_2m": [], "ddpm_b": []}
+    leg("ddpm")  # workspace, split planes, time table
     for _ in range(rounds):
-        ms["ddpm_a"].append(leg(False))
-        ms["ddim"].append(leg(True))
-        ms["ddpm_b"].append(leg(False))
+        ms["ddpm_a"].append(leg("ddpm"))
+        ms["ddim"].append(leg("ddim"))
+        ms["dpmpp_2m"].append(leg("dpm"))
+        ms["ddpm_b"].append(leg("ddpm"))
     med = {k: statistics.median(v) for k, v in ms.items()}
+    ddpm_mean = 0.5 * (med["ddpm_a"] + med["ddpm_b"])
     return {"ms_per_step_ddpm_a": round(med["ddpm_a"], 4), "ms_per_step_ddpm_b": round(med["ddpm_b"], 4),
-            "ms_per_step_ddim": round(med["ddim"], 4),
+            "ms_per_step_ddim": round(med["ddim"], 4), "ms_per_step_dpmpp_2m": round(med["dpmpp_2m"], 4),
             "ddpm_spread_ms": round(abs(med["ddpm_a"] - med["ddpm_b"]), 4),
-            "ddim_minus_ddpm_mean_ms": round(med["ddim"] - 0.5 * (med["ddpm_a"] + med["ddpm_b"]), 4),
+            "ddim_minus_ddpm_mean_ms": round(med["ddim"] - ddpm_mean, 4),
+            "dpmpp_2m_minus_ddpm_mean_ms": round(med["dpmpp_2m"] - ddpm_mean, 4),
+            "dpmpp_2m_minus_ddim_ms": round(med["dpmpp_2m"] - med["ddim"], 4),
             "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
 
 
@@ -103,7 +112,8 @@ def end_to_end(model, dev):
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
-    for name, extra, calls in (("ddim_S50_eta0", dict(sampler="ddim", steps=S, eta=0.0), 4), ("ddpm_T1000", {}, 2)):
+    for name, extra, calls in (("ddim_S50_eta0", dict(sampler="ddim", steps=S, eta=0.0), 4),
+                               ("dpmpp_2m_S20", dict(sampler="dpmpp_2m", steps=20), 4), ("ddpm_T1000", {}, 2)):
         secs = []
         for _ in range(calls):
             torch.cuda.synchronize()
