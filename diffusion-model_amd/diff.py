@@ -22,9 +22,14 @@ What changes is where the work happens:
   loop (``ddim_timesteps`` / ``ddim_tables`` / ``ddim_step``); the defaults leave the
   DDPM path untouched.  ``sampler="dpmpp_2m"`` runs DPM-Solver++(2M) over timesteps uniform in
   log-SNR through the same step and loop (``dpm_timesteps`` / ``dpm_tables`` / ``dpm_step``).
+* Image-conditioned sampling (not in the reference): ``sample_latent_cond(..., init_latent=z0,
+  mask=m, strength=s)`` starts any of the three samplers from z0 noised to an intermediate
+  position (img2img) and / or holds the latent outside ``m`` on z0's forward trajectory after
+  every step (inpainting; ``known_tables``, libdmx ``dmx_known_blend``).
 """
 from __future__ import annotations
 
+import math
 import os
 import queue
 import sys
@@ -198,7 +203,7 @@ class Diffuser:
             tau[i] = min(tau[i], tau[i + 1] - 1)
         return tau
 
-    def dpm_tables(self, steps: int, spacing: str = "logsnr", device="cpu"):
+    def dpm_tables(self, steps: int, spacing: str = "logsnr", device="cpu", start: Optional[int] = None):
         """(t_map, k_e, k_a, k_x, k_c, k_p) of the DPM-Solver++(2M) step from t = tau_p to s = tau_{p-1}
         (tau_0 = 0, alpha_bar 1), u = tau_{p+1} being the step before, per position p at index p-1:
         k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_x = sqrt(1-ab[s]) / sqrt(1-ab[t]),
@@ -206,8 +211,17 @@ class Diffuser:
         (p = S and p = 1): k_c = m, k_p = 0; otherwise r = (lam[t] - lam[u]) / (lam[s] - lam[t]),
         k_c = m (1 + 1/(2r)), k_p = -m / (2r); so that x0 = (x - k_e eps)/k_a and
         x' = k_x x + k_c x0 + k_p hist.  Computed in float64 from the fp32 alpha_bars and rounded to fp32
-        once; cached per (steps, spacing, device).  The result is an engine.DpmSchedule (a tuple)."""
-        key = (int(steps), str(spacing), str(device))
+        once; cached per (steps, spacing, device, start).  The result is an engine.DpmSchedule (a tuple).
+        start = p0 in [1, S): the schedule of a loop that enters at position p0 (img2img) — row p0 is
+        first-order too, so no step reads a history that was never written; the other rows are those
+        of start=None.  start = S is start=None."""
+        if start is not None:
+            start = int(start)
+            if not 1 <= start <= int(steps):
+                raise ValueError(f"start must be in [1, {int(steps)}] (got {start})")
+            if start == int(steps):
+                start = None
+        key = (int(steps), str(spacing), str(device)) + ((start,) if start is not None else ())
         cache = self.__dict__.setdefault("_dpm_tables", {})
         if key not in cache:
             tau = self.dpm_timesteps(steps, spacing)
@@ -227,10 +241,77 @@ class Diffuser:
                 r = (lt - lu) / (ls - lt)
                 k_c[mid] = m[mid] * (1 + 1 / (2 * r))
                 k_p[mid] = -m[mid] / (2 * r)
+            if start is not None:  # the loop enters here: nothing has written the history yet
+                k_c[start - 1], k_p[start - 1] = m[start - 1], 0.0
             tabs = (k_e, k_a, k_x, k_c, k_p)
             cache[key] = _engine.DpmSchedule((t.contiguous().to(device),)
                                              + tuple(v.float().contiguous().to(device) for v in tabs))
         return cache[key]
+
+    # ---- known-region sampling (img2img start, masked inpainting): one row per position, as above --
+    def known_tables(self, tau, device="cpu"):
+        """(q_a, q_e) of the known-region blend for the ascending timesteps `tau` of a loop (tau_p at
+        index p-1; the DDPM loop: 1..T): row p-1 holds q_a = sqrt(ab[s]), q_e = sqrt(1 - ab[s]) for
+        s = tau_{p-1}, the timestep the step at position p arrives at (tau_0 = 0, ab[0] = 1: row 0 is
+        exactly (1, 0)).  Computed in float64 from the fp32 alpha_bars and rounded to fp32 once; cached
+        per (tau, device)."""
+        tau = tuple(int(v) for v in tau)
+        T = int(self.num_timesteps)
+        if not tau or tau[0] < 1 or tau[-1] > T or any(b <= a for a, b in zip(tau, tau[1:])):
+            raise ValueError(f"tau must be strictly ascending timesteps in [1, {T}]")
+        key = (tau, str(device))
+        cache = self.__dict__.setdefault("_known_tables", {})
+        if key not in cache:
+            ab = torch.cat([torch.ones(1, dtype=torch.float64), self._host[1].double()])  # ab[0] := 1
+            ab_s = ab[torch.tensor((0,) + tau[:-1], dtype=torch.long)]
+            cache[key] = tuple(v.float().contiguous().to(device) for v in (torch.sqrt(ab_s), torch.sqrt(1 - ab_s)))
+        return cache[key]
+
+    def _mode_timesteps(self, mode) -> List[int]:
+        """tau of a _sampler_mode result: the timesteps its loop's positions 1..S stand for."""
+        if mode is None:
+            return list(range(1, int(self.num_timesteps) + 1))
+        return self.ddim_timesteps(mode[1]) if mode[0] == "ddim" else self.dpm_timesteps(mode[1], mode[2])
+
+    @staticmethod
+    def _known_start(strength, S: int) -> int:
+        """The position p0 a known-region loop of S positions enters at: S for strength None, otherwise
+        min(S, max(1, floor(strength S + 0.5))) for strength in (0, 1]."""
+        if strength is None:
+            return int(S)
+        s = float(strength)
+        if not 0.0 < s <= 1.0:
+            raise ValueError(f"strength must be in (0, 1] (got {strength})")
+        return min(int(S), max(1, int(math.floor(s * int(S) + 0.5))))
+
+    @staticmethod
+    def _known_inputs(init_latent, mask, strength, B: int, z_shape):
+        """Argument rules of the samplers' (init_latent, mask, strength) keywords -> None without them,
+        else (z0, mask or None, strength, (C, h, w)): z0 (B,C,h,w) and mask (B,1,h,w) fp32 contiguous,
+        broadcast to the batch.  Every violation raises ValueError."""
+        if init_latent is None:
+            if mask is not None or strength is not None:
+                raise ValueError("`mask` and `strength` need `init_latent`")
+            return None
+        Diffuser._known_start(strength, 1)
+        if not isinstance(init_latent, torch.Tensor) or init_latent.dim() not in (3, 4):
+            raise ValueError("init_latent must be a (B,C,h,w), (1,C,h,w) or (C,h,w) tensor")
+        z0 = init_latent if init_latent.dim() == 4 else init_latent.unsqueeze(0)
+        if z0.shape[0] not in (1, B) or min(z0.shape) < 1:
+            raise ValueError(f"init_latent has {z0.shape[0]} samples for a batch of {B}")
+        shape = tuple(int(v) for v in z0.shape[1:])
+        if z_shape is not None and tuple(int(v) for v in z_shape) != shape:
+            raise ValueError(f"init_latent shape {shape} != z_shape {tuple(z_shape)}")
+        z0 = z0.detach().to(torch.float32).expand(B, *shape).contiguous()
+        if mask is not None:
+            h, w = shape[1:]
+            if not isinstance(mask, torch.Tensor) or tuple(mask.shape) not in ((B, 1, h, w), (1, 1, h, w), (h, w)):
+                raise ValueError(f"mask must be a {(B, 1, h, w)}, {(1, 1, h, w)} or {(h, w)} tensor")
+            mask = mask.detach().to(torch.float32).reshape(-1, 1, h, w)
+            if not bool(((mask >= 0) & (mask <= 1)).all()):
+                raise ValueError("mask values must lie in [0, 1]")
+            mask = mask.expand(B, 1, h, w).contiguous()
+        return z0, mask, strength, shape
 
     @classmethod
     def _sampler_mode(cls, sampler, steps, eta, spacing, T):
@@ -352,9 +433,12 @@ class Diffuser:
         assert (t >= 1).all() and (t <= T).all()  # (reads t back: a device sync, as in the reference)
         return self._denoise_cond(model, x, t, y, guidance_scale, null_label, cond_vals, cond_mask)
 
-    def _denoise_cond(self, model, x, t, y=None, guidance_scale=0.0, null_label=0, cond_vals=None, cond_mask=None):
+    def _denoise_cond(self, model, x, t, y=None, guidance_scale=0.0, null_label=0, cond_vals=None, cond_mask=None,
+                      known=None):
         """denoise_cond after the range check — the samplers' own loops build t from a host-known
-        step in [1, T] and call this directly, so the host never waits on the device per step."""
+        step in [1, T] and call this directly, so the host never waits on the device per step.
+        known (engine.known_blend's 5-tuple, tables over tau = 1..T): the known-region blend follows
+        the step — inside the native step, or as a launch of its own after a foreign model's update."""
         tables = self.coef_tables(x.device, clamp_prev=True)
         with torch.no_grad():
             if guidance_scale and y is not None and guidance_scale > 0:
@@ -366,14 +450,14 @@ class Diffuser:
                     model.native().step(x.contiguous(), out, t.to(x.device), y.to(x.device), null_label,
                                         cond_vals if use else None, cond_mask if use else None,
                                         float(guidance_scale), tables, noise,
-                                        seed=self._seed() if noise is None else 0)
+                                        seed=self._seed() if noise is None else 0, known=known)
                     return out
                 y_null = torch.full_like(y, null_label)
                 eps_uncond, _ = model(x, t, y_null, cond_vals=cond_vals, cond_mask=cond_mask)
                 eps_cond, _ = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
                 noise = self._step_noise(x)
-                return _engine.ddpm_update(x, eps_uncond, eps_cond, float(guidance_scale), t, tables, noise,
-                                           seed=self._seed() if noise is None else 0)
+                return self._blend(_engine.ddpm_update(x, eps_uncond, eps_cond, float(guidance_scale), t, tables,
+                                                       noise, seed=self._seed() if noise is None else 0), t, known)
             else:
                 # plain conditional/unconditional — mirrors diff.py:152-156 literally, including
                 # its UnboundLocalError when y is given without guidance
@@ -383,7 +467,13 @@ class Diffuser:
         noise = self._step_noise(x)
         if not isinstance(eps, torch.Tensor):
             raise TypeError(f"unsupported operand type(s) for *: 'Tensor' and '{type(eps).__name__}'")
-        return _engine.ddpm_update(x, eps, None, 0.0, t, tables, noise, seed=self._seed() if noise is None else 0)
+        return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
+                                               seed=self._seed() if noise is None else 0), t, known)
+
+    @staticmethod
+    def _blend(x, pos, known):
+        """The known-region blend after a foreign model's update, in place on the update's output."""
+        return x if known is None else _engine.known_blend(x, pos, known, out=x)
 
     def ddim_step(self, model, x, pos, steps, eta=0.0, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
                   cond_mask=None):
@@ -396,7 +486,7 @@ class Diffuser:
                                guidance_scale, null_label, cond_vals, cond_mask)
 
     def _ddim_step(self, model, x, pos, sched, noisy, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                   cond_mask=None):
+                   cond_mask=None, known=None):
         """ddim_step after its checks; `noisy`: the schedule has noise (eta > 0).  Host-noise mode then
         draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws."""
         cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
@@ -412,7 +502,7 @@ class Diffuser:
                 use = cond_vals is not None and cond_mask is not None
                 model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
                                     cond_mask if use else None, g, None, noise,
-                                    seed=self._seed() if noisy and noise is None else 0, sched=sched)
+                                    seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known)
                 return out
 
             t = sched[0][pos - 1]
@@ -424,8 +514,8 @@ class Diffuser:
             eu = eps_of(torch.full_like(y, null_label) if cfg else y)
             ec = eps_of(y) if cfg else None
         noise = self._step_noise(x) if noisy else None
-        return _engine.ddim_update(x, eu, ec, g, pos, sched, noise,
-                                   seed=self._seed() if noisy and noise is None else 0)
+        return self._blend(_engine.ddim_update(x, eu, ec, g, pos, sched, noise,
+                                               seed=self._seed() if noisy and noise is None else 0), pos, known)
 
     def dpm_step(self, model, x, pos, hist, steps, spacing="logsnr", y=None, guidance_scale=0.0, null_label=0,
                  cond_vals=None, cond_mask=None):
@@ -439,7 +529,7 @@ class Diffuser:
                               null_label, cond_vals, cond_mask)
 
     def _dpm_step(self, model, x, pos, sched, hist, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                  cond_mask=None):
+                  cond_mask=None, known=None):
         """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update."""
         cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
         g = float(guidance_scale) if cfg else 0.0
@@ -452,7 +542,7 @@ class Diffuser:
                 out = torch.empty_like(x_in)
                 use = cond_vals is not None and cond_mask is not None
                 model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
-                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist)
+                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist, known=known)
                 return out
 
             t = sched[0][pos - 1]
@@ -463,7 +553,7 @@ class Diffuser:
 
             eu = eps_of(torch.full_like(y, null_label) if cfg else y)
             ec = eps_of(y) if cfg else None
-        return _engine.dpm_update(x, eu, ec, g, pos, sched, hist)
+        return self._blend(_engine.dpm_update(x, eu, ec, g, pos, sched, hist), pos, known)
 
     # ---- loops --------------------------------------------------------------------------------
     def sample(self, model, x_shape=(20, 3, 80, 80)):
@@ -677,6 +767,9 @@ class Diffuser:
         steps: Optional[int] = None,
         eta: float = 0.0,
         spacing: Optional[str] = None,
+        init_latent: Optional[torch.Tensor] = None,
+        mask: Optional[torch.Tensor] = None,
+        strength: Optional[float] = None,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -687,7 +780,18 @@ class Diffuser:
 
         sampler="dpmpp_2m", steps=S, spacing=None / "logsnr" (the default) or "uniform": S steps of
         DPM-Solver++(2M) over dpm_timesteps(S, spacing).  Deterministic (eta must be 0): only x_T is
-        drawn.  `spacing` belongs to this sampler alone."""
+        drawn.  `spacing` belongs to this sampler alone.
+
+        init_latent = z0 ((B,C,h,w), (1,C,h,w) or (C,h,w), broadcast to the batch; e.g. vae.encode(img)[0]),
+        with any sampler: image-conditioned sampling.  The one draw made for x_T, at its usual place in
+        the draw order, is the fixed noise e0 of the call.
+        strength in (0, 1]: img2img — the loop enters at position p0 = min(S, max(1, floor(strength S + 0.5)))
+        of its S positions (T for ddpm) from sqrt(ab) z0 + sqrt(1 - ab) e0 at that position's timestep
+        and runs p0 steps; None or p0 = S starts from e0 as every call does.
+        mask ((B,1,h,w), (1,1,h,w) or (h,w) in [0, 1]; 1 = regenerate, 0 = keep): inpainting — after
+        every step the latent is blended with z0's forward trajectory under e0 (known_tables), so the
+        result equals z0 exactly where mask == 0.  mask / strength need init_latent; with z_shape None
+        the shape is init_latent's and the VAE is not consulted (no encode draw)."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         device = self.device
         items = self._norm_counts(class_counts)
@@ -698,7 +802,10 @@ class Diffuser:
         y = torch.tensor(y_list, device=device, dtype=torch.long)
         vals, msk = self._build_cond(y_list, cond, cond_mask, key_order, class_keys, device)
 
-        if z_shape is None:
+        known = self._known_inputs(init_latent, mask, strength, B, z_shape)
+        if known is not None:
+            C, Hlat, Wlat = known[3]
+        elif z_shape is None:
             if vae is None:
                 raise ValueError("z_shape 省略時は vae が必要です。")
             C, Hlat, Wlat = self._latent_shape(vae, dummy_input_hw, device)
@@ -706,23 +813,52 @@ class Diffuser:
             C, Hlat, Wlat = z_shape
 
         x = self._randn((B, C, Hlat, Wlat), device)
-        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode)
+        x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
+                                **(dict(known=known[:3]) if known is not None else {}))
         if vae is None:
             return x
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         return self._decode(vae, x, to_pil)
 
-    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None):
+    def _known_setup(self, x, known, mode, total):
+        """The known-region state of a loop over `total` positions whose draw is x:
+        (x_start, p0, blend operands or None).  known = (z0, mask or None, strength) (_known_inputs).
+        p0 = total: x_start holds x's values.  Otherwise it is the blend's kn one table row up (position
+        p0 + 1 arrives at tau_p0), written to a new tensor.  Without a mask no step is blended."""
+        z0, kmask, strength = known
+        p0 = self._known_start(strength, total)
+        if p0 == total and kmask is None:
+            return x, p0, None
+        e0 = x.to(torch.float32).contiguous()
+        z0 = z0.to(x.device)
+        q_a, q_e = self.known_tables(self._mode_timesteps(mode), x.device)
+        if p0 < total:
+            pos = torch.full((1,), p0 + 1, dtype=torch.long, device=x.device)
+            x = _engine.known_blend(z0, pos, (z0, e0, None, q_a, q_e))
+        else:
+            x = e0.clone()  # (e0 stays a constant of the loop: in-place steps must not write it)
+        return x, p0, (z0, e0, kmask.to(x.device), q_a, q_e) if kmask is not None else None
+
+    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None):
         """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
         mode = ("ddim", S, eta) (_sampler_mode): the strided loop instead — the counter walks the S
         positions of ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and
         replay.  mode = ("dpm", S, spacing): likewise over dpm_tables(S, spacing); the solver's history
-        buffer lives here, and a replayed chunk restarts from the history it started with."""
+        buffer lives here, and a replayed chunk restarts from the history it started with.
+        known = (z0, mask or None, strength): x is the call's fixed draw e0; the loop enters at p0
+        (_known_setup) and, with a mask, every step on every path is followed by the known-region
+        blend.  z0, e0 and the mask are constants, so a replayed chunk needs nothing more."""
         ddim = mode[1:] if mode is not None and mode[0] == "ddim" else None
         dpm = mode is not None and mode[0] == "dpm"
         T = self.num_timesteps if mode is None else mode[1]
-        sched = (self.dpm_tables(mode[1], mode[2], x.device) if dpm
+        kkw, start = {}, None  # (without `known` every call below is the call it was)
+        if known is not None:
+            x, start, kn = self._known_setup(x, known, mode, T)
+            T = start  # from here: the p0 positions left to walk
+            if kn is not None:
+                kkw["known"] = kn
+        sched = (self.dpm_tables(mode[1], mode[2], x.device, start) if dpm
                  else self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None)
         native = _native_kind(model) in (1, 2) and x.is_cuda and guidance_scale and guidance_scale > 0
         bar = tqdm(total=T, desc="Sampling (cond+numeric)") if progress else None
@@ -733,6 +869,7 @@ class Diffuser:
             t_dev = torch.full((1,), T, device=x.device, dtype=torch.long)
             tables = self.coef_tables(x.device, clamp_prev=True) if sched is None else None
             skw = dict(sched=sched) if sched is not None else {}  # (the DDPM calls stay as they were)
+            skw.update(kkw)
             hist = None
             if dpm:  # position S does not read it: no initial value needed
                 hist = skw["hist"] = torch.empty_like(x, dtype=torch.float32)
@@ -777,12 +914,12 @@ class Diffuser:
             for i in range(i_from, i_to, -1):  # i in [1, T]: denoise_cond's assert holds by construction
                 t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
                 if sched is None:
-                    x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk)
+                    x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk, **kkw)
                 elif dpm:  # t holds the position
-                    x = self._dpm_step(model, x, t, sched, hist, y, guidance_scale, null_label, vals, msk)
+                    x = self._dpm_step(model, x, t, sched, hist, y, guidance_scale, null_label, vals, msk, **kkw)
                 else:
                     x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, guidance_scale, null_label, vals,
-                                        msk)
+                                        msk, **kkw)
                 if bar is not None:
                     bar.update(1)
             return x

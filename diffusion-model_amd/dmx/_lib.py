@@ -60,6 +60,12 @@ class DpmSched(ctypes.Structure):
                 ("hist", ctypes.c_void_p), ("S", ctypes.c_int)]
 
 
+class KnownSched(ctypes.Structure):
+    """dmx_known_sched (include/dmx.h): known latent, fixed draw, mask and per-position tables of a known-region loop."""
+    _fields_ = [("z0", ctypes.c_void_p), ("e0", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("q_a", ctypes.c_void_p), ("q_e", ctypes.c_void_p), ("S", ctypes.c_int)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -116,6 +122,11 @@ SIGNATURES = [
     ("dmx_step_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _P]),
     ("dmx_sample_loop_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _I, _I, _P]),
     ("dmx_dpm_update", _I, [_P, _P, _P, _P, ctypes.c_float, _P, _I, ctypes.POINTER(DpmSched), _I, _I, _I, _I, _P]),
+    ("dmx_known_blend", _I, [_P, _P, _P, _I, ctypes.POINTER(KnownSched), _I, _I, _I, _I, _P]),
+    ("dmx_step_known", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                            ctypes.POINTER(KnownSched), _P]),
+    ("dmx_sample_loop_known", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                                   ctypes.POINTER(KnownSched), _I, _I, _P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),
     ("dmx_eval_metrics", _I, [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P]),

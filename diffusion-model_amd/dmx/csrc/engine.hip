@@ -250,6 +250,7 @@ struct GraphKey {
   dmx_step_args a;
   dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
   dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
+  dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
@@ -1964,12 +1965,38 @@ static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
   p.hist = dp.hist;
 }
 
+// The blend's launch (kernels.h known_blend_kernel): float4 lanes where the rows and every pointer allow.
+static void launch_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_stride,
+                               const dmx_known_sched& kn, int n, int c, int hw, hipStream_t st) {
+  KnownBlendParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.x = x;
+  p.x_out = x_out;
+  p.z0 = kn.z0;
+  p.e0 = kn.e0;
+  p.mask = kn.mask;
+  p.q_a = kn.q_a;
+  p.q_e = kn.q_e;
+  p.pos = pos;
+  p.pos_stride = pos_stride;
+  p.S = kn.S;
+  p.HW = hw;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)kn.z0 | (uintptr_t)kn.e0 | (uintptr_t)kn.mask;
+  if (hw % 4 == 0 && bits % 16 == 0)
+    known_blend_kernel<true><<<dim3(cdiv(hw / 4, 256), c, n), 256, 0, st>>>(p);
+  else
+    known_blend_kernel<false><<<dim3(cdiv(hw, 256), c, n), 256, 0, st>>>(p);
+}
+
 // t_next (multi-step sample-loop graphs): the step's t - 1 is stored there by the embedding kernel.
 // sc (strided sampling, include/dmx.h dmx_ddim_sched): a.t holds positions, the tail applies the
 // DDIM update from sc's tables and a.c1 / c2 / sd / T are not read.
 // dp (include/dmx.h dmx_dpm_sched; at most one of sc / dp): the same with the DPM-Solver++(2M) update.
+// kn (include/dmx.h dmx_known_sched): the known-region blend follows the tail as a launch of its own,
+// on a.x_out in place, at the position the tail read.
 static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false,
-                      const dmx_ddim_sched* sc = nullptr, const dmx_dpm_sched* dp = nullptr) {
+                      const dmx_ddim_sched* sc = nullptr, const dmx_dpm_sched* dp = nullptr,
+                      const dmx_known_sched* kn = nullptr) {
   dmx_model* m = R.m;
   const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
   const int N = cfg ? 2 * a.n : a.n;
@@ -2030,6 +2057,13 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
   }
   R.end();
   HIPCHK(hipGetLastError());
+  if (kn != nullptr) {
+    R.layer = "known_blend";
+    R.begin("known_blend_kernel", 5.0 * a.n * p.Co * p.HW, 4.0 * (4.0 * p.Co + 1.0) * a.n * p.HW);
+    launch_known_blend(a.x_out, a.x_out, a.t, a.t_stride, *kn, a.n, p.Co, p.HW, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+  }
 }
 
 static void validate_sched(const dmx_ddim_sched* sc) {
@@ -2045,10 +2079,25 @@ static void validate_sched(const dmx_dpm_sched* dp) {
   REQUIRE(dp->hist != nullptr, "DPM schedule needs a history buffer");
 }
 
+static void validate_known(const dmx_known_sched* kn, const float* x_out) {
+  REQUIRE(kn != nullptr, "null known-region schedule");
+  REQUIRE(kn->S >= 1, "known-region schedule needs S >= 1 positions");
+  REQUIRE(kn->z0 && kn->e0 && kn->q_a && kn->q_e, "null tensor in known-region schedule");
+  REQUIRE(kn->z0 != x_out && kn->e0 != x_out && kn->mask != x_out, "z0 / e0 / mask must not alias x_out");
+}
+
 // sc / dp != null: the strided calls (a->c1 / c2 / sd / T are ignored there)
+// kn != null: the known-region calls, whose tables must cover the positions of the step's schedule
 static void validate_step(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc = nullptr,
-                          const dmx_dpm_sched* dp = nullptr) {
+                          const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr) {
   REQUIRE(a != nullptr, "null step args");
+  if (kn != nullptr) {
+    REQUIRE(sc == nullptr || dp == nullptr, "at most one of the DDIM and DPM schedules");
+    validate_known(kn, a->x_out);
+    REQUIRE(kn->mask != nullptr, "a known-region step needs a mask");
+    REQUIRE(a->n <= 65535, "known-region steps take at most 65535 samples");
+    REQUIRE(kn->S == (dp != nullptr ? dp->S : sc != nullptr ? sc->S : a->T), "known-region S differs from the schedule's");
+  }
   check_shapes(m, a->n, a->h, a->w);
   REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
   if (dp != nullptr) {
@@ -2553,17 +2602,30 @@ int dmx_step_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sche
   });
 }
 
+int dmx_step_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                   const dmx_known_sched* known, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr, "null model");
+    REQUIRE(known != nullptr, "null known-region schedule");
+    validate_step(m, a, ddim, dpm, known);
+    ensure_planes(m, (hipStream_t)stream);
+    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, ddim, dpm, known); });
+  });
+}
+
 static constexpr int kGraphSteps = 8;
 
 // dmx_sample_loop (sc == null) and dmx_sample_loop_ddim: the scalar a->t counts down by one per
 // step either way — timesteps in the first, positions of the schedule in the second.
 // dmx_sample_loop_dpm (dp != null, sc == null): positions again; the history buffer is updated in
 // place by every step, so it needs no ping-pong inside the multi-step graph.
+// kn != null (dmx_sample_loop_known): every step is followed by the known-region blend, which reads
+// the position scalar its tail read — the multi-step graph's ping-pong needs nothing more.
 static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc, int steps, int use_graph,
-                            void* stream, const dmx_dpm_sched* dp = nullptr) {
+                            void* stream, const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
-    validate_step(m, a, sc, dp);
+    validate_step(m, a, sc, dp, kn);
     REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
     REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
     REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
@@ -2573,7 +2635,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
     int64_t* tdev = const_cast<int64_t*>(a->t);
     if (!use_graph) {
       for (int i = 0; i < steps; ++i) {
-        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp); });
+        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp, kn); });
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
         HIPCHK(hipGetLastError());
       }
@@ -2610,6 +2672,16 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       key.dpm.hist = dp->hist;
       key.dpm.S = dp->S;
     }
+    if (kn != nullptr) {
+      // the known-region graphs also hold the blend's launches: its operands enter the key member by
+      // member, and S >= 1 keeps them apart from every plain key (known all zero)
+      key.known.z0 = kn->z0;
+      key.known.e0 = kn->e0;
+      key.known.mask = kn->mask;
+      key.known.q_a = kn->q_a;
+      key.known.q_e = kn->q_e;
+      key.known.S = kn->S;
+    }
     key.table_gen = m->ctx->table_gen;
     if (!(m->has_graph && key == m->gkey)) {
       drop_graph(m);
@@ -2619,7 +2691,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       m->ws.plan = true;
       {
         Run P{m, st, true, m->ws};
-        step_body(P, *a, nullptr, false, sc, dp);
+        step_body(P, *a, nullptr, false, sc, dp, kn);
       }
       ensure_ws(m);
       poison(m->ws_mem, m->ws.off, st);
@@ -2629,7 +2701,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       try {
         Run R{m, st, false, m->ws};
-        step_body(R, *a, nullptr, false, sc, dp);
+        step_body(R, *a, nullptr, false, sc, dp, kn);
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
       } catch (...) {
         hipGraph_t g;
@@ -2655,7 +2727,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
           Run R{m, st, false, m->ws};
           dmx_step_args ak = *a;
           ak.t = (k & 1) ? tscr : tdev;
-          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp);  // cond MLP rows from step 0 of the graph
+          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp, kn);  // cond MLP rows from step 0 of the graph
         }
       } catch (...) {
         hipGraph_t g;
@@ -2692,6 +2764,18 @@ int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sche
                         int use_graph, void* stream) {
   const int rc = guarded([&] { validate_sched(sched); });
   return rc != DMX_OK ? rc : sample_loop_impl(m, a, nullptr, steps, use_graph, stream, sched);
+}
+
+int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                          const dmx_dpm_sched* dpm, const dmx_known_sched* known, int steps, int use_graph,
+                          void* stream) {
+  const int rc = guarded([&] {
+    REQUIRE(known != nullptr, "null known-region schedule");
+    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
+    if (ddim != nullptr) validate_sched(ddim);
+    if (dpm != nullptr) validate_sched(dpm);
+  });
+  return rc != DMX_OK ? rc : sample_loop_impl(m, a, ddim, steps, use_graph, stream, dpm, known);
 }
 
 int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* recs, int cap, int* n_out,
@@ -2820,6 +2904,18 @@ int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* e
     set_sched(p, *sched);
     dim3 grid(cdiv(p.HW, 256), n);
     step_tail_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_stride,
+                    const dmx_known_sched* known, int n, int c, int h, int w, void* stream) {
+  return guarded([&] {
+    REQUIRE(x_out && pos, "null tensor");
+    validate_known(known, x_out);
+    REQUIRE(x != nullptr || known->mask == nullptr, "x may be NULL only without a mask");
+    REQUIRE(n >= 1 && n <= 65535 && c >= 1 && c <= 65535 && h >= 1 && w >= 1, "bad shape");
+    launch_known_blend(x, x_out, pos, pos_stride, *known, n, c, h * w, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
   });
 }

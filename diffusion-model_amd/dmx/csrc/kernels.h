@@ -949,6 +949,56 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
     p.x_out[idx] = ddpm_elem(p.x[idx], eps, p.c1[t - 1], p.c2[t - 1], p.sd[t - 1], nz);
 }
 
+// Known-region blend (include/dmx.h dmx_known_sched), a launch of its own after a step's tail: the
+// step's output xg at position p is overwritten outside the mask with the forward trajectory of the
+// known latent z0 under the fixed draw e0 at the step's target timestep s = tau_{p-1}:
+//   kn = q_a[p-1]*z0 + q_e[p-1]*e0;  x' = m == 0 ? kn : m == 1 ? xg : m*xg + (1-m)*kn
+// one rounding per op.  m == 0 and m == 1 are selects, not products: a non-finite xg under the mask
+// never reaches a kept element.  mask null: every element is kept, kn is written and x is not read
+// (the start latent of a truncated schedule).  x, x_out, z0, e0: NCHW [B][C][HW]; mask: [B][HW].
+struct KnownBlendParams {
+  const float* x; float* x_out;                       // x_out may alias x (same lane reads and writes)
+  const float* z0; const float* e0; const float* mask;
+  const float* q_a; const float* q_e;                 // [S], index p-1
+  const int64_t* pos; int pos_stride; int S;
+  int HW;
+};
+
+DMX_DEV float known_elem(float xg, float z0, float e0, float m, float qa, float qe) {
+  const float kn = rnd(qa * z0) + rnd(qe * e0);
+  return m == 0.f ? kn : m == 1.f ? xg : rnd(m * xg) + rnd(rnd(1.f - m) * kn);
+}
+
+// grid (cdiv(HW / (VEC ? 4 : 1), 256), C, B).  VEC: HW % 4 == 0 and every pointer 16-byte aligned.
+template <bool VEC>
+static __global__ __launch_bounds__(256) void known_blend_kernel(const KnownBlendParams p) {
+  const int n = blockIdx.z, c = blockIdx.y, C = gridDim.y;
+  const int pix = (blockIdx.x * 256 + threadIdx.x) * (VEC ? 4 : 1);
+  if (pix >= p.HW) return;
+  int64_t t = p.pos[(size_t)n * p.pos_stride];
+  t = t < 1 ? 1 : (t > p.S ? p.S : t);
+  const float qa = p.q_a[t - 1], qe = p.q_e[t - 1];
+  const size_t idx = ((size_t)n * C + c) * p.HW + pix, midx = (size_t)n * p.HW + pix;
+  if (VEC) {
+    const floatx4 z = ld4(p.z0 + idx), e = ld4(p.e0 + idx);
+    floatx4 m = {0.f, 0.f, 0.f, 0.f}, xg = {0.f, 0.f, 0.f, 0.f}, o;
+    if (p.mask != nullptr) {
+      m = ld4(p.mask + midx);
+      xg = ld4(p.x + idx);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = known_elem(xg[j], z[j], e[j], m[j], qa, qe);
+    st4(p.x_out + idx, o);
+  } else {
+    float m = 0.f, xg = 0.f;
+    if (p.mask != nullptr) {
+      m = p.mask[midx];
+      xg = p.x[idx];
+    }
+    p.x_out[idx] = known_elem(xg, p.z0[idx], p.e0[idx], m, qa, qe);
+  }
+}
+
 // conv1x1 64 -> Co + bias into NCHW (models/unet_cond.py:153, the `out` layer).
 static __global__ __launch_bounds__(256) void out_head_kernel(const float* feat, const float* w, const float* b, float* eps,
                                                        int Co, int HW, int* range_flag) {

@@ -169,8 +169,9 @@ class ShardedCondSampler:
 
     def sample(self, class_counts, z_shape=None, guidance_scale: float = 3.0, null_label: int = 0, cond=None,
                cond_mask=None, decode: bool = True, dummy_input_hw=(224, 224), sampler: str = "ddpm",
-               steps: Optional[int] = None, eta: float = 0.0,
-               spacing: Optional[str] = None) -> Optional[torch.Tensor]:
+               steps: Optional[int] = None, eta: float = 0.0, spacing: Optional[str] = None,
+               init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+               strength: Optional[float] = None) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -193,7 +194,12 @@ class ShardedCondSampler:
         order; with eta = 0 no rank draws per-step noise).  sampler="dpmpp_2m" with `spacing` walks
         the positions of the DPM-Solver++(2M) schedule: no rank draws anything after x_T (no seed
         either), and the solver's history buffer is shard-local (no collective); a replayed chunk
-        restarts from the history it started with."""
+        restarts from the history it started with.
+
+        init_latent / mask / strength as in Diffuser.sample_latent_cond, given for the global batch:
+        every rank takes its rows of them as it takes its rows of the global draws, the x_T draw being
+        the fixed noise e0.  The start latent and the per-step blend are shard-local (no collective),
+        and the loop walks the p0 positions the single-process sampler walks."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
@@ -209,7 +215,10 @@ class ShardedCondSampler:
         s, e = shard_range(B, ws, rank)
         y = torch.tensor(y_list[s:e], device=dev, dtype=torch.long)
         v, m = vals[s:e].float().contiguous(), msk[s:e].float().contiguous()
-        if z_shape is None:
+        known = d._known_inputs(init_latent, mask, strength, B, z_shape)
+        if known is not None:
+            z_shape = known[3]
+        elif z_shape is None:
             if self.vae is None:
                 raise ValueError("z_shape 省略時は vae が必要です。")
             z_shape = d._latent_shape(self.vae, dummy_input_hw, dev)
@@ -217,11 +226,19 @@ class ShardedCondSampler:
         nm = self.model.native() if e > s else None
         guard = d._guard_target(self.model) if nm is not None else None
         tables = d.coef_tables(dev, clamp_prev=True) if mode is None else None
-        sched = d.dpm_tables(mode[1], mode[2], dev) if dpm else d.ddim_tables(steps, eta, dev) if ddim else None
         T = int(steps) if mode is not None else d.num_timesteps  # the loop counter: timesteps, or positions
+        p0 = d._known_start(known[2], T) if known is not None else T  # the position the loop enters at
+        sched = (d.dpm_tables(mode[1], mode[2], dev, p0 if known is not None else None) if dpm
+                 else d.ddim_tables(steps, eta, dev) if ddim else None)
         draws = mode is None or (ddim and float(eta) > 0)  # DDIM with eta = 0 and DPM draw no per-step noise
         skw = dict(sched=sched) if mode is not None else {}  # (the DDPM calls stay exactly as they were)
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
+        if known is not None and e > s:  # this shard's rows of z0 / mask; x is its rows of e0
+            rows = (known[0][s:e], known[1][s:e] if known[1] is not None else None, known[2])
+            x, _, kn = d._known_setup(x, rows, mode, T)
+            if kn is not None:
+                skw["known"] = kn
+        T = p0
         hist = None
         if dpm:  # this shard's rows; position S does not read it, so it needs no initial value
             hist = skw["hist"] = torch.empty_like(x)

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimSched, DpmSched, StepArgs, check
+from ._lib import DdimSched, DpmSched, KnownSched, StepArgs, check
 
 TIME_DIM = 256
 
@@ -290,16 +290,19 @@ class NativeModel:
         return sc
 
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None, hist=None):
+             sample_offset=0, t_stride=1, sched=None, hist=None, known=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
         positions in [1, S] and `tables` is not read (may be None).
         sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place): one
-        DPM-Solver++(2M) step; `noise` must be None and `seed` is not read."""
+        DPM-Solver++(2M) step; `noise` must be None and `seed` is not read.
+        known (z0, e0, mask, q_a, q_e) with the tables of Diffuser.known_tables for the step's schedule
+        (the DDPM step: tau = 1..T): the known-region blend follows the step on x_out (known_blend)."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
         dpm = isinstance(sched, DpmSchedule)
+        kn = _known_struct(known, x_in.device, x_in, need_mask=True) if known is not None else None
         if sched is not None:
             sc = self._sched(sched, x_in.device, hist, x_in)
             tables = None
@@ -310,7 +313,11 @@ class NativeModel:
                        sample_offset)
         with torch.cuda.device(x_in.device):
             st = ctypes.c_void_p(_stream(x_in.device))
-            if dpm:
+            if kn is not None:
+                check(self.lib.dmx_step_known(self.handle, ctypes.byref(a),
+                                              ctypes.byref(sc) if sched is not None and not dpm else None,
+                                              ctypes.byref(sc) if dpm else None, ctypes.byref(kn), st))
+            elif dpm:
                 check(self.lib.dmx_step_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
             elif sched is not None:
                 check(self.lib.dmx_step_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
@@ -337,7 +344,7 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None, hist=None):
+                    use_graph=True, sched=None, hist=None, known=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -345,9 +352,12 @@ class NativeModel:
         sched (the 6-tuple of Diffuser.ddim_tables): strided DDIM steps; t_dev then holds the
         position in [1, S] and `tables` is not read (may be None).
         sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place):
-        DPM-Solver++(2M) steps, which draw nothing (`seed` is not read)."""
+        DPM-Solver++(2M) steps, which draw nothing (`seed` is not read).
+        known (z0, e0, mask, q_a, q_e) as in step(): every step is followed by the known-region blend.
+        A loop entering below position S starts from known_blend's start latent."""
         _check_state(x, "x")
         dpm = isinstance(sched, DpmSchedule)
+        kn = _known_struct(known, x.device, x, need_mask=True) if known is not None else None
         if sched is not None:
             sc = self._sched(sched, x.device, hist, x)
             tables = None
@@ -361,11 +371,17 @@ class NativeModel:
         cur = torch.cuda.current_stream(x.device)
         side = self.side_stream()
         side.wait_stream(cur)
-        for keep in (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables):
+        live = (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables) + tuple(known or ())
+        for keep in live:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if dpm:
+            if kn is not None:
+                check(self.lib.dmx_sample_loop_known(self.handle, ctypes.byref(a),
+                                                     ctypes.byref(sc) if sched is not None and not dpm else None,
+                                                     ctypes.byref(sc) if dpm else None, ctypes.byref(kn), int(steps),
+                                                     int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            elif dpm:
                 check(self.lib.dmx_sample_loop_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
                                                    int(use_graph), ctypes.c_void_p(side.cuda_stream)))
             elif sched is not None:
@@ -581,4 +597,62 @@ def dpm_update(x, eu, ec, guidance, pos, sched, hist, out=None):
     with torch.cuda.device(dev):
         check(lib.dmx_dpm_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
                                  ctypes.byref(sc), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+    return out
+
+
+def _known_struct(known, device, x, need_mask=False) -> KnownSched:
+    """The C view of a known region (z0, e0, mask, q_a, q_e): z0 / e0 contiguous fp32 of x's shape, mask
+    contiguous fp32 (n,1,h,w) or (n,h,w) (None where the caller allows: every element kept), q_a / q_e the
+    1-D fp32 tables of Diffuser.known_tables, all on `device`.  Nothing is converted: the kernels read the
+    caller's tensors.  Aliasing of x and S against the schedule are checked by the library."""
+    if not isinstance(known, (tuple, list)) or len(known) != 5:
+        raise ValueError("known must be the 5-tuple (z0, e0, mask, q_a, q_e)")
+    z0, e0, mask, q_a, q_e = known
+    n, _, h, w = x.shape
+    for v, nm in ((z0, "z0"), (e0, "e0")):
+        if (v.dtype != torch.float32 or not v.is_contiguous() or v.device != device
+                or tuple(v.shape) != tuple(x.shape)):
+            raise ValueError(f"known {nm} must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {device}")
+    if mask is None:
+        if need_mask:
+            raise ValueError("known mask is required here (None only in known_blend: every element kept)")
+    elif (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.device != device
+          or tuple(mask.shape) not in ((n, 1, h, w), (n, h, w))):
+        raise ValueError(f"known mask must be a contiguous fp32 tensor of shape {(n, 1, h, w)} on {device}")
+    S = int(q_a.numel())
+    for v, nm in ((q_a, "q_a"), (q_e, "q_e")):
+        if v.dtype != torch.float32 or v.dim() != 1 or v.numel() != S or not v.is_contiguous() or v.device != device:
+            raise ValueError(f"known {nm} must be a contiguous 1-D fp32 tensor of {S} entries on {device}")
+    if S < 1:
+        raise ValueError("known tables are empty")
+    return KnownSched(z0.data_ptr(), e0.data_ptr(), mask.data_ptr() if mask is not None else None,
+                      q_a.data_ptr(), q_e.data_ptr(), S)
+
+
+def known_blend(x, pos, known, out=None):
+    """The known-region blend alone (include/dmx.h dmx_known_blend), for duck-typed models and start
+    latents: returns x' = m == 0 ? kn : m == 1 ? x : m x + (1 - m) kn with kn = q_a[p-1] z0 + q_e[p-1] e0.
+    x: (n,C,h,w) on the GPU; pos: (n,) positions or one value for every sample, clamped to [1, S];
+    known: (z0, e0, mask, q_a, q_e) on x's device.  mask None: every element is kept, x' = kn, and x gives
+    only the shape (its values are not read; it may be z0 itself).
+    out: where x' goes (fp32, contiguous, x's shape; may be x itself, never z0 / e0 / mask), a new tensor
+    by default.  Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(x, "x")
+    dev = x.device
+    x_c = x.to(dtype=torch.float32).contiguous()
+    kn = _known_struct(known, dev, x_c)
+    n, c, h, w = x_c.shape
+    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
+    if p_c.numel() not in (1, n):
+        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
+    if out is None:
+        out = torch.empty_like(x_c)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev
+          or tuple(out.shape) != tuple(x_c.shape)):
+        raise ValueError(f"out must be a contiguous fp32 tensor of shape {tuple(x_c.shape)} on {dev}")
+    with torch.cuda.device(dev):
+        check(lib.dmx_known_blend(_ptr(x_c) if known[2] is not None else None, _ptr(out), _ptr(p_c),
+                                  0 if p_c.numel() == 1 and n > 1 else 1, ctypes.byref(kn), n, c, h, w,
+                                  ctypes.c_void_p(_stream(dev))))
     return out

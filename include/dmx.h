@@ -217,6 +217,43 @@ int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* e
                    const int64_t* pos, int pos_stride, const dmx_dpm_sched* sched, int n, int c, int h, int w,
                    void* stream);
 
+/* ---- Known-region sampling: img2img starts and masked inpainting (no reference counterpart).
+ * z0 is a known latent and e0 one fixed Gaussian draw, both (n,C,h,w); mask is (n,h,w) in [0,1],
+ * broadcast over channels, 1 = regenerate, 0 = keep.  Positions p in [1, S] and tau are those of
+ * the loop the blend follows (dmx_ddim_sched / dmx_dpm_sched; the DDPM loop: tau = 1..T, S = T).
+ * Row p-1 of the fp32 tables holds q_a = sqrt(ab[s]), q_e = sqrt(1 - ab[s]) for s = tau_{p-1}
+ * (tau_0 = 0, ab[0] = 1: row 0 is exactly (1, 0)).  After the step at position p has produced xg,
+ *   kn = q_a*z0 + q_e*e0;   x' = m == 0 ? kn : m == 1 ? xg : m*xg + (1-m)*kn
+ * one IEEE rounding per operation.  The two ends of the mask are selects: a non-finite xg where
+ * m != 0 cannot reach an element with m == 0, and those elements follow the forward trajectory of
+ * z0 under e0 down to z0 itself at p = 1.  Nothing is drawn.  All members are device pointers /
+ * counts owned by the caller and none may alias the x the blend writes. */
+typedef struct dmx_known_sched {
+  const float* z0;   /* (n,C,h,w) */
+  const float* e0;   /* (n,C,h,w) */
+  const float* mask; /* (n,h,w); NULL in dmx_known_blend: every element kept */
+  const float* q_a;  /* [S] each */
+  const float* q_e;
+  int S;
+} dmx_known_sched;
+
+/* The blend alone (duck-typed foreign models, and the start latent).  pos: device int64 positions,
+ * clamped to [1, S]; pos_stride 0 => one value for every sample.  x_out may alias x.
+ * known->mask NULL: x_out = kn and x is not read (may be NULL) — with pos = p0 + 1 this is the
+ * start latent sqrt(ab[tau_p0])*z0 + sqrt(1-ab[tau_p0])*e0 of a loop entering at p0 < S. */
+int dmx_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_stride,
+                    const dmx_known_sched* known, int n, int c, int h, int w, void* stream);
+/* dmx_step* / dmx_sample_loop* with the blend launched after the step's tail, reading the position
+ * the tail read and rewriting a->x_out in place.  At most one of ddim / dpm is non-NULL; both NULL:
+ * the DDPM step.  known->S must equal the schedule's S (a->T for DDPM) and known->mask must be
+ * given.  A captured graph belongs to one dmx_known_sched as it belongs to one schedule: the
+ * plain loops never replay a known-region graph, nor the reverse. */
+int dmx_step_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                   const dmx_known_sched* known, void* stream);
+int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                          const dmx_dpm_sched* dpm, const dmx_known_sched* known, int steps, int use_graph,
+                          void* stream);
+
 /* ---- VAE decode (replaces VAE.decode, vae.py:64-69, plus Diffuser.reverse_to_img's
  * x*255 -> clamp -> uint8, diff.py:58-62) ---------------------------------------------
  * z: (n,4,h,w); img: (n,3,8h,8w) fp32 or NULL; u8: (n,8h,8w,3) uint8 (HWC) or NULL. */

@@ -12,6 +12,9 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    known and the few-step legs are judged against it, not against a preset figure.  A model
    holds the graphs of one loop at a time: every leg first runs 8 steps untimed (capture), then 48 steps
    (six launches of the 8-step graph) between two device events.  Reported: the median over the rounds.
+   The known-region loop (img2img / inpainting: the same DPM-Solver++(2M) loop with the known-region blend
+   launched after every step) is measured likewise against the plain DPM loop, the plain leg twice per
+   round (legs dpmpp_2m_a, known, dpmpp_2m_b), and judged against that leg's own spread.
 2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
    (ddpm, T = 1000), (ddim, S = 50, eta = 0) and (dpmpp_2m, S = 20, log-SNR spacing): the first call (it captures the graphs) and the best of
    the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
@@ -95,6 +98,50 @@ def loop_legs(nm, d, dev, rounds):
             "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
 
 
+def known_legs(nm, d, dev, rounds):
+    """The DPM-Solver++(2M) loop with and without the known-region blend after every step: same schedule,
+    buffers and method as loop_legs; the blend's operands are a latent, a draw and a half-plane mask."""
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
+    g = torch.Generator().manual_seed(5)
+    z0, e0 = (torch.randn((B, 4, HW, HW), generator=g).to(dev) for _ in range(2))
+    kmask = torch.zeros((B, 1, HW, HW), device=dev)
+    kmask[..., HW // 2:] = 1.0
+    known = (z0, e0, kmask) + tuple(d.known_tables(d.dpm_timesteps(S, "logsnr"), dev))
+
+    def leg(blend):
+        kw = dict(sched=sched, hist=hist, known=known) if blend else dict(sched=sched, hist=hist)
+        x.copy_(x0)
+        t_dev.fill_(S)
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, None, WARM, **kw)  # captures this loop's graphs
+        x.copy_(x0)
+        t_dev.fill_(S)
+        torch.cuda.synchronize()
+        e_0, e_1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_0.record()
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, None, TIMED, **kw)
+        e_1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == S - TIMED and bool(torch.isfinite(x).all())
+        return e_0.elapsed_time(e_1) / TIMED
+
+    ms = {"dpmpp_2m_a": [], "known": [], "dpmpp_2m_b": []}
+    leg(False)
+    for _ in range(rounds):
+        ms["dpmpp_2m_a"].append(leg(False))
+        ms["known"].append(leg(True))
+        ms["dpmpp_2m_b"].append(leg(False))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    plain_mean = 0.5 * (med["dpmpp_2m_a"] + med["dpmpp_2m_b"])
+    return {"ms_per_step_dpmpp_2m_a": round(med["dpmpp_2m_a"], 4),
+            "ms_per_step_dpmpp_2m_b": round(med["dpmpp_2m_b"], 4), "ms_per_step_known": round(med["known"], 4),
+            "dpmpp_2m_spread_ms": round(abs(med["dpmpp_2m_a"] - med["dpmpp_2m_b"]), 4),
+            "known_minus_dpmpp_2m_mean_ms": round(med["known"] - plain_mean, 4),
+            "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
+
+
 def end_to_end(model, dev):
     import diff
     from dmx import synth
@@ -145,6 +192,7 @@ def main():
     res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
            "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
            "loops": loop_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds),
+           "known_loops": known_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds),
            "end_to_end": end_to_end(model, dev)}
     print(json.dumps(res))
 
