@@ -26,6 +26,10 @@ What changes is where the work happens:
   mask=m, strength=s)`` starts any of the three samplers from z0 noised to an intermediate
   position (img2img) and / or holds the latent outside ``m`` on z0's forward trajectory after
   every step (inpainting; ``known_tables``, libdmx ``dmx_known_blend``).
+* Guidance controls (not in the reference): ``sample_latent_cond(..., guidance_interval=(t_lo, t_hi),
+  guidance_rescale=phi)`` applies CFG only to the steps whose timestep lies in the interval — the others
+  are one conditional forward — and scales the guided prediction to the conditional one's per-sample
+  standard deviation (libdmx ``dmx_step_guided`` / ``dmx_cfg_rescale``).
 """
 from __future__ import annotations
 
@@ -330,6 +334,59 @@ class Diffuser:
             raise ValueError(f'spacing must be None, "logsnr" or "uniform" (got {spacing!r})')
         return ("dpm", int(steps), spacing)
 
+    # ---- guidance controls: CFG interval and CFG rescale ---------------------------------------
+    @staticmethod
+    def _guidance_args(guidance_scale, guidance_interval, guidance_rescale, T):
+        """Argument rules of the samplers' (guidance_interval, guidance_rescale) keywords ->
+        (None or (t_lo, t_hi) ints, phi float).  The interval bounds are network timesteps with
+        1 <= t_lo <= t_hi <= T, phi lies in [0, 1], and either control needs guidance_scale > 0.
+        Every violation raises ValueError."""
+        try:
+            phi = float(guidance_rescale)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_rescale must be a number in [0, 1] (got {guidance_rescale!r})") from None
+        if not 0.0 <= phi <= 1.0:  # (NaN fails both comparisons)
+            raise ValueError(f"guidance_rescale must be in [0, 1] (got {guidance_rescale})")
+        interval = None
+        if guidance_interval is not None:
+            iv = guidance_interval
+            ok = isinstance(iv, (tuple, list)) and len(iv) == 2 and all(
+                isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in iv)
+            if not ok or not 1 <= int(iv[0]) <= int(iv[1]) <= int(T):
+                raise ValueError(f"guidance_interval must be None or ints (t_lo, t_hi) with 1 <= t_lo <= t_hi <= {T} "
+                                 f"(got {guidance_interval!r})")
+            interval = (int(iv[0]), int(iv[1]))
+        if (interval is not None or phi > 0.0) and not (guidance_scale is not None and guidance_scale > 0):
+            raise ValueError("guidance_interval / guidance_rescale need guidance_scale > 0 "
+                             f"(got guidance_scale={guidance_scale!r})")
+        return interval, phi
+
+    @staticmethod
+    def _guided_run(tau, interval):
+        """The positions of the ascending timesteps `tau` (tau_p at index p-1) whose step uses CFG:
+        (p_lo, p_hi), inclusive, for the timesteps inside interval = (t_lo, t_hi); (1, S) for interval
+        None; None when no timestep of the schedule lies inside.  tau ascends, so the run is contiguous."""
+        S = len(tau)
+        if interval is None:
+            return (1, S)
+        inside = [p for p in range(1, S + 1) if interval[0] <= tau[p - 1] <= interval[1]]
+        return (inside[0], inside[-1]) if inside else None
+
+    @staticmethod
+    def _guidance_segments(i_from, i_to, run):
+        """The steps at positions i_from, i_from - 1, .., i_to + 1 (a guard chunk, or a whole loop) cut
+        where the step kind changes: a list of (a, b, guided), each covering positions a down to b + 1,
+        guided iff they lie inside run = (p_lo, p_hi) (_guided_run; None: nothing is guided).  At most
+        three segments, in walking order; empty when i_from <= i_to."""
+        i_from, i_to = int(i_from), int(i_to)
+        if i_from <= i_to:
+            return []
+        if run is None:
+            return [(i_from, i_to, False)]
+        p_lo, p_hi = run
+        cuts = sorted({i_from, i_to, min(max(p_hi, i_to), i_from), min(max(p_lo - 1, i_to), i_from)}, reverse=True)
+        return [(a, b, p_lo <= a <= p_hi) for a, b in zip(cuts, cuts[1:])]
+
     @staticmethod
     def _check_sampler(sampler, steps, eta, T):
         """Argument rules of the samplers' (sampler, steps, eta) keywords -> True for the strided path."""
@@ -434,13 +491,32 @@ class Diffuser:
         return self._denoise_cond(model, x, t, y, guidance_scale, null_label, cond_vals, cond_mask)
 
     def _denoise_cond(self, model, x, t, y=None, guidance_scale=0.0, null_label=0, cond_vals=None, cond_mask=None,
-                      known=None):
+                      known=None, unguided=False, rescale=0.0):
         """denoise_cond after the range check — the samplers' own loops build t from a host-known
         step in [1, T] and call this directly, so the host never waits on the device per step.
         known (engine.known_blend's 5-tuple, tables over tau = 1..T): the known-region blend follows
-        the step — inside the native step, or as a launch of its own after a foreign model's update."""
+        the step — inside the native step, or as a launch of its own after a foreign model's update.
+        unguided (the samplers' steps outside a guidance interval; y given): one conditional forward,
+        eps = model(x, t, y, cond_vals, cond_mask), whatever guidance_scale says — the public branch
+        for "y without guidance" below mirrors the reference's error instead.
+        rescale = phi > 0 (guided steps only): the guided prediction is scaled to the conditional
+        one's per-sample standard deviation before the update (engine.cfg_rescale)."""
         tables = self.coef_tables(x.device, clamp_prev=True)
         with torch.no_grad():
+            if unguided:
+                if _native_kind(model) in (1, 2) and x.is_cuda:
+                    noise = self._step_noise(x)
+                    out = torch.empty_like(x)
+                    use = cond_vals is not None and cond_mask is not None
+                    model.native().step(x.contiguous(), out, t.to(x.device), y.to(x.device), null_label,
+                                        cond_vals if use else None, cond_mask if use else None, 0.0, tables, noise,
+                                        seed=self._seed() if noise is None else 0, known=known)
+                    return out
+                eps = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
+                eps = eps[0] if isinstance(eps, (tuple, list)) else eps
+                noise = self._step_noise(x)
+                return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
+                                                       seed=self._seed() if noise is None else 0), t, known)
             if guidance_scale and y is not None and guidance_scale > 0:
                 kind = _native_kind(model)
                 if kind in (1, 2) and x.is_cuda:
@@ -450,11 +526,15 @@ class Diffuser:
                     model.native().step(x.contiguous(), out, t.to(x.device), y.to(x.device), null_label,
                                         cond_vals if use else None, cond_mask if use else None,
                                         float(guidance_scale), tables, noise,
-                                        seed=self._seed() if noise is None else 0, known=known)
+                                        seed=self._seed() if noise is None else 0, known=known,
+                                        **(dict(rescale=float(rescale)) if rescale > 0 else {}))
                     return out
                 y_null = torch.full_like(y, null_label)
                 eps_uncond, _ = model(x, t, y_null, cond_vals=cond_vals, cond_mask=cond_mask)
                 eps_cond, _ = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
+                if rescale > 0:  # the standalone kernel, then the update on its eps
+                    eps_uncond, _ = _engine.cfg_rescale(eps_uncond, eps_cond, float(guidance_scale), float(rescale))
+                    eps_cond, guidance_scale = None, 0.0
                 noise = self._step_noise(x)
                 return self._blend(_engine.ddpm_update(x, eps_uncond, eps_cond, float(guidance_scale), t, tables,
                                                        noise, seed=self._seed() if noise is None else 0), t, known)
@@ -486,9 +566,10 @@ class Diffuser:
                                guidance_scale, null_label, cond_vals, cond_mask)
 
     def _ddim_step(self, model, x, pos, sched, noisy, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                   cond_mask=None, known=None):
+                   cond_mask=None, known=None, rescale=0.0):
         """ddim_step after its checks; `noisy`: the schedule has noise (eta > 0).  Host-noise mode then
-        draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws."""
+        draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws.
+        rescale = phi > 0 (CFG steps only): as in _denoise_cond."""
         cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
         g = float(guidance_scale) if cfg else 0.0
         pos = pos.to(device=x.device, dtype=torch.long)
@@ -502,7 +583,8 @@ class Diffuser:
                 use = cond_vals is not None and cond_mask is not None
                 model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
                                     cond_mask if use else None, g, None, noise,
-                                    seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known)
+                                    seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known,
+                                    **(dict(rescale=float(rescale)) if cfg and rescale > 0 else {}))
                 return out
 
             t = sched[0][pos - 1]
@@ -513,6 +595,8 @@ class Diffuser:
 
             eu = eps_of(torch.full_like(y, null_label) if cfg else y)
             ec = eps_of(y) if cfg else None
+            if cfg and rescale > 0:  # the standalone kernel, then the update on its eps
+                eu, ec, g = _engine.cfg_rescale(eu, ec, g, float(rescale))[0], None, 0.0
         noise = self._step_noise(x) if noisy else None
         return self._blend(_engine.ddim_update(x, eu, ec, g, pos, sched, noise,
                                                seed=self._seed() if noisy and noise is None else 0), pos, known)
@@ -529,8 +613,9 @@ class Diffuser:
                               null_label, cond_vals, cond_mask)
 
     def _dpm_step(self, model, x, pos, sched, hist, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                  cond_mask=None, known=None):
-        """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update."""
+                  cond_mask=None, known=None, rescale=0.0):
+        """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update.
+        rescale = phi > 0 (CFG steps only): as in _denoise_cond."""
         cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
         g = float(guidance_scale) if cfg else 0.0
         pos = pos.to(device=x.device, dtype=torch.long)
@@ -542,7 +627,8 @@ class Diffuser:
                 out = torch.empty_like(x_in)
                 use = cond_vals is not None and cond_mask is not None
                 model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
-                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist, known=known)
+                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist, known=known,
+                                    **(dict(rescale=float(rescale)) if cfg and rescale > 0 else {}))
                 return out
 
             t = sched[0][pos - 1]
@@ -553,6 +639,8 @@ class Diffuser:
 
             eu = eps_of(torch.full_like(y, null_label) if cfg else y)
             ec = eps_of(y) if cfg else None
+            if cfg and rescale > 0:
+                eu, ec, g = _engine.cfg_rescale(eu, ec, g, float(rescale))[0], None, 0.0
         return self._blend(_engine.dpm_update(x, eu, ec, g, pos, sched, hist), pos, known)
 
     # ---- loops --------------------------------------------------------------------------------
@@ -770,6 +858,8 @@ class Diffuser:
         init_latent: Optional[torch.Tensor] = None,
         mask: Optional[torch.Tensor] = None,
         strength: Optional[float] = None,
+        guidance_interval: Optional[Tuple[int, int]] = None,
+        guidance_rescale: float = 0.0,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -791,8 +881,17 @@ class Diffuser:
         mask ((B,1,h,w), (1,1,h,w) or (h,w) in [0, 1]; 1 = regenerate, 0 = keep): inpainting — after
         every step the latent is blended with z0's forward trajectory under e0 (known_tables), so the
         result equals z0 exactly where mask == 0.  mask / strength need init_latent; with z_shape None
-        the shape is init_latent's and the VAE is not consulted (no encode draw)."""
+        the shape is init_latent's and the VAE is not consulted (no encode draw).
+
+        guidance_interval = (t_lo, t_hi), network timesteps with 1 <= t_lo <= t_hi <= num_timesteps, with
+        any sampler (Kynkäänniemi et al. 2024): a step whose timestep lies inside uses CFG, every other
+        step takes the conditional prediction alone — one B-sample forward instead of the 2B one.  An
+        interval that holds no timestep of the schedule leaves the whole loop conditional-only; None
+        guides every step.  guidance_rescale = phi in [0, 1] (Lin et al. 2023, §3.4), guided steps only:
+        the guided prediction eg is scaled per sample by 1 + phi (std(ec) / std(eg) - 1), ec being the
+        conditional prediction.  Both need guidance_scale > 0 and neither changes the draw order."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
+        interval, phi = self._guidance_args(guidance_scale, guidance_interval, guidance_rescale, self.num_timesteps)
         device = self.device
         items = self._norm_counts(class_counts)
         y_list: List[int] = []
@@ -813,8 +912,13 @@ class Diffuser:
             C, Hlat, Wlat = z_shape
 
         x = self._randn((B, C, Hlat, Wlat), device)
+        gkw = {}  # (with both keywords at their defaults the loop is called as it was)
+        if interval is not None:
+            gkw["interval"] = interval
+        if phi > 0:
+            gkw["rescale"] = phi
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
-                                **(dict(known=known[:3]) if known is not None else {}))
+                                **(dict(known=known[:3]) if known is not None else {}), **gkw)
         if vae is None:
             return x
         if torch.cuda.is_available():
@@ -840,7 +944,8 @@ class Diffuser:
             x = e0.clone()  # (e0 stays a constant of the loop: in-place steps must not write it)
         return x, p0, (z0, e0, kmask.to(x.device), q_a, q_e) if kmask is not None else None
 
-    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None):
+    def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
+                       interval=None, rescale=0.0):
         """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
         mode = ("ddim", S, eta) (_sampler_mode): the strided loop instead — the counter walks the S
         positions of ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and
@@ -848,7 +953,17 @@ class Diffuser:
         buffer lives here, and a replayed chunk restarts from the history it started with.
         known = (z0, mask or None, strength): x is the call's fixed draw e0; the loop enters at p0
         (_known_setup) and, with a mask, every step on every path is followed by the known-region
-        blend.  z0, e0 and the mask are constants, so a replayed chunk needs nothing more."""
+        blend.  z0, e0 and the mask are constants, so a replayed chunk needs nothing more.
+        interval = (t_lo, t_hi) / rescale = phi (_guidance_args): the positions whose timestep lies
+        outside the interval run unguided (one conditional forward), the others with CFG and, for
+        phi > 0, the rescaled prediction.  Every chunk is walked segment by segment
+        (_guidance_segments); a replayed chunk walks the same segments."""
+        run_g = self._guided_run(self._mode_timesteps(mode), interval) if interval is not None else True
+        rkw = dict(rescale=float(rescale)) if rescale > 0 else {}
+
+        def segments(i_from, i_to):  # without an interval: the one guided piece every chunk was
+            return [(i_from, i_to, True)] if run_g is True else self._guidance_segments(i_from, i_to, run_g)
+
         ddim = mode[1:] if mode is not None and mode[0] == "ddim" else None
         dpm = mode is not None and mode[0] == "dpm"
         T = self.num_timesteps if mode is None else mode[1]
@@ -877,21 +992,25 @@ class Diffuser:
             v, m = vals.float().contiguous(), msk.float().contiguous()
             guard = self._guard_target(model)
             done = 0
+
+            def launch(p, k):  # k steps from position p; the position scalar runs on across the segments
+                for a, b, guided in segments(p, p - k):
+                    nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0, tables,
+                                   a - b, seed=seed, use_graph=self.use_graph, **skw, **(rkw if guided else {}))
+
             with torch.no_grad():
                 while done < T:
                     k = min(self.GUARD_CHUNK, T - done)
                     x0 = x.clone() if guard is not None else None
                     h0 = hist.clone() if guard is not None and dpm else None
-                    nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k, seed=seed,
-                                   use_graph=self.use_graph, **skw)
+                    launch(T - done, k)
                     if guard is not None and guard.range_tripped():
                         x.copy_(x0)
                         if dpm:
                             hist.copy_(h0)
                         t_dev.fill_(T - done)
                         with guard.precision_override("fp32"):
-                            nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, k,
-                                           seed=seed, use_graph=self.use_graph, **skw)
+                            launch(T - done, k)
                         guard.range_tripped()
                         self.range_fallbacks += 1
                     done += k
@@ -913,13 +1032,16 @@ class Diffuser:
                 snap[0] = hist.clone()
             for i in range(i_from, i_to, -1):  # i in [1, T]: denoise_cond's assert holds by construction
                 t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
-                if sched is None:
-                    x = self._denoise_cond(model, x, t, y, guidance_scale, null_label, vals, msk, **kkw)
+                guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
+                gs = guidance_scale if guided else 0.0
+                skw = dict(kkw, **rkw) if guided else kkw
+                if sched is None:  # (the unguided DDPM step: not the public branch, which mirrors an error)
+                    x = self._denoise_cond(model, x, t, y, gs, null_label, vals, msk, **skw,
+                                           **({} if guided else dict(unguided=True)))
                 elif dpm:  # t holds the position
-                    x = self._dpm_step(model, x, t, sched, hist, y, guidance_scale, null_label, vals, msk, **kkw)
+                    x = self._dpm_step(model, x, t, sched, hist, y, gs, null_label, vals, msk, **skw)
                 else:
-                    x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, guidance_scale, null_label, vals,
-                                        msk, **kkw)
+                    x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, gs, null_label, vals, msk, **skw)
                 if bar is not None:
                     bar.update(1)
             return x

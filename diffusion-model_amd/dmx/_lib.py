@@ -66,6 +66,11 @@ class KnownSched(ctypes.Structure):
                 ("q_a", ctypes.c_void_p), ("q_e", ctypes.c_void_p), ("S", ctypes.c_int)]
 
 
+class Guidance(ctypes.Structure):
+    """dmx_guidance (include/dmx.h): the guidance controls of a CFG step beyond its scale."""
+    _fields_ = [("rescale", ctypes.c_float)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -127,6 +132,13 @@ SIGNATURES = [
                             ctypes.POINTER(KnownSched), _P]),
     ("dmx_sample_loop_known", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
                                    ctypes.POINTER(KnownSched), _I, _I, _P]),
+    ("dmx_step_guided", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                             ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance), _P]),
+    ("dmx_sample_loop_guided", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched),
+                                    ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
+                                    _I, _I, _P]),
+    ("dmx_cfg_rescale", _I, [_P, _P, ctypes.c_float, ctypes.c_float, _P, _P, _I, _I, _I, _I, _P]),
+    ("dmx_model_graph_captures", _I64, [_P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),
     ("dmx_eval_metrics", _I, [_P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P]),

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "graph_slots.h"
 #include "igemm.h"
 #include "igemm_x3.h"
 #include "kernels.h"
@@ -251,9 +252,19 @@ struct GraphKey {
   dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
   dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
   dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
+  dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
+
+// One captured loop: the one-step graph and the same step captured kGraphSteps times back to back.
+struct GraphPair {
+  hipGraphExec_t gexec;
+  hipGraph_t graph;
+  hipGraphExec_t gexec_k;
+  hipGraph_t graph_k;
+};
+static constexpr int kGraphSlots = 4;
 
 struct Tape;  // training forward record (train_engine.h)
 struct VaeTape;  // the VAE's (vae_train_engine.h)
@@ -300,12 +311,11 @@ struct dmx_model {
   dmx::Arena ws;
   void* ws_mem = nullptr;
   size_t ws_cap = 0;
-  hipGraphExec_t gexec = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec_k = nullptr;  // the same step captured kGraphSteps times back to back
-  hipGraph_t graph_k = nullptr;
-  dmx::GraphKey gkey{};
-  bool has_graph = false;
+  // The graph pairs of the last kGraphSlots distinct loops (graph_slots.h: least recently used is
+  // replaced).  All of them point into ws_mem and replay one after another on one stream; that is
+  // safe only while ws_mem is never reallocated under a live slot (ensure_ws drops them all first).
+  dmx::LruSlots<dmx::GraphKey, dmx::GraphPair, dmx::kGraphSlots> graphs;
+  int64_t graph_captures = 0;  // pairs captured so far (dmx_model_graph_captures)
   // debug taps: (name, device pointer into the workspace, element count, C)
   bool debug = false;
   int prec = 1;  // 0: fp32 MFMA (exact fp32 products), 1: fp16 hi/lo x3 split MFMA, 2: fp16 (config 4)
@@ -1849,16 +1859,21 @@ static void check_shapes(dmx_model* m, int n, int h, int w) {
   REQUIRE(m->ctx->pos_table != nullptr, "time table not set (dmx_set_time_table)");
 }
 
+using GraphSlot = decltype(dmx_model::graphs)::Slot;
+
+// Free what one slot owns (any of the four handles may still be null after a failed capture).
+static void drop_slot(dmx_model* m, GraphSlot* s) {
+  if (s->val.gexec) (void)hipGraphExecDestroy(s->val.gexec);
+  if (s->val.graph) (void)hipGraphDestroy(s->val.graph);
+  if (s->val.gexec_k) (void)hipGraphExecDestroy(s->val.gexec_k);
+  if (s->val.graph_k) (void)hipGraphDestroy(s->val.graph_k);
+  m->graphs.release(s);
+}
+
+// Every captured graph goes: whatever invalidates one (the arena moved, other GEMM arithmetic,
+// re-derived weight planes, a failed capture, teardown) invalidates all of them.
 static void drop_graph(dmx_model* m) {
-  if (m->has_graph) {
-    (void)hipGraphExecDestroy(m->gexec);
-    (void)hipGraphDestroy(m->graph);
-    if (m->gexec_k) (void)hipGraphExecDestroy(m->gexec_k);
-    if (m->graph_k) (void)hipGraphDestroy(m->graph_k);
-    m->gexec_k = nullptr;
-    m->graph_k = nullptr;
-    m->has_graph = false;
-  }
+  for (GraphSlot& s : m->graphs.slot) drop_slot(m, &s);
 }
 
 // Re-derive the f16 planes of the split GEMMs after dmx_model_refresh (weights changed in
@@ -1994,11 +2009,16 @@ static void launch_known_blend(const float* x, float* x_out, const int64_t* pos,
 // dp (include/dmx.h dmx_dpm_sched; at most one of sc / dp): the same with the DPM-Solver++(2M) update.
 // kn (include/dmx.h dmx_known_sched): the known-region blend follows the tail as a launch of its own,
 // on a.x_out in place, at the position the tail read.
+// gd (include/dmx.h dmx_guidance) with rescale > 0, a CFG step: the tail becomes three launches
+// (guidance.h, through launch.h) whose eg and block partials come from the arena, in the dry run as in
+// the real one; they read the position scalar the tail reads, through step_tail_kernel.
 static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false,
                       const dmx_ddim_sched* sc = nullptr, const dmx_dpm_sched* dp = nullptr,
-                      const dmx_known_sched* kn = nullptr) {
+                      const dmx_known_sched* kn = nullptr, const dmx_guidance* gd = nullptr) {
   dmx_model* m = R.m;
   const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
+  const bool resc = gd != nullptr && gd->rescale > 0.f;
+  REQUIRE(!resc || cfg, "guidance rescale needs a CFG step (guidance > 0, y given, a conditional model)");
   const int N = cfg ? 2 * a.n : a.n;
   FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
   in.t_next = t_next;
@@ -2011,6 +2031,10 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
     in.n_pos = dp->S;
   }
   float* feat = unet_trunk(R, in, N, a.h, a.w);
+  const int pixb = m->in_ch == 4 ? 16 : 256;  // pixels per block of the rescaled tail's first stage
+  const int nb = cdiv(a.h * a.w, pixb);
+  float* eg = resc ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
+  double* part = resc ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
   if (R.plan) return;
   StepTailParams p;
   std::memset(&p, 0, sizeof(p));
@@ -2042,7 +2066,28 @@ static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr,
     p.sd = a.sd;
   }
   R.layer = dpm ? "out+cfg+dpm" : ddim ? "out+cfg+ddim" : "out+cfg+ddpm";
-  if (p.Co == 4 && p.feat != nullptr) {
+  if (resc) {
+    const double el = (double)a.n * p.Co * p.HW;
+    R.begin(p.Co == 4 ? "cfg_stats4_kernel" : "cfg_stats_kernel", 2.0 * N * p.HW * 64.0 * p.Co,
+            4.0 * ((double)N * p.HW * 64 + el));
+    CfgHeadParams hp{p.feat, p.w, p.b, p.Co, p.B, p.HW, p.guidance, p.range_flag};
+    launch_cfg_stats(hp, eg, part, nb, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+    R.begin("cfg_scale_kernel", el, 8.0 * el);
+    launch_cfg_scale(eg, part, nb, pixb, p.Co, p.HW, a.n, gd->rescale, nullptr, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+    // the update on the scaled eg: the tail's precomputed-eps form (it raises the range flag on it)
+    p.feat = nullptr;
+    p.cfg = 0;
+    p.eps_u = eg;
+    dim3 grid(cdiv(p.HW, 256), a.n);
+    R.begin("step_tail_kernel", 8.0 * el, 4.0 * 4.0 * el);
+    if (dpm) step_tail_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
+    else if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
+    else step_tail_kernel<false><<<grid, 256, 0, R.st>>>(p);
+  } else if (p.Co == 4 && p.feat != nullptr) {
     dim3 grid(cdiv(p.HW, 16), a.n);
     R.begin("step_tail4_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
     if (dpm) step_tail4_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
@@ -2621,11 +2666,15 @@ static constexpr int kGraphSteps = 8;
 // place by every step, so it needs no ping-pong inside the multi-step graph.
 // kn != null (dmx_sample_loop_known): every step is followed by the known-region blend, which reads
 // the position scalar its tail read — the multi-step graph's ping-pong needs nothing more.
+// gd != null with rescale > 0 (dmx_sample_loop_guided): every step is a rescaled CFG step; phi enters
+// the graph key.  rescale == 0 leaves key and launches exactly those of the plain loop.
 static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc, int steps, int use_graph,
-                            void* stream, const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr) {
+                            void* stream, const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr,
+                            const dmx_guidance* gd = nullptr) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
     validate_step(m, a, sc, dp, kn);
+    if (gd != nullptr && !(gd->rescale > 0.f)) gd = nullptr;
     REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
     REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
     REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
@@ -2635,7 +2684,7 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
     int64_t* tdev = const_cast<int64_t*>(a->t);
     if (!use_graph) {
       for (int i = 0; i < steps; ++i) {
-        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp, kn); });
+        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp, kn, gd); });
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
         HIPCHK(hipGetLastError());
       }
@@ -2682,18 +2731,22 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       key.known.q_e = kn->q_e;
       key.known.S = kn->S;
     }
+    if (gd != nullptr) key.gd.rescale = gd->rescale;  // (all zero on every other path)
     key.table_gen = m->ctx->table_gen;
-    if (!(m->has_graph && key == m->gkey)) {
-      drop_graph(m);
+    GraphSlot* slot = m->graphs.find(key);
+    if (slot == nullptr) {
       // plan + allocate outside capture, then capture the real launches
       m->ws.base = nullptr;
       m->ws.off = 0;
       m->ws.plan = true;
       {
         Run P{m, st, true, m->ws};
-        step_body(P, *a, nullptr, false, sc, dp, kn);
+        step_body(P, *a, nullptr, false, sc, dp, kn, gd);
       }
-      ensure_ws(m);
+      ensure_ws(m);  // (a grown arena drops every slot: their graphs point into the old one)
+      slot = m->graphs.victim();
+      drop_slot(m, slot);  // a free slot, or the least recently used pair makes room
+      GraphPair& gp = slot->val;
       poison(m->ws_mem, m->ws.off, st);
       m->ws.base = static_cast<char*>(m->ws_mem);
       m->ws.off = 0;
@@ -2701,17 +2754,23 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
       HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       try {
         Run R{m, st, false, m->ws};
-        step_body(R, *a, nullptr, false, sc, dp, kn);
+        step_body(R, *a, nullptr, false, sc, dp, kn, gd);
         decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
       } catch (...) {
-        hipGraph_t g;
+        hipGraph_t g = nullptr;
         (void)hipStreamEndCapture(st, &g);
         if (g) (void)hipGraphDestroy(g);
+        drop_graph(m);
         throw;
       }
-      HIPCHK(hipStreamEndCapture(st, &m->graph));
-      HIPCHK(hipGraphInstantiate(&m->gexec, m->graph, nullptr, nullptr, 0));
-      m->has_graph = true;  // owns gexec / graph from here (drop_graph frees them on any failure below)
+      // the slot owns each handle from the moment it is stored; it is not `used` (no key can find
+      // it) until both graphs are instantiated, and any failure on the way drops every slot
+      const hipError_t e1 = hipStreamEndCapture(st, &gp.graph);
+      const hipError_t i1 = e1 == hipSuccess ? hipGraphInstantiate(&gp.gexec, gp.graph, nullptr, nullptr, 0) : e1;
+      if (i1 != hipSuccess) {
+        drop_graph(m);
+        HIPCHK(i1);
+      }
       // kGraphSteps consecutive steps in one graph: the gap between two graph launches (≈9 µs of
       // idle GPU per step in the replay trace) is paid once per kGraphSteps steps.  Inside it, t
       // alternates between the caller's scalar and a scratch scalar: step k reads one and its
@@ -2727,26 +2786,27 @@ static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim
           Run R{m, st, false, m->ws};
           dmx_step_args ak = *a;
           ak.t = (k & 1) ? tscr : tdev;
-          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp, kn);  // cond MLP rows from step 0 of the graph
+          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp, kn, gd);  // cond MLP rows from step 0 of the graph
         }
       } catch (...) {
-        hipGraph_t g;
+        hipGraph_t g = nullptr;
         (void)hipStreamEndCapture(st, &g);
         if (g) (void)hipGraphDestroy(g);
         drop_graph(m);
         throw;
       }
-      const hipError_t ec = hipStreamEndCapture(st, &m->graph_k);
-      const hipError_t ei = ec == hipSuccess ? hipGraphInstantiate(&m->gexec_k, m->graph_k, nullptr, nullptr, 0) : ec;
+      const hipError_t ec = hipStreamEndCapture(st, &gp.graph_k);
+      const hipError_t ei = ec == hipSuccess ? hipGraphInstantiate(&gp.gexec_k, gp.graph_k, nullptr, nullptr, 0) : ec;
       if (ei != hipSuccess) {  // never leave a key that claims a graph pair without the 8-step exec
         drop_graph(m);
         HIPCHK(ei);
       }
-      m->gkey = key;  // only once both graphs are instantiated
+      m->graphs.claim(slot, key);  // only once both graphs are instantiated
+      ++m->graph_captures;
     }
     int i = 0;
-    for (; i + kGraphSteps <= steps; i += kGraphSteps) HIPCHK(hipGraphLaunch(m->gexec_k, st));
-    for (; i < steps; ++i) HIPCHK(hipGraphLaunch(m->gexec, st));
+    for (; i + kGraphSteps <= steps; i += kGraphSteps) HIPCHK(hipGraphLaunch(slot->val.gexec_k, st));
+    for (; i < steps; ++i) HIPCHK(hipGraphLaunch(slot->val.gexec, st));
   });
 }
 
@@ -2776,6 +2836,58 @@ int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_s
     if (dpm != nullptr) validate_sched(dpm);
   });
   return rc != DMX_OK ? rc : sample_loop_impl(m, a, ddim, steps, use_graph, stream, dpm, known);
+}
+
+// rescale in [0, 1]; > 0 only on a CFG step of a conditional model
+static void validate_guidance(const dmx_model* m, const dmx_step_args* a, const dmx_guidance* gd) {
+  REQUIRE(m != nullptr && a != nullptr, "null argument");
+  REQUIRE(gd != nullptr, "null guidance");
+  REQUIRE(gd->rescale >= 0.f && gd->rescale <= 1.f, "guidance rescale must lie in [0, 1]");
+  if (gd->rescale > 0.f) {
+    REQUIRE(m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr,
+            "guidance rescale needs a CFG step (guidance > 0, y given, a conditional model)");
+    REQUIRE(a->n <= 65535, "rescaled steps take at most 65535 samples");
+  }
+}
+
+int dmx_step_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                    const dmx_known_sched* known, const dmx_guidance* guidance, void* stream) {
+  return guarded([&] {
+    validate_guidance(m, a, guidance);
+    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
+    if (ddim != nullptr) validate_sched(ddim);
+    if (dpm != nullptr) validate_sched(dpm);
+    validate_step(m, a, ddim, dpm, known);
+    ensure_planes(m, (hipStream_t)stream);
+    run_planned(m, (hipStream_t)stream,
+                [&](Run& R) { step_body(R, *a, nullptr, false, ddim, dpm, known, guidance); });
+  });
+}
+
+int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                           const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                           int steps, int use_graph, void* stream) {
+  const int rc = guarded([&] {
+    validate_guidance(m, a, guidance);
+    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
+    if (ddim != nullptr) validate_sched(ddim);
+    if (dpm != nullptr) validate_sched(dpm);
+  });
+  return rc != DMX_OK ? rc : sample_loop_impl(m, a, ddim, steps, use_graph, stream, dpm, known, guidance);
+}
+
+int64_t dmx_model_graph_captures(const dmx_model* m) { return m ? m->graph_captures : -1; }
+
+int dmx_cfg_rescale(const float* eu, const float* ec, float guidance, float rescale, float* eps_out,
+                    float* ratio_out, int n, int c, int h, int w, void* stream) {
+  return guarded([&] {
+    REQUIRE(eu && ec && eps_out, "null tensor");
+    REQUIRE(n >= 1 && c >= 1 && h >= 1 && w >= 1, "bad shape");
+    REQUIRE(rescale >= 0.f && rescale <= 1.f, "guidance rescale must lie in [0, 1]");
+    const int64_t total = (int64_t)c * h * w;
+    launch_cfg_rescale(eu, ec, guidance, rescale, eps_out, ratio_out, n, total, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
 }
 
 int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* recs, int cap, int* n_out,

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "source.h"
+#include "tail_math.h"
 
 namespace dmx {
 
@@ -769,21 +770,6 @@ struct StepTailParams {
   float* hist;
 };
 
-// Range guard of the split-precision modes: an operand beyond the f16 range (|v| >= 65520)
-// becomes inf in its hi plane, and any inf / NaN reaching a network output makes that output
-// non-finite.  Output kernels raise a sticky flag (a plain vector store) that the host reads
-// at its checkpoints and answers by recomputing in exact-fp32 MFMA mode.
-DMX_DEV void flag_nonfinite(int* flag, float v) {
-  if (flag != nullptr && !(fabsf(v) <= 3.402823466e38f)) *flag = 1;
-}
-
-// One IEEE rounding per reference op: the product is forced through a register
-// (opaque asm barrier) so no multiply-add pair can be contracted into an FMA,
-// whatever the -ffp-contract mode of the including code.
-DMX_DEV float rnd(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float nz) {
   const float mu = rnd(x - rnd(c1 * eps)) / c2;
   return mu + rnd(nz * sd);
@@ -886,18 +872,6 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
 // coalesced, instead of 64 rows at a 256-byte lane stride); the 1x1-conv dot products are
 // reduced over the 16 lanes with DPP (fixed order), then lanes 0..3 of the group finish
 // channel c = lane (CFG mix, posterior mean, Philox noise, store).
-DMX_DEV float group_sum16(float s) {  // sum over aligned 16-lane rows (DPP), same bits in every lane
-  auto dpp = [](float v, auto ctrl) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value,
-                                                                 0xF, 0xF, false));
-  };
-  s += dpp(s, std::integral_constant<int, 0xB1>{});   // quad_perm [1,0,3,2]
-  s += dpp(s, std::integral_constant<int, 0x4E>{});   // quad_perm [2,3,0,1]
-  s += dpp(s, std::integral_constant<int, 0x141>{});  // row_half_mirror
-  s += dpp(s, std::integral_constant<int, 0x140>{});  // row_mirror
-  return s;
-}
-
 template <bool DDIM, bool DPM = false>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;

@@ -56,5 +56,22 @@ void launch_tok_qkv_w(int C, int x1, const TokParams& tp, dim3 grid, hipStream_t
 void launch_tok_qkv(int C, int nb, int x1, const TokParams& tp, dim3 grid, hipStream_t st);
 void launch_tok_out(int C, int tm, int x1, int nw, int lds, int tpb, const TokParams& tp, int blocks,
                     hipStream_t st);
+// CFG rescale (guidance.h), k_guidance.hip.  The head's operands as the step tails take them: feat
+// [2B][HW][64] NHWC = [uncond B | cond B], w [Co][64], b [Co]; range_flag as in StepTailParams.
+struct CfgHeadParams {
+  const float* feat; const float* w; const float* b;
+  int Co, B, HW;
+  float guidance;
+  int* range_flag;
+};
+// stage 1: head + CFG mix, eg (NCHW [B][Co][HW]) and per-block moments part [B][nb][4] (doubles),
+// nb = cdiv(HW, Co == 4 ? 16 : 256) blocks per sample
+void launch_cfg_stats(const CfgHeadParams& p, float* eg, double* part, int nb, hipStream_t st);
+// stage 2: r[n] from the partials (pixb pixels per stage-1 block), eg scaled in place; ratio_out [B] or null
+void launch_cfg_scale(float* eg, const double* part, int nb, int pixb, int Co, int HW, int B, float phi,
+                      float* ratio_out, hipStream_t st);
+// standalone: one block per sample over its `total` = c*h*w elements
+void launch_cfg_rescale(const float* eu, const float* ec, float g, float phi, float* eps, float* ratio_out, int n,
+                        int64_t total, hipStream_t st);
 
 }  // namespace dmx

@@ -171,7 +171,8 @@ class ShardedCondSampler:
                cond_mask=None, decode: bool = True, dummy_input_hw=(224, 224), sampler: str = "ddpm",
                steps: Optional[int] = None, eta: float = 0.0, spacing: Optional[str] = None,
                init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-               strength: Optional[float] = None) -> Optional[torch.Tensor]:
+               strength: Optional[float] = None, guidance_interval=None,
+               guidance_rescale: float = 0.0) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -199,10 +200,20 @@ class ShardedCondSampler:
         init_latent / mask / strength as in Diffuser.sample_latent_cond, given for the global batch:
         every rank takes its rows of them as it takes its rows of the global draws, the x_T draw being
         the fixed noise e0.  The start latent and the per-step blend are shard-local (no collective),
-        and the loop walks the p0 positions the single-process sampler walks."""
+        and the loop walks the p0 positions the single-process sampler walks.
+
+        guidance_interval / guidance_rescale as in Diffuser.sample_latent_cond: every rank cuts each
+        chunk into the same unguided / guided segments (they follow from the schedule alone), and the
+        rescale's statistics are per sample, hence shard-local (no collective)."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
+        interval, phi = d._guidance_args(guidance_scale, guidance_interval, guidance_rescale, d.num_timesteps)
+        run_g = d._guided_run(d._mode_timesteps(mode), interval) if interval is not None else True
+        rkw = dict(rescale=phi) if phi > 0 else {}  # (with both keywords at their defaults every call stays as it was)
+
+        def segments(i_from, i_to):
+            return [(i_from, i_to, True)] if run_g is True else d._guidance_segments(i_from, i_to, run_g)
         ddim = mode is not None and mode[0] == "ddim"
         dpm = mode is not None and mode[0] == "dpm"
         items = d._norm_counts(class_counts)
@@ -255,8 +266,10 @@ class ShardedCondSampler:
             def run(i_from, i_to, xs):  # device Philox loop, graph-replayed, t decremented in-graph
                 if xs.shape[0] > 0:
                     t_dev.fill_(i_from)
-                    nm.sample_loop(xs, t_dev, y, null_label, v, m, float(guidance_scale), tables, i_from - i_to,
-                                   seed=seed, sample_offset=s, use_graph=d.use_graph, **skw)
+                    for a, b, guided in segments(i_from, i_to):  # the position scalar runs on across them
+                        nm.sample_loop(xs, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
+                                       tables, a - b, seed=seed, sample_offset=s, use_graph=d.use_graph, **skw,
+                                       **(rkw if guided else {}))
                 return xs
         else:
             def run(i_from, i_to, xs):
@@ -272,8 +285,9 @@ class ShardedCondSampler:
                         if xs.shape[0] > 0:  # an empty shard (B < world size) only keeps the draw order
                             out = torch.empty_like(xs)
                             tt = torch.full((xs.shape[0],), i, dtype=torch.long, device=dev)
-                            nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale), tables, noise,
-                                    **skw)
+                            guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
+                            nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
+                                    tables, noise, **skw, **(rkw if guided else {}))
                             xs = out
                 finally:
                     if pf is not None:

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimSched, DpmSched, KnownSched, StepArgs, check
+from ._lib import DdimSched, DpmSched, Guidance, KnownSched, StepArgs, check
 
 TIME_DIM = 256
 
@@ -197,6 +197,10 @@ class NativeModel:
     def workspace_bytes(self) -> int:
         return int(self.lib.dmx_model_workspace_bytes(self.handle))
 
+    def graph_captures(self) -> int:
+        """Graph pairs (1-step + 8-step) captured by sample_loop since the model was created."""
+        return int(self.lib.dmx_model_graph_captures(self.handle))
+
     # ---- U-Net ---------------------------------------------------------------------------
     def forward(self, x, t, y=None, vals=None, mask=None, want_geom=False):
         n, c, h, w = x.shape
@@ -290,7 +294,7 @@ class NativeModel:
         return sc
 
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None, hist=None, known=None):
+             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -298,9 +302,13 @@ class NativeModel:
         sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place): one
         DPM-Solver++(2M) step; `noise` must be None and `seed` is not read.
         known (z0, e0, mask, q_a, q_e) with the tables of Diffuser.known_tables for the step's schedule
-        (the DDPM step: tau = 1..T): the known-region blend follows the step on x_out (known_blend)."""
+        (the DDPM step: tau = 1..T): the known-region blend follows the step on x_out (known_blend).
+        rescale = phi in (0, 1] (a CFG step only; include/dmx.h dmx_guidance): the guided prediction is
+        scaled per sample to the conditional one's standard deviation before the update.  0 is the
+        plain step, launched exactly as without the keyword."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        gd = _guidance_struct(rescale, guidance, y)
         dpm = isinstance(sched, DpmSchedule)
         kn = _known_struct(known, x_in.device, x_in, need_mask=True) if known is not None else None
         if sched is not None:
@@ -313,7 +321,12 @@ class NativeModel:
                        sample_offset)
         with torch.cuda.device(x_in.device):
             st = ctypes.c_void_p(_stream(x_in.device))
-            if kn is not None:
+            if gd is not None:
+                check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a),
+                                               ctypes.byref(sc) if sched is not None and not dpm else None,
+                                               ctypes.byref(sc) if dpm else None,
+                                               ctypes.byref(kn) if kn is not None else None, ctypes.byref(gd), st))
+            elif kn is not None:
                 check(self.lib.dmx_step_known(self.handle, ctypes.byref(a),
                                               ctypes.byref(sc) if sched is not None and not dpm else None,
                                               ctypes.byref(sc) if dpm else None, ctypes.byref(kn), st))
@@ -344,7 +357,7 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None, hist=None, known=None):
+                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -354,8 +367,12 @@ class NativeModel:
         sched a DpmSchedule (Diffuser.dpm_tables) with hist (x's shape, updated in place):
         DPM-Solver++(2M) steps, which draw nothing (`seed` is not read).
         known (z0, e0, mask, q_a, q_e) as in step(): every step is followed by the known-region blend.
-        A loop entering below position S starts from known_blend's start latent."""
+        A loop entering below position S starts from known_blend's start latent.
+        rescale = phi in (0, 1] as in step(): every step of the loop is a rescaled CFG step.
+        The model keeps the captured graphs of the last few distinct loops (graph_captures counts the
+        captures), so alternating guided, unguided and rescaled loops replay instead of recapturing."""
         _check_state(x, "x")
+        gd = _guidance_struct(rescale, guidance, y)
         dpm = isinstance(sched, DpmSchedule)
         kn = _known_struct(known, x.device, x, need_mask=True) if known is not None else None
         if sched is not None:
@@ -376,7 +393,14 @@ class NativeModel:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if kn is not None:
+            if gd is not None:
+                check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a),
+                                                      ctypes.byref(sc) if sched is not None and not dpm else None,
+                                                      ctypes.byref(sc) if dpm else None,
+                                                      ctypes.byref(kn) if kn is not None else None,
+                                                      ctypes.byref(gd), int(steps), int(use_graph),
+                                                      ctypes.c_void_p(side.cuda_stream)))
+            elif kn is not None:
                 check(self.lib.dmx_sample_loop_known(self.handle, ctypes.byref(a),
                                                      ctypes.byref(sc) if sched is not None and not dpm else None,
                                                      ctypes.byref(sc) if dpm else None, ctypes.byref(kn), int(steps),
@@ -467,6 +491,44 @@ def _check_state(x: torch.Tensor, what: str) -> None:
     require_cuda(x, what)
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError(f"{what} must be a contiguous float32 tensor (got {x.dtype}, contiguous={x.is_contiguous()})")
+
+
+def _guidance_struct(rescale, guidance, y) -> Optional[Guidance]:
+    """The C view of a step's guidance controls: None for rescale 0 (the plain calls are made)."""
+    phi = float(rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"rescale must be in [0, 1] (got {rescale})")
+    if phi == 0.0:
+        return None
+    if y is None or not float(guidance) > 0:
+        raise ValueError("rescale applies to CFG steps: it needs y and guidance > 0")
+    return Guidance(phi)
+
+
+def cfg_rescale(eu, ec, guidance, phi):
+    """Standalone CFG mix + rescale (include/dmx.h dmx_cfg_rescale) for duck-typed models ->
+    (eps, r): eg = eu + g (ec - eu); r[n] = 1 + phi (std(ec[n]) / std(eg[n]) - 1) over the sample's
+    elements, moments in double, 1 where std(eg[n]) is not a positive finite number; eps = eg r[n].
+    eu, ec: (n,c,h,w) on the GPU, any c, h, w >= 1; phi in [0, 1] (0: eps = eg, r = 1).
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(eu, "eps_uncond")
+    phi = float(phi)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"phi must be in [0, 1] (got {phi})")
+    dev = eu.device
+    eu_c = eu.to(dtype=torch.float32).contiguous()
+    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous()
+    if eu_c.dim() != 4 or tuple(ec_c.shape) != tuple(eu_c.shape) or min(eu_c.shape) < 1:
+        raise ValueError(f"eps_uncond / eps_cond must be equal (n,c,h,w) tensors (got {tuple(eu.shape)}, "
+                         f"{tuple(ec.shape)})")
+    n, c, h, w = eu_c.shape
+    eps = torch.empty_like(eu_c)
+    r = torch.empty((n,), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(lib.dmx_cfg_rescale(_ptr(eu_c), _ptr(ec_c), float(guidance), phi, _ptr(eps), _ptr(r), n, c, h, w,
+                                  ctypes.c_void_p(_stream(dev))))
+    return eps, r
 
 
 def ddpm_update(x, eu, ec, guidance, t, tables, noise=None, seed=0, sample_offset=0):

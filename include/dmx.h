@@ -254,6 +254,50 @@ int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_s
                           const dmx_dpm_sched* dpm, const dmx_known_sched* known, int steps, int use_graph,
                           void* stream);
 
+/* ---- Guidance controls of a CFG step beyond its scale (no reference counterpart).
+ * rescale = phi in [0, 1] (Lin et al. 2023, "Common diffusion noise schedules and sample steps are
+ * flawed", §3.4): with eu / ec the unconditional / conditional predictions and
+ * eg = eu + g*(ec-eu) the guided one (one IEEE rounding per operation, as in every step), each
+ * sample n is scaled over its C*h*w elements by
+ *   r[n] = 1 + phi*(std(ec[n]) / std(eg[n]) - 1);   eps = eg * r[n]
+ * before the DDPM / DDIM / DPM update.  The moments are accumulated in double in a fixed order
+ * from the fp32 values (per-block mean and centred sum of squares, combined in block order about
+ * the sample mean), r is formed in double and rounded to fp32 once, and r[n] = 1 where std(eg[n]) is not a
+ * positive finite number.  A sample's result does not depend on the batch it sits in.  A
+ * non-finite eg raises the range flag as in the plain step.  phi = 0 is the plain step.
+ * (The guidance interval of the samplers needs no ABI: a step outside it is the plain step with
+ * guidance 0 and y given, one conditional forward.) */
+typedef struct dmx_guidance {
+  float rescale;
+} dmx_guidance;
+
+/* dmx_step* / dmx_sample_loop* with the guidance controls: at most one of ddim / dpm is non-NULL
+ * (both NULL: the DDPM step), known may be NULL (no blend), guidance must be given.  With
+ * rescale > 0 the step must be a CFG step (a->guidance > 0, a->y given, a conditional model); its
+ * single tail launch becomes three (head + CFG mix + block moments; ratio + scale; update), whose
+ * workspace is part of the model's planned arena.  With rescale == 0 both calls are exactly the
+ * plain / known-region calls and share their graphs. */
+int dmx_step_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                    const dmx_known_sched* known, const dmx_guidance* guidance, void* stream);
+int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                           const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                           int steps, int use_graph, void* stream);
+/* The CFG mix and rescale alone, for duck-typed foreign models (no model, no arena): eu, ec, eps_out
+ * (n,c,h,w) with any c, h, w >= 1; ratio_out (n,) receives r or is NULL; eps_out may alias eu or ec.
+ * One block per sample: mean, then centred squares, then the scaling, each reduction in a fixed
+ * order in double.  Feed eps_out to dmx_*_update with ec = NULL. */
+int dmx_cfg_rescale(const float* eu, const float* ec, float guidance, float rescale, float* eps_out,
+                    float* ratio_out, int n, int c, int h, int w, void* stream);
+
+/* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
+ * distinct loops (distinct dmx_step_args / schedule / known region / guidance / time-table
+ * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
+ * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
+ * after another, inside the model's one workspace; whatever reallocates or invalidates it (a
+ * larger batch, dmx_model_set_precision to another mode, dmx_model_refresh) drops every pair.
+ * Returns the number of pairs captured since the model was created (-1: NULL model). */
+int64_t dmx_model_graph_captures(const dmx_model* m);
+
 /* ---- VAE decode (replaces VAE.decode, vae.py:64-69, plus Diffuser.reverse_to_img's
  * x*255 -> clamp -> uint8, diff.py:58-62) ---------------------------------------------
  * z: (n,4,h,w); img: (n,3,8h,8w) fp32 or NULL; u8: (n,8h,8w,3) uint8 (HWC) or NULL. */

@@ -1,7 +1,7 @@
 """Few-step sampling (strided DDIM, DPM-Solver++(2M)) against the full DDPM walk on one MI355X: prints
 one JSON line.
 
-  python tools/sampler_bench.py [--rounds 5]
+  python tools/sampler_bench.py [--rounds 5] [--groups loops,known_loops,guidance_loops,end_to_end]
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -10,15 +10,22 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    reads and writes its history buffer) and the DDPM loop alternate in one process, the DDPM leg twice per
    round (legs ddpm_a, ddim, dpmpp_2m, ddpm_b), so the spread between two measurements of the SAME loop is
    known and the few-step legs are judged against it, not against a preset figure.  A model
-   holds the graphs of one loop at a time: every leg first runs 8 steps untimed (capture), then 48 steps
-   (six launches of the 8-step graph) between two device events.  Reported: the median over the rounds.
+   keeps the graphs of its last four loops: every leg first runs 8 steps untimed (a capture, or a
+   replay where its graphs are still held), then 48 steps (six launches of the 8-step graph)
+   between two device events.  Reported: the median over the rounds.
    The known-region loop (img2img / inpainting: the same DPM-Solver++(2M) loop with the known-region blend
    launched after every step) is measured likewise against the plain DPM loop, the plain leg twice per
    round (legs dpmpp_2m_a, known, dpmpp_2m_b), and judged against that leg's own spread.
+   The guidance controls likewise (legs dpmpp_2m_a, unguided, rescaled, dpmpp_2m_b): the unguided loop
+   (guidance 0 with y given: one B-sample forward per step) and the rescaled CFG loop (phi = 0.7: three
+   tail launches instead of one), with the unguided / plain ratio.
 2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
    (ddpm, T = 1000), (ddim, S = 50, eta = 0) and (dpmpp_2m, S = 20, log-SNR spacing): the first call (it captures the graphs) and the best of
    the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
-   from the steady ones by the sampler's own start-up only.
+   from the steady ones by the sampler's own start-up only.  (dpmpp_2m, S = 20) is also run with a guidance
+   interval that covers half of its positions (the middle ten), to be compared with the plain leg of
+   the same run: its loop alternates unguided / guided / unguided segments, so it shows whether their
+   graphs are reused.
 
 There is no fallback: without a GPU this fails."""
 import argparse
@@ -142,6 +149,51 @@ def known_legs(nm, d, dev, rounds):
             "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
 
 
+def guidance_legs(nm, d, dev, rounds):
+    """The DPM-Solver++(2M) loop plain (CFG), unguided (one conditional forward per step) and with the
+    rescaled tail: same schedule, buffers and method as loop_legs."""
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
+
+    def leg(kind):
+        g = 0.0 if kind == "unguided" else GUIDANCE
+        kw = dict(sched=sched, hist=hist, **(dict(rescale=0.7) if kind == "rescaled" else {}))
+        x.copy_(x0)
+        t_dev.fill_(S)
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, g, None, WARM, **kw)  # captures this loop's graphs once
+        x.copy_(x0)
+        t_dev.fill_(S)
+        torch.cuda.synchronize()
+        e_0, e_1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_0.record()
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, g, None, TIMED, **kw)
+        e_1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == S - TIMED and bool(torch.isfinite(x).all())
+        return e_0.elapsed_time(e_1) / TIMED
+
+    ms = {"dpmpp_2m_a": [], "unguided": [], "rescaled": [], "dpmpp_2m_b": []}
+    leg("plain")
+    c0 = nm.graph_captures()
+    for _ in range(rounds):
+        ms["dpmpp_2m_a"].append(leg("plain"))
+        ms["unguided"].append(leg("unguided"))
+        ms["rescaled"].append(leg("rescaled"))
+        ms["dpmpp_2m_b"].append(leg("plain"))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    plain_mean = 0.5 * (med["dpmpp_2m_a"] + med["dpmpp_2m_b"])
+    return {"ms_per_step_dpmpp_2m_a": round(med["dpmpp_2m_a"], 4),
+            "ms_per_step_dpmpp_2m_b": round(med["dpmpp_2m_b"], 4),
+            "ms_per_step_unguided": round(med["unguided"], 4), "ms_per_step_rescaled": round(med["rescaled"], 4),
+            "dpmpp_2m_spread_ms": round(abs(med["dpmpp_2m_a"] - med["dpmpp_2m_b"]), 4),
+            "unguided_over_dpmpp_2m_mean": round(med["unguided"] / plain_mean, 4),
+            "rescaled_minus_dpmpp_2m_mean_ms": round(med["rescaled"] - plain_mean, 4),
+            "graph_captures_in_rounds": nm.graph_captures() - c0,
+            "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
+
+
 def end_to_end(model, dev):
     import diff
     from dmx import synth
@@ -159,9 +211,13 @@ def end_to_end(model, dev):
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
+    tau20 = d.dpm_timesteps(20)
+    half = dict(sampler="dpmpp_2m", steps=20, guidance_interval=(tau20[5], tau20[14]))  # positions 6..15
     for name, extra, calls in (("ddim_S50_eta0", dict(sampler="ddim", steps=S, eta=0.0), 4),
-                               ("dpmpp_2m_S20", dict(sampler="dpmpp_2m", steps=20), 4), ("ddpm_T1000", {}, 2)):
+                               ("dpmpp_2m_S20", dict(sampler="dpmpp_2m", steps=20), 4),
+                               ("dpmpp_2m_S20_interval_half", half, 4), ("ddpm_T1000", {}, 2)):
         secs = []
+        c0 = model.native().graph_captures()
         for _ in range(calls):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -170,7 +226,8 @@ def end_to_end(model, dev):
             assert len(imgs) == B and imgs[0].size == (8 * HW, 8 * HW)
         out[name] = {"first_call_s": round(secs[0], 4), "first_call_images_per_s": round(B / secs[0], 2),
                      "steady_s": round(min(secs[1:]), 4), "steady_images_per_s": round(B / min(secs[1:]), 2),
-                     "calls_s": [round(v, 4) for v in secs]}
+                     "calls_s": [round(v, 4) for v in secs],
+                     "graph_captures": model.native().graph_captures() - c0}
     out["range_fallbacks"] = d.range_fallbacks
     return out
 
@@ -178,7 +235,9 @@ def end_to_end(model, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--groups", default="loops,known_loops,guidance_loops,end_to_end")
     args = ap.parse_args()
+    groups = args.groups.split(",")
     if not torch.cuda.is_available():
         raise SystemExit("sampler_bench needs an MI355X: no GPU visible, and there is no fallback")
     dev = torch.device("cuda", 0)
@@ -190,10 +249,12 @@ def main():
     model.load_state_dict(synth.unet_cond_geom_weights(0))
     model.to(dev).eval()
     res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
-           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds,
-           "loops": loop_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds),
-           "known_loops": known_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds),
-           "end_to_end": end_to_end(model, dev)}
+           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
+    for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs)):
+        if name in groups:
+            res[name] = fn(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
+    if "end_to_end" in groups:
+        res["end_to_end"] = end_to_end(model, dev)
     print(json.dumps(res))
 
 
