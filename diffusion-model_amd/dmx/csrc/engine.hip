@@ -1,5 +1,5 @@
-// dmx engine: weights, workspace planning, U-Net / VAE orchestration, hipGraph
-// step loop and the C ABI of include/dmx.h.
+// dmx engine: weights, workspace planning, U-Net / VAE orchestration and the C ABI of
+// include/dmx.h (the sampling step and its hipGraph loop: sample_engine.h).
 #include "dmx.h"
 
 #include <cmath>
@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "graph_slots.h"
+#include "step_mode.h"
 #include "igemm.h"
 #include "igemm_x3.h"
 #include "kernels.h"
@@ -245,16 +246,6 @@ struct Arena {
     // same branch (and allocates the same) in both passes; it is never dereferenced
     return reinterpret_cast<T*>(plan ? reinterpret_cast<char*>(static_cast<uintptr_t>(4096) + off) : p);
   }
-};
-
-struct GraphKey {
-  dmx_step_args a;
-  dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
-  dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
-  dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
-  dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
-  int table_gen;  // dmx_ctx::table_gen at capture
-  bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
 
 // One captured loop: the one-step graph and the same step captured kGraphSteps times back to back.
@@ -818,8 +809,8 @@ struct Run {
   void tap(const std::string& name, const float* p, size_t count);
   std::string ck_layer;
   // DMX_CKSUM: one workspace checksum per layer, taken when the next layer's first kernel begins
-  // set by run_planned's real pass only: graph captures (dmx_sample_loop, dmx_step_profile) build
-  // their own Runs and never take checksums (the device slots may not exist yet, and a captured
+  // set by run_planned's real pass only: graph captures (dmx_sample_loop) build their own Runs
+  // and never take checksums (the device slots may not exist yet, and a captured
   // atomic would replay into stale slots)
   bool cksum = false;
   void ck() {
@@ -1912,8 +1903,9 @@ static void ensure_ws(dmx_model* m) {
   }
 }
 
+// The dry run of `body`, then an arena of the size it asked for (returned), ready for the real pass.
 template <typename F>
-static void run_planned(dmx_model* m, hipStream_t st, F&& body) {
+static size_t plan_ws(dmx_model* m, hipStream_t st, F&& body) {
   m->ws.base = nullptr;
   m->ws.off = 0;
   m->ws.plan = true;
@@ -1923,10 +1915,17 @@ static void run_planned(dmx_model* m, hipStream_t st, F&& body) {
   }
   ensure_ws(m);
   const size_t planned = m->ws.off;
-  poison(m->ws_mem, m->ws.off, st);
+  poison(m->ws_mem, planned, st);
   m->ws.base = static_cast<char*>(m->ws_mem);
   m->ws.off = 0;
   m->ws.plan = false;
+  return planned;
+}
+
+// prof: event timing of every launch of the real pass (dmx_step_profile)
+template <typename F>
+static void run_planned(dmx_model* m, hipStream_t st, F&& body, Prof* prof = nullptr) {
+  const size_t planned = plan_ws(m, st, body);
   Cksum& ck = cksum_state();
   if (cksum_enabled()) {
     if (ck.dev == nullptr) HIPCHK(hipMalloc(&ck.dev, 1024 * sizeof(unsigned long long)));
@@ -1934,7 +1933,7 @@ static void run_planned(dmx_model* m, hipStream_t st, F&& body) {
     HIPCHK(hipMemsetAsync(m->ws_mem, 0xFF, planned, st));
     ck.names.clear();
   }
-  Run R{m, st, false, m->ws};
+  Run R{m, st, false, m->ws, prof};
   R.cksum = cksum_enabled();
   body(R);
   if (m->ws.off != planned) throw Error(DMX_E_INTERNAL, "workspace plan / run mismatch");
@@ -1955,210 +1954,6 @@ static void run_planned(dmx_model* m, hipStream_t st, F&& body) {
     ck.prev_names = ck.names;
     ++ck.runs;
   }
-}
-
-// The strided form of the tail: positions in [1, S], one table row per position.
-static void set_sched(StepTailParams& p, const dmx_ddim_sched& sc) {
-  p.tmax = sc.S;
-  p.t_map = sc.t_map;
-  p.k_e = sc.k_e;
-  p.k_a = sc.k_a;
-  p.k_s = sc.k_s;
-  p.k_d = sc.k_d;
-  p.k_n = sc.k_n;
-}
-
-// The DPM-Solver++(2M) form: positions as above, its own three tables and the history buffer.
-static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
-  p.tmax = dp.S;
-  p.t_map = dp.t_map;
-  p.k_e = dp.k_e;
-  p.k_a = dp.k_a;
-  p.k_x = dp.k_x;
-  p.k_c = dp.k_c;
-  p.k_p = dp.k_p;
-  p.hist = dp.hist;
-}
-
-// The blend's launch (kernels.h known_blend_kernel): float4 lanes where the rows and every pointer allow.
-static void launch_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_stride,
-                               const dmx_known_sched& kn, int n, int c, int hw, hipStream_t st) {
-  KnownBlendParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.x = x;
-  p.x_out = x_out;
-  p.z0 = kn.z0;
-  p.e0 = kn.e0;
-  p.mask = kn.mask;
-  p.q_a = kn.q_a;
-  p.q_e = kn.q_e;
-  p.pos = pos;
-  p.pos_stride = pos_stride;
-  p.S = kn.S;
-  p.HW = hw;
-  const uintptr_t bits = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)kn.z0 | (uintptr_t)kn.e0 | (uintptr_t)kn.mask;
-  if (hw % 4 == 0 && bits % 16 == 0)
-    known_blend_kernel<true><<<dim3(cdiv(hw / 4, 256), c, n), 256, 0, st>>>(p);
-  else
-    known_blend_kernel<false><<<dim3(cdiv(hw, 256), c, n), 256, 0, st>>>(p);
-}
-
-// t_next (multi-step sample-loop graphs): the step's t - 1 is stored there by the embedding kernel.
-// sc (strided sampling, include/dmx.h dmx_ddim_sched): a.t holds positions, the tail applies the
-// DDIM update from sc's tables and a.c1 / c2 / sd / T are not read.
-// dp (include/dmx.h dmx_dpm_sched; at most one of sc / dp): the same with the DPM-Solver++(2M) update.
-// kn (include/dmx.h dmx_known_sched): the known-region blend follows the tail as a launch of its own,
-// on a.x_out in place, at the position the tail read.
-// gd (include/dmx.h dmx_guidance) with rescale > 0, a CFG step: the tail becomes three launches
-// (guidance.h, through launch.h) whose eg and block partials come from the arena, in the dry run as in
-// the real one; they read the position scalar the tail reads, through step_tail_kernel.
-static void step_body(Run& R, const dmx_step_args& a, int64_t* t_next = nullptr, bool cond_cached = false,
-                      const dmx_ddim_sched* sc = nullptr, const dmx_dpm_sched* dp = nullptr,
-                      const dmx_known_sched* kn = nullptr, const dmx_guidance* gd = nullptr) {
-  dmx_model* m = R.m;
-  const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
-  const bool resc = gd != nullptr && gd->rescale > 0.f;
-  REQUIRE(!resc || cfg, "guidance rescale needs a CFG step (guidance > 0, y given, a conditional model)");
-  const int N = cfg ? 2 * a.n : a.n;
-  FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
-  in.t_next = t_next;
-  in.cond_cached = cond_cached;
-  if (sc != nullptr) {
-    in.t_map = sc->t_map;
-    in.n_pos = sc->S;
-  } else if (dp != nullptr) {
-    in.t_map = dp->t_map;
-    in.n_pos = dp->S;
-  }
-  float* feat = unet_trunk(R, in, N, a.h, a.w);
-  const int pixb = m->in_ch == 4 ? 16 : 256;  // pixels per block of the rescaled tail's first stage
-  const int nb = cdiv(a.h * a.w, pixb);
-  float* eg = resc ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
-  double* part = resc ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
-  if (R.plan) return;
-  StepTailParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.feat = feat;
-  p.w = m->out_w;
-  p.b = m->out_b;
-  p.Co = m->in_ch;
-  p.B = a.n;
-  p.HW = a.h * a.w;
-  p.cfg = cfg ? 1 : 0;
-  p.guidance = a.guidance;
-  p.x = a.x_in;
-  p.x_out = a.x_out;
-  p.t = a.t;
-  p.t_stride = a.t_stride;
-  p.noise = a.noise;
-  p.seed = a.seed;
-  p.sample_offset = a.sample_offset;
-  p.range_flag = m->range_flag;
-  const bool ddim = sc != nullptr, dpm = dp != nullptr;
-  if (dpm) {
-    set_sched(p, *dp);
-  } else if (ddim) {
-    set_sched(p, *sc);
-  } else {
-    p.tmax = a.T;
-    p.c1 = a.c1;
-    p.c2 = a.c2;
-    p.sd = a.sd;
-  }
-  R.layer = dpm ? "out+cfg+dpm" : ddim ? "out+cfg+ddim" : "out+cfg+ddpm";
-  if (resc) {
-    const double el = (double)a.n * p.Co * p.HW;
-    R.begin(p.Co == 4 ? "cfg_stats4_kernel" : "cfg_stats_kernel", 2.0 * N * p.HW * 64.0 * p.Co,
-            4.0 * ((double)N * p.HW * 64 + el));
-    CfgHeadParams hp{p.feat, p.w, p.b, p.Co, p.B, p.HW, p.guidance, p.range_flag};
-    launch_cfg_stats(hp, eg, part, nb, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    R.begin("cfg_scale_kernel", el, 8.0 * el);
-    launch_cfg_scale(eg, part, nb, pixb, p.Co, p.HW, a.n, gd->rescale, nullptr, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-    // the update on the scaled eg: the tail's precomputed-eps form (it raises the range flag on it)
-    p.feat = nullptr;
-    p.cfg = 0;
-    p.eps_u = eg;
-    dim3 grid(cdiv(p.HW, 256), a.n);
-    R.begin("step_tail_kernel", 8.0 * el, 4.0 * 4.0 * el);
-    if (dpm) step_tail_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
-    else if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
-    else step_tail_kernel<false><<<grid, 256, 0, R.st>>>(p);
-  } else if (p.Co == 4 && p.feat != nullptr) {
-    dim3 grid(cdiv(p.HW, 16), a.n);
-    R.begin("step_tail4_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    if (dpm) step_tail4_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
-    else if (ddim) step_tail4_kernel<true><<<grid, 256, 0, R.st>>>(p);
-    else step_tail4_kernel<false><<<grid, 256, 0, R.st>>>(p);
-  } else {
-    dim3 grid(cdiv(p.HW, 256), a.n);
-    R.begin("step_tail_kernel", 2.0 * N * p.HW * 64.0 * p.Co, 4.0 * ((double)N * p.HW * 64 + 3.0 * a.n * p.HW * p.Co));
-    if (dpm) step_tail_kernel<false, true><<<grid, 256, 0, R.st>>>(p);
-    else if (ddim) step_tail_kernel<true><<<grid, 256, 0, R.st>>>(p);
-    else step_tail_kernel<false><<<grid, 256, 0, R.st>>>(p);
-  }
-  R.end();
-  HIPCHK(hipGetLastError());
-  if (kn != nullptr) {
-    R.layer = "known_blend";
-    R.begin("known_blend_kernel", 5.0 * a.n * p.Co * p.HW, 4.0 * (4.0 * p.Co + 1.0) * a.n * p.HW);
-    launch_known_blend(a.x_out, a.x_out, a.t, a.t_stride, *kn, a.n, p.Co, p.HW, R.st);
-    R.end();
-    HIPCHK(hipGetLastError());
-  }
-}
-
-static void validate_sched(const dmx_ddim_sched* sc) {
-  REQUIRE(sc != nullptr, "null schedule");
-  REQUIRE(sc->S >= 1, "schedule needs S >= 1 positions");
-  REQUIRE(sc->t_map && sc->k_e && sc->k_a && sc->k_s && sc->k_d && sc->k_n, "null table in schedule");
-}
-
-static void validate_sched(const dmx_dpm_sched* dp) {
-  REQUIRE(dp != nullptr, "null schedule");
-  REQUIRE(dp->S >= 1, "schedule needs S >= 1 positions");
-  REQUIRE(dp->t_map && dp->k_e && dp->k_a && dp->k_x && dp->k_c && dp->k_p, "null table in schedule");
-  REQUIRE(dp->hist != nullptr, "DPM schedule needs a history buffer");
-}
-
-static void validate_known(const dmx_known_sched* kn, const float* x_out) {
-  REQUIRE(kn != nullptr, "null known-region schedule");
-  REQUIRE(kn->S >= 1, "known-region schedule needs S >= 1 positions");
-  REQUIRE(kn->z0 && kn->e0 && kn->q_a && kn->q_e, "null tensor in known-region schedule");
-  REQUIRE(kn->z0 != x_out && kn->e0 != x_out && kn->mask != x_out, "z0 / e0 / mask must not alias x_out");
-}
-
-// sc / dp != null: the strided calls (a->c1 / c2 / sd / T are ignored there)
-// kn != null: the known-region calls, whose tables must cover the positions of the step's schedule
-static void validate_step(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc = nullptr,
-                          const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr) {
-  REQUIRE(a != nullptr, "null step args");
-  if (kn != nullptr) {
-    REQUIRE(sc == nullptr || dp == nullptr, "at most one of the DDIM and DPM schedules");
-    validate_known(kn, a->x_out);
-    REQUIRE(kn->mask != nullptr, "a known-region step needs a mask");
-    REQUIRE(a->n <= 65535, "known-region steps take at most 65535 samples");
-    REQUIRE(kn->S == (dp != nullptr ? dp->S : sc != nullptr ? sc->S : a->T), "known-region S differs from the schedule's");
-  }
-  check_shapes(m, a->n, a->h, a->w);
-  REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
-  if (dp != nullptr) {
-    validate_sched(dp);
-    REQUIRE(a->noise == nullptr, "the DPM solver takes no noise (noise must be NULL)");
-    REQUIRE(dp->hist != a->x_in && dp->hist != a->x_out, "hist must not alias x");
-  } else if (sc != nullptr) {
-    validate_sched(sc);
-  } else {
-    REQUIRE(a->c1 && a->c2 && a->sd, "null tensor in step args");
-    REQUIRE(a->T >= 1, "T must be >= 1");
-  }
-  REQUIRE(m->in_ch <= 4, "in_ch must be <= 4");
-  if (m->kind != DMX_UNET && a->guidance > 0.f) REQUIRE(a->y != nullptr, "CFG needs y");
-  if (m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND)
-    REQUIRE((a->vals == nullptr) == (a->mask == nullptr), "vals and mask must be given together");
 }
 
 // VAE decoder (models/vae.py:35-49,64-69) on one chunk of n latents:
@@ -2256,6 +2051,7 @@ static void vae_enc_body(Run& R, const float* x, const float* eps, float* z, flo
 
 }  // namespace dmx
 
+#include "sample_engine.h"
 #include "train_engine.h"
 #include "vae_train_engine.h"
 
@@ -2618,262 +2414,78 @@ int dmx_unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64
   });
 }
 
+// The step and loop entries: each fills a StepMode (step_mode.h) for sample_step / sample_loop
+// (sample_engine.h); the part an entry is named after must be given.
 int dmx_step(dmx_model* m, const dmx_step_args* a, void* stream) {
-  return guarded([&] {
-    REQUIRE(m != nullptr, "null model");
-    validate_step(m, a);
-    ensure_planes(m, (hipStream_t)stream);
-    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a); });
-  });
+  return guarded([&] { sample_step(m, a, StepMode{}, (hipStream_t)stream); });
 }
 
 int dmx_step_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, void* stream) {
   return guarded([&] {
-    REQUIRE(m != nullptr, "null model");
-    validate_sched(sched);
-    validate_step(m, a, sched);
-    ensure_planes(m, (hipStream_t)stream);
-    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, sched); });
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_step(m, a, StepMode{sched}, (hipStream_t)stream);
   });
 }
 
 int dmx_step_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, void* stream) {
   return guarded([&] {
-    REQUIRE(m != nullptr, "null model");
-    validate_sched(sched);
-    validate_step(m, a, nullptr, sched);
-    ensure_planes(m, (hipStream_t)stream);
-    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, nullptr, sched); });
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_step(m, a, StepMode{nullptr, sched}, (hipStream_t)stream);
   });
 }
 
 int dmx_step_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
                    const dmx_known_sched* known, void* stream) {
   return guarded([&] {
-    REQUIRE(m != nullptr, "null model");
     REQUIRE(known != nullptr, "null known-region schedule");
-    validate_step(m, a, ddim, dpm, known);
-    ensure_planes(m, (hipStream_t)stream);
-    run_planned(m, (hipStream_t)stream, [&](Run& R) { step_body(R, *a, nullptr, false, ddim, dpm, known); });
+    sample_step(m, a, StepMode{ddim, dpm, known}, (hipStream_t)stream);
   });
-}
-
-static constexpr int kGraphSteps = 8;
-
-// dmx_sample_loop (sc == null) and dmx_sample_loop_ddim: the scalar a->t counts down by one per
-// step either way — timesteps in the first, positions of the schedule in the second.
-// dmx_sample_loop_dpm (dp != null, sc == null): positions again; the history buffer is updated in
-// place by every step, so it needs no ping-pong inside the multi-step graph.
-// kn != null (dmx_sample_loop_known): every step is followed by the known-region blend, which reads
-// the position scalar its tail read — the multi-step graph's ping-pong needs nothing more.
-// gd != null with rescale > 0 (dmx_sample_loop_guided): every step is a rescaled CFG step; phi enters
-// the graph key.  rescale == 0 leaves key and launches exactly those of the plain loop.
-static int sample_loop_impl(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sc, int steps, int use_graph,
-                            void* stream, const dmx_dpm_sched* dp = nullptr, const dmx_known_sched* kn = nullptr,
-                            const dmx_guidance* gd = nullptr) {
-  return guarded([&] {
-    REQUIRE(m != nullptr, "null model");
-    validate_step(m, a, sc, dp, kn);
-    if (gd != nullptr && !(gd->rescale > 0.f)) gd = nullptr;
-    REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
-    REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
-    REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
-    REQUIRE(steps >= 0, "steps must be >= 0");
-    hipStream_t st = (hipStream_t)stream;
-    ensure_planes(m, st);
-    int64_t* tdev = const_cast<int64_t*>(a->t);
-    if (!use_graph) {
-      for (int i = 0; i < steps; ++i) {
-        run_planned(m, st, [&](Run& R) { step_body(R, *a, nullptr, false, sc, dp, kn, gd); });
-        decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
-        HIPCHK(hipGetLastError());
-      }
-      return;
-    }
-    GraphKey key;
-    std::memset(&key, 0, sizeof(key));
-    std::memcpy(&key.a, a, sizeof(dmx_step_args));
-    if (sc != nullptr) {
-      // the strided graphs read the schedule instead of c1 / c2 / sd / T: those leave the key, the
-      // schedule (member by member: the key is compared bytewise, padding must stay zero) enters
-      // it, and S >= 1 keeps every strided key apart from the DDPM keys (sched all zero)
-      key.a.c1 = key.a.c2 = key.a.sd = nullptr;
-      key.a.T = 0;
-      key.sched.t_map = sc->t_map;
-      key.sched.k_e = sc->k_e;
-      key.sched.k_a = sc->k_a;
-      key.sched.k_s = sc->k_s;
-      key.sched.k_d = sc->k_d;
-      key.sched.k_n = sc->k_n;
-      key.sched.S = sc->S;
-    } else if (dp != nullptr) {
-      // likewise for the DPM graphs, which also read and write the history buffer; S >= 1 keeps
-      // their keys apart from the DDPM and DDIM keys (dpm all zero)
-      key.a.c1 = key.a.c2 = key.a.sd = nullptr;
-      key.a.T = 0;
-      key.a.seed = 0;  // (not read: the solver draws nothing)
-      key.dpm.t_map = dp->t_map;
-      key.dpm.k_e = dp->k_e;
-      key.dpm.k_a = dp->k_a;
-      key.dpm.k_x = dp->k_x;
-      key.dpm.k_c = dp->k_c;
-      key.dpm.k_p = dp->k_p;
-      key.dpm.hist = dp->hist;
-      key.dpm.S = dp->S;
-    }
-    if (kn != nullptr) {
-      // the known-region graphs also hold the blend's launches: its operands enter the key member by
-      // member, and S >= 1 keeps them apart from every plain key (known all zero)
-      key.known.z0 = kn->z0;
-      key.known.e0 = kn->e0;
-      key.known.mask = kn->mask;
-      key.known.q_a = kn->q_a;
-      key.known.q_e = kn->q_e;
-      key.known.S = kn->S;
-    }
-    if (gd != nullptr) key.gd.rescale = gd->rescale;  // (all zero on every other path)
-    key.table_gen = m->ctx->table_gen;
-    GraphSlot* slot = m->graphs.find(key);
-    if (slot == nullptr) {
-      // plan + allocate outside capture, then capture the real launches
-      m->ws.base = nullptr;
-      m->ws.off = 0;
-      m->ws.plan = true;
-      {
-        Run P{m, st, true, m->ws};
-        step_body(P, *a, nullptr, false, sc, dp, kn, gd);
-      }
-      ensure_ws(m);  // (a grown arena drops every slot: their graphs point into the old one)
-      slot = m->graphs.victim();
-      drop_slot(m, slot);  // a free slot, or the least recently used pair makes room
-      GraphPair& gp = slot->val;
-      poison(m->ws_mem, m->ws.off, st);
-      m->ws.base = static_cast<char*>(m->ws_mem);
-      m->ws.off = 0;
-      m->ws.plan = false;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      try {
-        Run R{m, st, false, m->ws};
-        step_body(R, *a, nullptr, false, sc, dp, kn, gd);
-        decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
-      } catch (...) {
-        hipGraph_t g = nullptr;
-        (void)hipStreamEndCapture(st, &g);
-        if (g) (void)hipGraphDestroy(g);
-        drop_graph(m);
-        throw;
-      }
-      // the slot owns each handle from the moment it is stored; it is not `used` (no key can find
-      // it) until both graphs are instantiated, and any failure on the way drops every slot
-      const hipError_t e1 = hipStreamEndCapture(st, &gp.graph);
-      const hipError_t i1 = e1 == hipSuccess ? hipGraphInstantiate(&gp.gexec, gp.graph, nullptr, nullptr, 0) : e1;
-      if (i1 != hipSuccess) {
-        drop_graph(m);
-        HIPCHK(i1);
-      }
-      // kGraphSteps consecutive steps in one graph: the gap between two graph launches (≈9 µs of
-      // idle GPU per step in the replay trace) is paid once per kGraphSteps steps.  Inside it, t
-      // alternates between the caller's scalar and a scratch scalar: step k reads one and its
-      // embedding kernel stores t - 1 in the other (no one-thread decrement launch per step; an even
-      // kGraphSteps ends in the caller's scalar).  The noise is keyed by (seed, t, sample), so the
-      // captured steps compute what kGraphSteps replays of the one-step graph compute.
-      static_assert(kGraphSteps % 2 == 0, "t ping-pong must end in the caller's buffer");
-      int64_t* tscr = m->t_scratch;
-      HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      try {
-        for (int k = 0; k < kGraphSteps; ++k) {
-          m->ws.off = 0;
-          Run R{m, st, false, m->ws};
-          dmx_step_args ak = *a;
-          ak.t = (k & 1) ? tscr : tdev;
-          step_body(R, ak, (k & 1) ? tdev : tscr, k > 0, sc, dp, kn, gd);  // cond MLP rows from step 0 of the graph
-        }
-      } catch (...) {
-        hipGraph_t g = nullptr;
-        (void)hipStreamEndCapture(st, &g);
-        if (g) (void)hipGraphDestroy(g);
-        drop_graph(m);
-        throw;
-      }
-      const hipError_t ec = hipStreamEndCapture(st, &gp.graph_k);
-      const hipError_t ei = ec == hipSuccess ? hipGraphInstantiate(&gp.gexec_k, gp.graph_k, nullptr, nullptr, 0) : ec;
-      if (ei != hipSuccess) {  // never leave a key that claims a graph pair without the 8-step exec
-        drop_graph(m);
-        HIPCHK(ei);
-      }
-      m->graphs.claim(slot, key);  // only once both graphs are instantiated
-      ++m->graph_captures;
-    }
-    int i = 0;
-    for (; i + kGraphSteps <= steps; i += kGraphSteps) HIPCHK(hipGraphLaunch(slot->val.gexec_k, st));
-    for (; i < steps; ++i) HIPCHK(hipGraphLaunch(slot->val.gexec, st));
-  });
-}
-
-int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
-  return sample_loop_impl(m, a, nullptr, steps, use_graph, stream);
-}
-
-int dmx_sample_loop_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, int steps,
-                         int use_graph, void* stream) {
-  const int rc = guarded([&] { validate_sched(sched); });
-  return rc != DMX_OK ? rc : sample_loop_impl(m, a, sched, steps, use_graph, stream);
-}
-
-int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, int steps,
-                        int use_graph, void* stream) {
-  const int rc = guarded([&] { validate_sched(sched); });
-  return rc != DMX_OK ? rc : sample_loop_impl(m, a, nullptr, steps, use_graph, stream, sched);
-}
-
-int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
-                          const dmx_dpm_sched* dpm, const dmx_known_sched* known, int steps, int use_graph,
-                          void* stream) {
-  const int rc = guarded([&] {
-    REQUIRE(known != nullptr, "null known-region schedule");
-    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
-    if (ddim != nullptr) validate_sched(ddim);
-    if (dpm != nullptr) validate_sched(dpm);
-  });
-  return rc != DMX_OK ? rc : sample_loop_impl(m, a, ddim, steps, use_graph, stream, dpm, known);
-}
-
-// rescale in [0, 1]; > 0 only on a CFG step of a conditional model
-static void validate_guidance(const dmx_model* m, const dmx_step_args* a, const dmx_guidance* gd) {
-  REQUIRE(m != nullptr && a != nullptr, "null argument");
-  REQUIRE(gd != nullptr, "null guidance");
-  REQUIRE(gd->rescale >= 0.f && gd->rescale <= 1.f, "guidance rescale must lie in [0, 1]");
-  if (gd->rescale > 0.f) {
-    REQUIRE(m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr,
-            "guidance rescale needs a CFG step (guidance > 0, y given, a conditional model)");
-    REQUIRE(a->n <= 65535, "rescaled steps take at most 65535 samples");
-  }
 }
 
 int dmx_step_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
                     const dmx_known_sched* known, const dmx_guidance* guidance, void* stream) {
   return guarded([&] {
-    validate_guidance(m, a, guidance);
-    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
-    if (ddim != nullptr) validate_sched(ddim);
-    if (dpm != nullptr) validate_sched(dpm);
-    validate_step(m, a, ddim, dpm, known);
-    ensure_planes(m, (hipStream_t)stream);
-    run_planned(m, (hipStream_t)stream,
-                [&](Run& R) { step_body(R, *a, nullptr, false, ddim, dpm, known, guidance); });
+    REQUIRE(guidance != nullptr, "null guidance");
+    sample_step(m, a, StepMode{ddim, dpm, known, guidance}, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
+  return guarded([&] { sample_loop(m, a, StepMode{}, steps, use_graph, (hipStream_t)stream); });
+}
+
+int dmx_sample_loop_ddim(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* sched, int steps,
+                         int use_graph, void* stream) {
+  return guarded([&] {
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_loop(m, a, StepMode{sched}, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sched, int steps,
+                        int use_graph, void* stream) {
+  return guarded([&] {
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_loop(m, a, StepMode{nullptr, sched}, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                          const dmx_dpm_sched* dpm, const dmx_known_sched* known, int steps, int use_graph,
+                          void* stream) {
+  return guarded([&] {
+    REQUIRE(known != nullptr, "null known-region schedule");
+    sample_loop(m, a, StepMode{ddim, dpm, known}, steps, use_graph, (hipStream_t)stream);
   });
 }
 
 int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
                            const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
                            int steps, int use_graph, void* stream) {
-  const int rc = guarded([&] {
-    validate_guidance(m, a, guidance);
-    REQUIRE(ddim == nullptr || dpm == nullptr, "at most one of the DDIM and DPM schedules");
-    if (ddim != nullptr) validate_sched(ddim);
-    if (dpm != nullptr) validate_sched(dpm);
+  return guarded([&] {
+    REQUIRE(guidance != nullptr, "null guidance");
+    sample_loop(m, a, StepMode{ddim, dpm, known, guidance}, steps, use_graph, (hipStream_t)stream);
   });
-  return rc != DMX_OK ? rc : sample_loop_impl(m, a, ddim, steps, use_graph, stream, dpm, known, guidance);
 }
 
 int64_t dmx_model_graph_captures(const dmx_model* m) { return m ? m->graph_captures : -1; }
@@ -2894,23 +2506,11 @@ int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* re
                      void* stream) {
   return guarded([&] {
     REQUIRE(m != nullptr && recs != nullptr && n_out != nullptr, "null argument");
-    validate_step(m, a);
+    validate(m, a, StepMode{}, false);
     hipStream_t st = (hipStream_t)stream;
     ensure_planes(m, st);
     Prof prof;
-    m->ws.base = nullptr;
-    m->ws.off = 0;
-    m->ws.plan = true;
-    {
-      Run P{m, st, true, m->ws};
-      step_body(P, *a);
-    }
-    ensure_ws(m);
-    m->ws.base = static_cast<char*>(m->ws_mem);
-    m->ws.off = 0;
-    m->ws.plan = false;
-    Run R{m, st, false, m->ws, &prof};
-    step_body(R, *a);
+    run_planned(m, st, [&](Run& R) { step_body(R, *a, StepMode{}); }, &prof);
     HIPCHK(hipStreamSynchronize(st));
     int n = 0;
     for (auto& r : prof.recs) {
@@ -2934,21 +2534,9 @@ int dmx_ddpm_update(const float* x, float* x_out, const float* eu, const float* 
                     const float* noise, uint64_t seed, int64_t sample_offset, int n, int c, int h, int w,
                     void* stream) {
   return guarded([&] {
-    REQUIRE(x && x_out && eu && t && c1 && c2 && sd, "null tensor");
-    REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1 && T >= 1, "bad shape");
-    StepTailParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.Co = c;
-    p.B = n;
-    p.HW = h * w;
-    p.cfg = ec != nullptr ? 1 : 0;
-    p.guidance = guidance;
-    p.eps_u = eu;
-    p.eps_c = ec;
-    p.x = x;
-    p.x_out = x_out;
-    p.t = t;
-    p.t_stride = t_stride;
+    REQUIRE(c1 && c2 && sd, "null tensor");
+    REQUIRE(T >= 1, "bad shape");
+    StepTailParams p = update_params(x, x_out, eu, ec, guidance, t, t_stride, n, c, h, w);
     p.tmax = T;
     p.c1 = c1;
     p.c2 = c2;
@@ -2956,9 +2544,7 @@ int dmx_ddpm_update(const float* x, float* x_out, const float* eu, const float* 
     p.noise = noise;
     p.seed = seed;
     p.sample_offset = sample_offset;
-    dim3 grid(cdiv(p.HW, 256), n);
-    step_tail_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    HIPCHK(hipGetLastError());
+    launch_update(p, Rule::DDPM, (hipStream_t)stream);
   });
 }
 
@@ -2966,29 +2552,13 @@ int dmx_ddim_update(const float* x, float* x_out, const float* eu, const float* 
                     const int64_t* pos, int pos_stride, const dmx_ddim_sched* sched, const float* noise,
                     uint64_t seed, int64_t sample_offset, int n, int c, int h, int w, void* stream) {
   return guarded([&] {
-    REQUIRE(x && x_out && eu && pos, "null tensor");
-    validate_sched(sched);
-    REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1, "bad shape");
-    StepTailParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.Co = c;
-    p.B = n;
-    p.HW = h * w;
-    p.cfg = ec != nullptr ? 1 : 0;
-    p.guidance = guidance;
-    p.eps_u = eu;
-    p.eps_c = ec;
-    p.x = x;
-    p.x_out = x_out;
-    p.t = pos;
-    p.t_stride = pos_stride;
+    check_sched(sched);
+    StepTailParams p = update_params(x, x_out, eu, ec, guidance, pos, pos_stride, n, c, h, w);
     set_sched(p, *sched);
     p.noise = noise;
     p.seed = seed;
     p.sample_offset = sample_offset;
-    dim3 grid(cdiv(p.HW, 256), n);
-    step_tail_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    HIPCHK(hipGetLastError());
+    launch_update(p, Rule::DDIM, (hipStream_t)stream);
   });
 }
 
@@ -2996,27 +2566,11 @@ int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* e
                    const int64_t* pos, int pos_stride, const dmx_dpm_sched* sched, int n, int c, int h, int w,
                    void* stream) {
   return guarded([&] {
-    REQUIRE(x && x_out && eu && pos, "null tensor");
-    validate_sched(sched);
+    check_sched(sched);
     REQUIRE(sched->hist != x && sched->hist != x_out, "hist must not alias x");
-    REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1, "bad shape");
-    StepTailParams p;
-    std::memset(&p, 0, sizeof(p));
-    p.Co = c;
-    p.B = n;
-    p.HW = h * w;
-    p.cfg = ec != nullptr ? 1 : 0;
-    p.guidance = guidance;
-    p.eps_u = eu;
-    p.eps_c = ec;
-    p.x = x;
-    p.x_out = x_out;
-    p.t = pos;
-    p.t_stride = pos_stride;
+    StepTailParams p = update_params(x, x_out, eu, ec, guidance, pos, pos_stride, n, c, h, w);
     set_sched(p, *sched);
-    dim3 grid(cdiv(p.HW, 256), n);
-    step_tail_kernel<false, true><<<grid, 256, 0, (hipStream_t)stream>>>(p);
-    HIPCHK(hipGetLastError());
+    launch_update(p, Rule::DPM, (hipStream_t)stream);
   });
 }
 
@@ -3024,7 +2578,7 @@ int dmx_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_st
                     const dmx_known_sched* known, int n, int c, int h, int w, void* stream) {
   return guarded([&] {
     REQUIRE(x_out && pos, "null tensor");
-    validate_known(known, x_out);
+    check_known(known, x_out);
     REQUIRE(x != nullptr || known->mask == nullptr, "x may be NULL only without a mask");
     REQUIRE(n >= 1 && n <= 65535 && c >= 1 && c <= 65535 && h >= 1 && w >= 1, "bad shape");
     launch_known_blend(x, x_out, pos, pos_stride, *known, n, c, h * w, (hipStream_t)stream);

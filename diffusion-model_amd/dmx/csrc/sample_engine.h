@@ -1,0 +1,352 @@
+// dmx — sampling on the host side: one denoising step (U-Net trunk + the tail's update, in every
+// mode of step_mode.h), its argument rules, the eager / hipGraph sample loop, and the launches of
+// the standalone updates and the known-region blend.  The C ABI entries in engine.hip fill a
+// StepMode and call sample_step / sample_loop.
+//
+// Included by engine.hip after the inference engine (same translation unit).
+#pragma once
+
+namespace dmx {
+
+// The blend's launch (kernels.h known_blend_kernel): float4 lanes where the rows and every pointer allow.
+static void launch_known_blend(const float* x, float* x_out, const int64_t* pos, int pos_stride,
+                               const dmx_known_sched& kn, int n, int c, int hw, hipStream_t st) {
+  KnownBlendParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.x = x;
+  p.x_out = x_out;
+  p.z0 = kn.z0;
+  p.e0 = kn.e0;
+  p.mask = kn.mask;
+  p.q_a = kn.q_a;
+  p.q_e = kn.q_e;
+  p.pos = pos;
+  p.pos_stride = pos_stride;
+  p.S = kn.S;
+  p.HW = hw;
+  const uintptr_t bits = (uintptr_t)x | (uintptr_t)x_out | (uintptr_t)kn.z0 | (uintptr_t)kn.e0 | (uintptr_t)kn.mask;
+  if (hw % 4 == 0 && bits % 16 == 0)
+    known_blend_kernel<true><<<dim3(cdiv(hw / 4, 256), c, n), 256, 0, st>>>(p);
+  else
+    known_blend_kernel<false><<<dim3(cdiv(hw, 256), c, n), 256, 0, st>>>(p);
+}
+
+// The strided form of the tail: positions in [1, S], one table row per position.
+static void set_sched(StepTailParams& p, const dmx_ddim_sched& sc) {
+  p.tmax = sc.S;
+  p.t_map = sc.t_map;
+  p.k_e = sc.k_e;
+  p.k_a = sc.k_a;
+  p.k_s = sc.k_s;
+  p.k_d = sc.k_d;
+  p.k_n = sc.k_n;
+}
+
+// The DPM-Solver++(2M) form: positions as above, its own three tables and the history buffer.
+static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
+  p.tmax = dp.S;
+  p.t_map = dp.t_map;
+  p.k_e = dp.k_e;
+  p.k_a = dp.k_a;
+  p.k_x = dp.k_x;
+  p.k_c = dp.k_c;
+  p.k_p = dp.k_p;
+  p.hist = dp.hist;
+}
+
+// The tail's launch: the instance of the update rule; head4 = the network head path with Co = 4
+// (16 pixels per block), else one pixel per thread.
+static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st) {
+  if (!head4) {
+    if (rule == Rule::DPM) step_tail_kernel<false, true><<<grid, 256, 0, st>>>(p);
+    else if (rule == Rule::DDIM) step_tail_kernel<true><<<grid, 256, 0, st>>>(p);
+    else step_tail_kernel<false><<<grid, 256, 0, st>>>(p);
+  } else {
+    if (rule == Rule::DPM) step_tail4_kernel<false, true><<<grid, 256, 0, st>>>(p);
+    else if (rule == Rule::DDIM) step_tail4_kernel<true><<<grid, 256, 0, st>>>(p);
+    else step_tail4_kernel<false><<<grid, 256, 0, st>>>(p);
+  }
+}
+
+// A step's place in a multi-step sample-loop graph: t_next is where the embedding kernel stores the
+// step's t - 1; cond_cached = the conditioning MLP rows of the graph's first step are still valid.
+struct GraphStep {
+  int64_t* t_next = nullptr;
+  bool cond_cached = false;
+};
+
+// One step, validated by validate().  With mode.rescale() > 0 the tail becomes three launches
+// (guidance.h, through launch.h) whose eg and block partials come from the arena, in the dry run as
+// in the real one; they read the position scalar the tail reads, through step_tail_kernel.  The
+// known-region blend follows the tail as a launch of its own, on a.x_out in place, at the position
+// the tail read.
+static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, GraphStep gs = {}) {
+  dmx_model* m = R.m;
+  const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
+  const bool resc = mode.rescale() > 0.f;
+  const Rule rule = mode.rule();
+  const int N = cfg ? 2 * a.n : a.n;
+  FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
+  in.t_next = gs.t_next;
+  in.cond_cached = gs.cond_cached;
+  if (rule != Rule::DDPM) {
+    in.t_map = mode.t_map();
+    in.n_pos = mode.positions(a);
+  }
+  float* feat = unet_trunk(R, in, N, a.h, a.w);
+  const int pixb = m->in_ch == 4 ? 16 : 256;  // pixels per block of the rescaled tail's first stage
+  const int nb = cdiv(a.h * a.w, pixb);
+  float* eg = resc ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
+  double* part = resc ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
+  if (R.plan) return;
+  StepTailParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.feat = feat;
+  p.w = m->out_w;
+  p.b = m->out_b;
+  p.Co = m->in_ch;
+  p.B = a.n;
+  p.HW = a.h * a.w;
+  p.cfg = cfg ? 1 : 0;
+  p.guidance = a.guidance;
+  p.x = a.x_in;
+  p.x_out = a.x_out;
+  p.t = a.t;
+  p.t_stride = a.t_stride;
+  p.noise = a.noise;
+  p.seed = a.seed;
+  p.sample_offset = a.sample_offset;
+  p.range_flag = m->range_flag;
+  if (rule == Rule::DPM) {
+    set_sched(p, *mode.dpm);
+  } else if (rule == Rule::DDIM) {
+    set_sched(p, *mode.ddim);
+  } else {
+    p.tmax = a.T;
+    p.c1 = a.c1;
+    p.c2 = a.c2;
+    p.sd = a.sd;
+  }
+  R.layer = rule == Rule::DPM ? "out+cfg+dpm" : rule == Rule::DDIM ? "out+cfg+ddim" : "out+cfg+ddpm";
+  const double el = (double)a.n * p.Co * p.HW;
+  const double head_flops = 2.0 * N * p.HW * 64.0 * p.Co, head_bytes = 4.0 * ((double)N * p.HW * 64 + 3.0 * el);
+  if (resc) {
+    R.begin(p.Co == 4 ? "cfg_stats4_kernel" : "cfg_stats_kernel", head_flops, 4.0 * ((double)N * p.HW * 64 + el));
+    CfgHeadParams hp{p.feat, p.w, p.b, p.Co, p.B, p.HW, p.guidance, p.range_flag};
+    launch_cfg_stats(hp, eg, part, nb, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+    R.begin("cfg_scale_kernel", el, 8.0 * el);
+    launch_cfg_scale(eg, part, nb, pixb, p.Co, p.HW, a.n, mode.rescale(), nullptr, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+    // the update on the scaled eg: the tail's precomputed-eps form (it raises the range flag on it)
+    p.feat = nullptr;
+    p.cfg = 0;
+    p.eps_u = eg;
+    R.begin("step_tail_kernel", 8.0 * el, 4.0 * 4.0 * el);
+    launch_step_tail(p, rule, false, dim3(cdiv(p.HW, 256), a.n), R.st);
+  } else if (p.Co == 4 && p.feat != nullptr) {
+    R.begin("step_tail4_kernel", head_flops, head_bytes);
+    launch_step_tail(p, rule, true, dim3(cdiv(p.HW, 16), a.n), R.st);
+  } else {
+    R.begin("step_tail_kernel", head_flops, head_bytes);
+    launch_step_tail(p, rule, false, dim3(cdiv(p.HW, 256), a.n), R.st);
+  }
+  R.end();
+  HIPCHK(hipGetLastError());
+  if (mode.known != nullptr) {
+    R.layer = "known_blend";
+    R.begin("known_blend_kernel", 5.0 * a.n * p.Co * p.HW, 4.0 * (4.0 * p.Co + 1.0) * a.n * p.HW);
+    launch_known_blend(a.x_out, a.x_out, a.t, a.t_stride, *mode.known, a.n, p.Co, p.HW, R.st);
+    R.end();
+    HIPCHK(hipGetLastError());
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Argument rules
+// ---------------------------------------------------------------------------
+static void check_sched(const dmx_ddim_sched* sc) {
+  REQUIRE(sc != nullptr, "null schedule");
+  REQUIRE(sc->S >= 1, "schedule needs S >= 1 positions");
+  REQUIRE(sc->t_map && sc->k_e && sc->k_a && sc->k_s && sc->k_d && sc->k_n, "null table in schedule");
+}
+
+static void check_sched(const dmx_dpm_sched* dp) {
+  REQUIRE(dp != nullptr, "null schedule");
+  REQUIRE(dp->S >= 1, "schedule needs S >= 1 positions");
+  REQUIRE(dp->t_map && dp->k_e && dp->k_a && dp->k_x && dp->k_c && dp->k_p, "null table in schedule");
+  REQUIRE(dp->hist != nullptr, "DPM schedule needs a history buffer");
+}
+
+static void check_known(const dmx_known_sched* kn, const float* x_out) {
+  REQUIRE(kn != nullptr, "null known-region schedule");
+  REQUIRE(kn->S >= 1, "known-region schedule needs S >= 1 positions");
+  REQUIRE(kn->z0 && kn->e0 && kn->q_a && kn->q_e, "null tensor in known-region schedule");
+  REQUIRE(kn->z0 != x_out && kn->e0 != x_out && kn->mask != x_out, "z0 / e0 / mask must not alias x_out");
+}
+
+// Every rule of a step (for_loop: of a sample loop) in `mode`; a null member of mode is a part not
+// asked for.  The parts are checked before the model's state, the step args after it.
+static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode, bool for_loop) {
+  REQUIRE(m != nullptr, "null model");
+  REQUIRE(a != nullptr, "null step args");
+  const bool cfg = m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr;
+  if (mode.gd != nullptr) {
+    REQUIRE(mode.gd->rescale >= 0.f && mode.gd->rescale <= 1.f, "guidance rescale must lie in [0, 1]");
+    if (mode.rescale() > 0.f) {
+      REQUIRE(cfg, "guidance rescale needs a CFG step (guidance > 0, y given, a conditional model)");
+      REQUIRE(a->n <= 65535, "rescaled steps take at most 65535 samples");
+    }
+  }
+  REQUIRE(mode.ddim == nullptr || mode.dpm == nullptr, "at most one of the DDIM and DPM schedules");
+  if (mode.ddim != nullptr) check_sched(mode.ddim);
+  if (mode.dpm != nullptr) check_sched(mode.dpm);
+  if (mode.known != nullptr) {  // its tables must cover the positions of the step's schedule
+    check_known(mode.known, a->x_out);
+    REQUIRE(mode.known->mask != nullptr, "a known-region step needs a mask");
+    REQUIRE(a->n <= 65535, "known-region steps take at most 65535 samples");
+    REQUIRE(mode.known->S == mode.positions(*a), "known-region S differs from the schedule's");
+  }
+  check_shapes(m, a->n, a->h, a->w);
+  REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
+  if (mode.rule() == Rule::DPM) {
+    REQUIRE(a->noise == nullptr, "the DPM solver takes no noise (noise must be NULL)");
+    REQUIRE(mode.dpm->hist != a->x_in && mode.dpm->hist != a->x_out, "hist must not alias x");
+  } else if (mode.rule() == Rule::DDPM) {  // (the strided steps ignore these)
+    REQUIRE(a->c1 && a->c2 && a->sd, "null tensor in step args");
+    REQUIRE(a->T >= 1, "T must be >= 1");
+  }
+  REQUIRE(m->in_ch <= 4, "in_ch must be <= 4");
+  if (m->kind != DMX_UNET && a->guidance > 0.f) REQUIRE(a->y != nullptr, "CFG needs y");
+  if (m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND)
+    REQUIRE((a->vals == nullptr) == (a->mask == nullptr), "vals and mask must be given together");
+  if (for_loop) {
+    REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");
+    REQUIRE(a->t_stride == 0, "sample loop needs a device scalar t (t_stride 0)");
+    REQUIRE(a->noise == nullptr, "sample loop draws on-device Philox noise (noise must be NULL)");
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The step and the loop behind the dmx_step* / dmx_sample_loop* entries
+// ---------------------------------------------------------------------------
+static void sample_step(dmx_model* m, const dmx_step_args* a, const StepMode& mode, hipStream_t st) {
+  validate(m, a, mode, false);
+  ensure_planes(m, st);
+  run_planned(m, st, [&](Run& R) { step_body(R, *a, mode); });
+}
+
+// Capture what `body` launches on st into *graph and instantiate it as *exec (both owned by a graph
+// slot of m from the moment they are stored).  Any failure on the way drops every slot.
+template <typename F>
+static void capture(dmx_model* m, hipStream_t st, F&& body, hipGraph_t* graph, hipGraphExec_t* exec) {
+  HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+  try {
+    body();
+  } catch (...) {
+    hipGraph_t g = nullptr;
+    (void)hipStreamEndCapture(st, &g);
+    if (g) (void)hipGraphDestroy(g);
+    drop_graph(m);
+    throw;
+  }
+  const hipError_t ec = hipStreamEndCapture(st, graph);
+  const hipError_t ei = ec == hipSuccess ? hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) : ec;
+  if (ei != hipSuccess) {
+    drop_graph(m);
+    HIPCHK(ei);
+  }
+}
+
+static constexpr int kGraphSteps = 8;
+
+// `steps` in-place steps.  The scalar a->t counts down by one per step in every mode — timesteps in
+// the DDPM loop, positions of the schedule in the strided ones.  The DPM history buffer is updated
+// in place by every step and the known-region blend reads the position scalar its tail read, so
+// neither needs more than t's ping-pong inside the multi-step graph.
+static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mode, int steps, int use_graph,
+                        hipStream_t st) {
+  validate(m, a, mode, true);
+  REQUIRE(steps >= 0, "steps must be >= 0");
+  ensure_planes(m, st);
+  int64_t* tdev = const_cast<int64_t*>(a->t);
+  if (!use_graph) {
+    for (int i = 0; i < steps; ++i) {
+      run_planned(m, st, [&](Run& R) { step_body(R, *a, mode); });
+      decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
+      HIPCHK(hipGetLastError());
+    }
+    return;
+  }
+  const GraphKey key = make_graph_key(*a, mode, m->ctx->table_gen);
+  GraphSlot* slot = m->graphs.find(key);
+  if (slot == nullptr) {
+    // plan + allocate outside capture (a grown arena drops every slot: their graphs point into the
+    // old one), then capture the real launches
+    plan_ws(m, st, [&](Run& R) { step_body(R, *a, mode); });
+    slot = m->graphs.victim();
+    drop_slot(m, slot);  // a free slot, or the least recently used pair makes room
+    GraphPair& gp = slot->val;
+    capture(m, st, [&] {
+      Run R{m, st, false, m->ws};
+      step_body(R, *a, mode);
+      decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
+    }, &gp.graph, &gp.gexec);
+    // kGraphSteps consecutive steps in one graph: the gap between two graph launches (≈9 µs of
+    // idle GPU per step in the replay trace) is paid once per kGraphSteps steps.  Inside it, t
+    // alternates between the caller's scalar and a scratch scalar: step k reads one and its
+    // embedding kernel stores t - 1 in the other (no one-thread decrement launch per step; an even
+    // kGraphSteps ends in the caller's scalar).  The noise is keyed by (seed, t, sample), so the
+    // captured steps compute what kGraphSteps replays of the one-step graph compute.
+    static_assert(kGraphSteps % 2 == 0, "t ping-pong must end in the caller's buffer");
+    int64_t* tscr = m->t_scratch;
+    capture(m, st, [&] {
+      for (int k = 0; k < kGraphSteps; ++k) {
+        m->ws.off = 0;
+        Run R{m, st, false, m->ws};
+        dmx_step_args ak = *a;
+        ak.t = (k & 1) ? tscr : tdev;
+        step_body(R, ak, mode, {(k & 1) ? tdev : tscr, k > 0});  // cond MLP rows from step 0 of the graph
+      }
+    }, &gp.graph_k, &gp.gexec_k);
+    // the slot is not `used` (no key can find it) until both graphs are instantiated
+    m->graphs.claim(slot, key);
+    ++m->graph_captures;
+  }
+  int i = 0;
+  for (; i + kGraphSteps <= steps; i += kGraphSteps) HIPCHK(hipGraphLaunch(slot->val.gexec_k, st));
+  for (; i < steps; ++i) HIPCHK(hipGraphLaunch(slot->val.gexec, st));
+}
+
+// ---------------------------------------------------------------------------
+// Standalone updates (dmx_ddpm_update / dmx_ddim_update / dmx_dpm_update): the tail on given eps
+// ---------------------------------------------------------------------------
+// What the three have in common; the caller adds its tables (and noise, where its rule draws).
+static StepTailParams update_params(const float* x, float* x_out, const float* eu, const float* ec, float guidance,
+                                    const int64_t* t, int t_stride, int n, int c, int h, int w) {
+  REQUIRE(x && x_out && eu && t, "null tensor");
+  REQUIRE(n >= 1 && c >= 1 && c <= 4 && h >= 1 && w >= 1, "bad shape");
+  StepTailParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.Co = c;
+  p.B = n;
+  p.HW = h * w;
+  p.cfg = ec != nullptr ? 1 : 0;
+  p.guidance = guidance;
+  p.eps_u = eu;
+  p.eps_c = ec;
+  p.x = x;
+  p.x_out = x_out;
+  p.t = t;
+  p.t_stride = t_stride;
+  return p;
+}
+
+static void launch_update(const StepTailParams& p, Rule rule, hipStream_t st) {
+  launch_step_tail(p, rule, false, dim3(cdiv(p.HW, 256), p.B), st);
+  HIPCHK(hipGetLastError());
+}
+
+}  // namespace dmx

@@ -1,0 +1,83 @@
+// What kind of step a sampling call runs, and the key its captured graphs are kept under
+// (sample_engine.h).  Host C++ only — no HIP type or call appears here — so the key's rules are
+// exercised by a stand-alone program as well (tools/step_mode_check.cpp).
+#pragma once
+#include <cstring>
+
+#include "dmx.h"
+
+namespace dmx {
+
+enum class Rule { DDPM, DDIM, DPM };  // the tail's update
+
+// The optional parts of a step (include/dmx.h); all null: the plain DDPM step.
+struct StepMode {
+  const dmx_ddim_sched* ddim = nullptr;    // strided sampling: a.t holds positions, a.c1 / c2 / sd / T are not read
+  const dmx_dpm_sched* dpm = nullptr;      // the same with the DPM-Solver++(2M) update (at most one of ddim / dpm)
+  const dmx_known_sched* known = nullptr;  // the known-region blend follows the tail
+  const dmx_guidance* gd = nullptr;        // guidance controls beyond the scale
+
+  Rule rule() const { return dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM; }
+  // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
+  // rescale == 0 is no guidance struct at all: launches and graph key are those of the plain call.
+  float rescale() const { return gd != nullptr && gd->rescale > 0.f ? gd->rescale : 0.f; }
+  // positions of the step's schedule, and their timesteps (null: the position is the timestep)
+  int positions(const dmx_step_args& a) const { return dpm != nullptr ? dpm->S : ddim != nullptr ? ddim->S : a.T; }
+  const int64_t* t_map() const { return dpm != nullptr ? dpm->t_map : ddim != nullptr ? ddim->t_map : nullptr; }
+};
+
+// Compared bytewise, so every byte is zero unless make_graph_key sets it.
+struct GraphKey {
+  dmx_step_args a;
+  dmx_ddim_sched sched;  // strided loops: the schedule the graphs read (all zero: the DDPM loop)
+  dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
+  dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
+  dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
+  int table_gen;  // dmx_ctx::table_gen at capture
+  bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
+};
+
+// The key of a loop: everything its graphs hold.  The step args enter as the caller's bytes; the
+// optional structs enter member by member, so their padding stays zero.  A validated schedule has
+// S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart.
+inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen) {
+  GraphKey key;
+  std::memset(&key, 0, sizeof(key));
+  std::memcpy(&key.a, &a, sizeof(dmx_step_args));
+  if (mode.rule() != Rule::DDPM) {  // the strided graphs read the schedule instead of these
+    key.a.c1 = key.a.c2 = key.a.sd = nullptr;
+    key.a.T = 0;
+  }
+  if (mode.rule() == Rule::DDIM) {
+    key.sched.t_map = mode.ddim->t_map;
+    key.sched.k_e = mode.ddim->k_e;
+    key.sched.k_a = mode.ddim->k_a;
+    key.sched.k_s = mode.ddim->k_s;
+    key.sched.k_d = mode.ddim->k_d;
+    key.sched.k_n = mode.ddim->k_n;
+    key.sched.S = mode.ddim->S;
+  } else if (mode.rule() == Rule::DPM) {
+    key.a.seed = 0;  // (not read: the solver draws nothing)
+    key.dpm.t_map = mode.dpm->t_map;
+    key.dpm.k_e = mode.dpm->k_e;
+    key.dpm.k_a = mode.dpm->k_a;
+    key.dpm.k_x = mode.dpm->k_x;
+    key.dpm.k_c = mode.dpm->k_c;
+    key.dpm.k_p = mode.dpm->k_p;
+    key.dpm.hist = mode.dpm->hist;  // read and written by every step
+    key.dpm.S = mode.dpm->S;
+  }
+  if (mode.known != nullptr) {  // the blend's launches are in the graphs too
+    key.known.z0 = mode.known->z0;
+    key.known.e0 = mode.known->e0;
+    key.known.mask = mode.known->mask;
+    key.known.q_a = mode.known->q_a;
+    key.known.q_e = mode.known->q_e;
+    key.known.S = mode.known->S;
+  }
+  key.gd.rescale = mode.rescale();
+  key.table_gen = table_gen;
+  return key;
+}
+
+}  // namespace dmx

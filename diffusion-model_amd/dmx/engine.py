@@ -293,6 +293,23 @@ class NativeModel:
         self.ctx.ensure_time_table(last[1])
         return sc
 
+    def _mode(self, x, sched, hist, known, rescale, guidance, y, tables):
+        """The optional parts of a step or loop on x, as documented there -> (the ddim, dpm, known and
+        guidance arguments of dmx_step_guided / dmx_sample_loop_guided, the tables its step args carry:
+        None with a schedule).  rescale 0 goes as a guidance struct too: the library then runs exactly
+        the plain / known-region call.  Makes sure the time table reaches the last timestep."""
+        gd = _guidance_struct(rescale, guidance, y)
+        kn = _known_struct(known, x.device, x, need_mask=True) if known is not None else None
+        sc = None
+        if sched is not None:
+            sc = self._sched(sched, x.device, hist, x)
+            tables = None
+        else:
+            self.ctx.ensure_time_table(int(tables[0].numel()))
+        dpm = isinstance(sc, DpmSched)
+        parts = (None if dpm else sc, sc if dpm else None, kn, gd if gd is not None else Guidance(0.0))
+        return tuple(None if s is None else ctypes.byref(s) for s in parts), tables
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
              sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
@@ -308,34 +325,13 @@ class NativeModel:
         plain step, launched exactly as without the keyword."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
-        gd = _guidance_struct(rescale, guidance, y)
-        dpm = isinstance(sched, DpmSchedule)
-        kn = _known_struct(known, x_in.device, x_in, need_mask=True) if known is not None else None
-        if sched is not None:
-            sc = self._sched(sched, x_in.device, hist, x_in)
-            tables = None
-        else:
-            self.ctx.ensure_time_table(int(tables[0].numel()))
+        mode, tables = self._mode(x_in, sched, hist, known, rescale, guidance, y, tables)
         t, y, vals, mask, noise = self._norm_inputs(x_in, t, y, vals, mask, noise)
         a = self._args(x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
                        sample_offset)
         with torch.cuda.device(x_in.device):
-            st = ctypes.c_void_p(_stream(x_in.device))
-            if gd is not None:
-                check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a),
-                                               ctypes.byref(sc) if sched is not None and not dpm else None,
-                                               ctypes.byref(sc) if dpm else None,
-                                               ctypes.byref(kn) if kn is not None else None, ctypes.byref(gd), st))
-            elif kn is not None:
-                check(self.lib.dmx_step_known(self.handle, ctypes.byref(a),
-                                              ctypes.byref(sc) if sched is not None and not dpm else None,
-                                              ctypes.byref(sc) if dpm else None, ctypes.byref(kn), st))
-            elif dpm:
-                check(self.lib.dmx_step_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
-            elif sched is not None:
-                check(self.lib.dmx_step_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), st))
-            else:
-                check(self.lib.dmx_step(self.handle, ctypes.byref(a), st))
+            check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a), *mode,
+                                           ctypes.c_void_p(_stream(x_in.device))))
 
     def step_profile(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
                      t_stride=1, cap=1024):
@@ -372,14 +368,7 @@ class NativeModel:
         The model keeps the captured graphs of the last few distinct loops (graph_captures counts the
         captures), so alternating guided, unguided and rescaled loops replay instead of recapturing."""
         _check_state(x, "x")
-        gd = _guidance_struct(rescale, guidance, y)
-        dpm = isinstance(sched, DpmSchedule)
-        kn = _known_struct(known, x.device, x, need_mask=True) if known is not None else None
-        if sched is not None:
-            sc = self._sched(sched, x.device, hist, x)
-            tables = None
-        else:
-            self.ctx.ensure_time_table(int(tables[0].numel()))
+        mode, tables = self._mode(x, sched, hist, known, rescale, guidance, y, tables)
         if t_dev.dtype != torch.long or not t_dev.is_contiguous() or t_dev.device != x.device:
             raise ValueError("sample_loop: t_dev must be a contiguous int64 device scalar on x's device "
                              "(it is decremented in place)")
@@ -393,27 +382,8 @@ class NativeModel:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if gd is not None:
-                check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a),
-                                                      ctypes.byref(sc) if sched is not None and not dpm else None,
-                                                      ctypes.byref(sc) if dpm else None,
-                                                      ctypes.byref(kn) if kn is not None else None,
-                                                      ctypes.byref(gd), int(steps), int(use_graph),
-                                                      ctypes.c_void_p(side.cuda_stream)))
-            elif kn is not None:
-                check(self.lib.dmx_sample_loop_known(self.handle, ctypes.byref(a),
-                                                     ctypes.byref(sc) if sched is not None and not dpm else None,
-                                                     ctypes.byref(sc) if dpm else None, ctypes.byref(kn), int(steps),
-                                                     int(use_graph), ctypes.c_void_p(side.cuda_stream)))
-            elif dpm:
-                check(self.lib.dmx_sample_loop_dpm(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
-                                                   int(use_graph), ctypes.c_void_p(side.cuda_stream)))
-            elif sched is not None:
-                check(self.lib.dmx_sample_loop_ddim(self.handle, ctypes.byref(a), ctypes.byref(sc), int(steps),
-                                                    int(use_graph), ctypes.c_void_p(side.cuda_stream)))
-            else:
-                check(self.lib.dmx_sample_loop(self.handle, ctypes.byref(a), int(steps), int(use_graph),
-                                               ctypes.c_void_p(side.cuda_stream)))
+            check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a), *mode, int(steps), int(use_graph),
+                                                  ctypes.c_void_p(side.cuda_stream)))
         cur.wait_stream(side)
 
     # ---- VAE -----------------------------------------------------------------------------
@@ -494,7 +464,7 @@ def _check_state(x: torch.Tensor, what: str) -> None:
 
 
 def _guidance_struct(rescale, guidance, y) -> Optional[Guidance]:
-    """The C view of a step's guidance controls: None for rescale 0 (the plain calls are made)."""
+    """The C view of a step's guidance controls: None for rescale 0 (nothing is asked of y or the scale)."""
     phi = float(rescale)
     if not 0.0 <= phi <= 1.0:
         raise ValueError(f"rescale must be in [0, 1] (got {rescale})")
@@ -531,6 +501,24 @@ def cfg_rescale(eu, ec, guidance, phi):
     return eps, r
 
 
+def _update_operands(x, eu, ec, noise, pos, pos_name):
+    """The operands the standalone updates share, as contiguous fp32 / int64 tensors on x's device and
+    of x's shape (pos: one entry per sample) -> (x, eu, ec or None, noise or None, pos)."""
+    require_cuda(x, "x")
+    dev = x.device
+    x_c = x.to(dtype=torch.float32).contiguous()
+    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
+    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
+    nz_c = noise.to(device=dev, dtype=torch.float32).contiguous() if noise is not None else None
+    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
+    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond"), (nz_c, "noise")):
+        if e is not None and tuple(e.shape) != tuple(x_c.shape):
+            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
+    if p_c.numel() != x_c.shape[0]:
+        raise ValueError(f"{pos_name} has {p_c.numel()} entries for a batch of {x_c.shape[0]}")
+    return x_c, eu_c, ec_c, nz_c, p_c
+
+
 def ddpm_update(x, eu, ec, guidance, t, tables, noise=None, seed=0, sample_offset=0):
     """Standalone K1 (diff.py:151,158-162) for duck-typed models: returns x'.
 
@@ -539,24 +527,13 @@ def ddpm_update(x, eu, ec, guidance, t, tables, noise=None, seed=0, sample_offse
     caching allocator)."""
     lib = _lib.load()
     c1, c2, sd = tables
-    require_cuda(x, "x")
-    dev = x.device
-    x_c = x.to(dtype=torch.float32).contiguous()
+    x_c, eu_c, ec_c, nz_c, t_c = _update_operands(x, eu, ec, noise, t, "t")
     n, c, h, w = x_c.shape
-    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
-    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
-    nz_c = noise.to(device=dev, dtype=torch.float32).contiguous() if noise is not None else None
-    t_c = t.to(device=dev, dtype=torch.long).contiguous()
-    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond"), (nz_c, "noise")):
-        if e is not None and tuple(e.shape) != tuple(x_c.shape):
-            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
-    if t_c.numel() != n:
-        raise ValueError(f"t has {t_c.numel()} entries for a batch of {n}")
     out = torch.empty_like(x_c)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(x.device):
         check(lib.dmx_ddpm_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(t_c),
                                   1, _ptr(c1), _ptr(c2), _ptr(sd), int(c1.numel()), _ptr(nz_c), int(seed),
-                                  int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+                                  int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(x.device))))
     return out
 
 
@@ -582,24 +559,14 @@ def ddim_update(x, eu, ec, guidance, pos, sched, noise=None, seed=0, sample_offs
     Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
     lib = _lib.load()
     require_cuda(x, "x")
-    dev = x.device
-    sc = _sched_struct(sched, dev)
-    x_c = x.to(dtype=torch.float32).contiguous()
+    sc = _sched_struct(sched, x.device)
+    x_c, eu_c, ec_c, nz_c, p_c = _update_operands(x, eu, ec, noise, pos, "pos")
     n, c, h, w = x_c.shape
-    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
-    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
-    nz_c = noise.to(device=dev, dtype=torch.float32).contiguous() if noise is not None else None
-    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
-    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond"), (nz_c, "noise")):
-        if e is not None and tuple(e.shape) != tuple(x_c.shape):
-            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
-    if p_c.numel() != n:
-        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
     out = torch.empty_like(x_c)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(x.device):
         check(lib.dmx_ddim_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
                                   ctypes.byref(sc), _ptr(nz_c), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                  int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+                                  int(sample_offset), n, c, h, w, ctypes.c_void_p(_stream(x.device))))
     return out
 
 
@@ -638,19 +605,10 @@ def dpm_update(x, eu, ec, guidance, pos, sched, hist, out=None):
     out: where x' goes (fp32, contiguous, x's shape; may be x itself), a new tensor by default.
     Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
     lib = _lib.load()
-    require_cuda(x, "x")
+    x_c, eu_c, ec_c, _, p_c = _update_operands(x, eu, ec, None, pos, "pos")
     dev = x.device
-    x_c = x.to(dtype=torch.float32).contiguous()
     sc = _dpm_struct(sched, dev, hist, x_c)
     n, c, h, w = x_c.shape
-    eu_c = eu.to(device=dev, dtype=torch.float32).contiguous()
-    ec_c = ec.to(device=dev, dtype=torch.float32).contiguous() if ec is not None else None
-    p_c = pos.to(device=dev, dtype=torch.long).contiguous()
-    for e, nm in ((eu_c, "eps"), (ec_c, "eps_cond")):
-        if e is not None and tuple(e.shape) != tuple(x_c.shape):
-            raise ValueError(f"{nm} shape {tuple(e.shape)} != x shape {tuple(x_c.shape)}")
-    if p_c.numel() != n:
-        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
     if out is None:
         out = torch.empty_like(x_c)
     elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev

@@ -199,12 +199,21 @@ def test_header_and_bindings_name_the_new_symbols():
 
 
 # ---- the graph slots' bookkeeping, stand-alone under the host sanitizers ---------------------------------
-def test_graph_slots_lru_standalone(tmp_path):
+def _standalone_check(tmp_path, name):
     from dmx import build
     cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or build.HIPCC  # (host code only)
-    exe = str(tmp_path / "graph_slots_check")
+    exe = str(tmp_path / name)
     subprocess.run([cxx, "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "diffusion-model_amd", "dmx", "csrc"),
-                    os.path.join(REPO, "tools", "graph_slots_check.cpp"), "-o", exe], check=True)
+                    "-I", os.path.join(REPO, "include"), "-I", os.path.join(REPO, "diffusion-model_amd", "dmx", "csrc"),
+                    os.path.join(REPO, "tools", name + ".cpp"), "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True)
-    assert "graph_slots_check: ok" in out.stdout
+    assert name + ": ok" in out.stdout
+
+
+def test_graph_slots_lru_standalone(tmp_path):
+    _standalone_check(tmp_path, "graph_slots_check")
+
+
+# ---- the graph key's rules (what enters it in which mode), stand-alone likewise ---------------------------
+def test_step_mode_key_standalone(tmp_path):
+    _standalone_check(tmp_path, "step_mode_check")

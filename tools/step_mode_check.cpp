@@ -1,0 +1,167 @@
+// Stand-alone check of the sample-loop graph key's rules (dmx/csrc/step_mode.h).
+// Host C++ only; build it with the host compiler and sanitizers and run it:
+//   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include \
+//       -I diffusion-model_amd/dmx/csrc tools/step_mode_check.cpp -o step_mode_check && ./step_mode_check
+// The pointers are dummies: the key holds their values and nothing dereferences them.
+#include <cstdio>
+#include <cstring>
+
+#include "step_mode.h"
+
+using namespace dmx;
+
+static int fails = 0;
+#define CHECK(c)                                                  \
+  do {                                                            \
+    if (!(c)) {                                                   \
+      std::fprintf(stderr, "line %d: %s\n", __LINE__, #c);       \
+      ++fails;                                                    \
+    }                                                             \
+  } while (0)
+
+static float mem[64];
+static int64_t imem[8];
+
+// Every struct is filled over `fill` bytes first: what its padding then holds.
+struct Inputs {
+  dmx_step_args a;
+  dmx_ddim_sched ddim;
+  dmx_dpm_sched dpm;
+  dmx_known_sched known;
+  dmx_guidance gd;
+  explicit Inputs(int fill = 0) {
+    std::memset(&a, 0, sizeof(a));  // (the step args enter the key as the caller's bytes)
+    a.x_in = a.x_out = mem;
+    a.t = imem;
+    a.y = imem + 1;
+    a.null_label = 3;
+    a.vals = mem + 1;
+    a.mask = mem + 2;
+    a.guidance = 3.f;
+    a.c1 = mem + 3;
+    a.c2 = mem + 4;
+    a.sd = mem + 5;
+    a.T = 1000;
+    a.seed = 7;
+    a.sample_offset = 64;
+    a.n = 2;
+    a.h = a.w = 8;
+    std::memset(&ddim, fill, sizeof(ddim));
+    ddim.t_map = imem + 2;
+    ddim.k_e = mem + 6;
+    ddim.k_a = mem + 7;
+    ddim.k_s = mem + 8;
+    ddim.k_d = mem + 9;
+    ddim.k_n = mem + 10;
+    ddim.S = 3;
+    std::memset(&dpm, fill, sizeof(dpm));
+    dpm.t_map = imem + 2;
+    dpm.k_e = mem + 6;
+    dpm.k_a = mem + 7;
+    dpm.k_x = mem + 8;
+    dpm.k_c = mem + 9;
+    dpm.k_p = mem + 10;
+    dpm.hist = mem + 11;
+    dpm.S = 3;
+    std::memset(&known, fill, sizeof(known));
+    known.z0 = mem + 12;
+    known.e0 = mem + 13;
+    known.mask = mem + 14;
+    known.q_a = mem + 15;
+    known.q_e = mem + 16;
+    known.S = 3;
+    std::memset(&gd, fill, sizeof(gd));
+    gd.rescale = 0.f;
+  }
+  GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1) const {
+    return make_graph_key(a, StepMode{use_ddim ? &ddim : nullptr, use_dpm ? &dpm : nullptr,
+                                      use_known ? &known : nullptr, use_gd ? &gd : nullptr}, table_gen);
+  }
+};
+
+// Does the key of the given mode differ from `base` once `edit` has changed one member of the inputs?
+template <typename Edit>
+static bool moved(const GraphKey& base, bool ddim, bool dpm, bool known, Edit&& edit) {
+  Inputs in;
+  edit(in);
+  return !(in.key(ddim, dpm, known) == base);
+}
+#define MOVES(ddim, dpm, known, stmt) \
+  CHECK(moved(Inputs().key(ddim, dpm, known), ddim, dpm, known, [](Inputs& in) { stmt; }))
+#define STAYS(ddim, dpm, known, stmt) \
+  CHECK(!moved(Inputs().key(ddim, dpm, known), ddim, dpm, known, [](Inputs& in) { stmt; }))
+
+int main() {
+  // 1. the DDPM key holds the tables, T and the seed
+  MOVES(false, false, false, in.a.c1 = mem + 40);
+  MOVES(false, false, false, in.a.c2 = mem + 40);
+  MOVES(false, false, false, in.a.sd = mem + 40);
+  MOVES(false, false, false, in.a.T = 999);
+  MOVES(false, false, false, in.a.seed = 8);
+  // 2. a DDIM key holds its schedule and the seed instead of the tables and T
+  STAYS(true, false, false, in.a.c1 = mem + 40);
+  STAYS(true, false, false, in.a.c2 = nullptr);
+  STAYS(true, false, false, in.a.sd = mem + 40);
+  STAYS(true, false, false, in.a.T = 0);
+  MOVES(true, false, false, in.ddim.t_map = imem + 5);
+  MOVES(true, false, false, in.ddim.k_e = mem + 40);
+  MOVES(true, false, false, in.ddim.k_a = mem + 40);
+  MOVES(true, false, false, in.ddim.k_s = mem + 40);
+  MOVES(true, false, false, in.ddim.k_d = mem + 40);
+  MOVES(true, false, false, in.ddim.k_n = mem + 40);
+  MOVES(true, false, false, in.ddim.S = 4);
+  MOVES(true, false, false, in.a.seed = 8);
+  // 3. a DPM key holds neither those nor the seed; it holds its schedule and the history buffer
+  STAYS(false, true, false, in.a.c1 = mem + 40);
+  STAYS(false, true, false, in.a.c2 = mem + 40);
+  STAYS(false, true, false, in.a.sd = nullptr);
+  STAYS(false, true, false, in.a.T = 0);
+  STAYS(false, true, false, in.a.seed = 8);
+  MOVES(false, true, false, in.dpm.hist = mem + 40);
+  MOVES(false, true, false, in.dpm.t_map = imem + 5);
+  MOVES(false, true, false, in.dpm.k_e = mem + 40);
+  MOVES(false, true, false, in.dpm.k_a = mem + 40);
+  MOVES(false, true, false, in.dpm.k_x = mem + 40);
+  MOVES(false, true, false, in.dpm.k_c = mem + 40);
+  MOVES(false, true, false, in.dpm.k_p = mem + 40);
+  MOVES(false, true, false, in.dpm.S = 4);
+  // 4. no guidance struct, rescale 0 and the plain mode are one key; every phi > 0 is its own
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    Inputs in;
+    const GraphKey plain = in.key(ddim, dpm);
+    CHECK(in.key(ddim, dpm, false, true) == plain);
+    CHECK(plain == make_graph_key(in.a, StepMode{ddim ? &in.ddim : nullptr, dpm ? &in.dpm : nullptr}, 1));
+    in.gd.rescale = 0.25f;
+    const GraphKey quarter = in.key(ddim, dpm, false, true);
+    in.gd.rescale = 0.5f;
+    const GraphKey half = in.key(ddim, dpm, false, true);
+    CHECK(!(quarter == plain) && !(half == plain) && !(quarter == half));
+  }
+  CHECK(StepMode{}.rescale() == 0.f);
+  // 5. a known region is part of the key, member by member
+  CHECK(!(Inputs().key(false, false, true) == Inputs().key(false, false)));
+  CHECK(!(Inputs().key(true, false, true) == Inputs().key(true, false)));
+  MOVES(true, false, true, in.known.z0 = mem + 40);
+  MOVES(true, false, true, in.known.e0 = mem + 40);
+  MOVES(true, false, true, in.known.mask = mem + 40);
+  MOVES(true, false, true, in.known.q_a = mem + 40);
+  MOVES(true, false, true, in.known.q_e = mem + 40);
+  MOVES(true, false, true, in.known.S = 4);
+  // 6. the three rules never share a key
+  {
+    const GraphKey ddpm = Inputs().key(false, false), ddim = Inputs().key(true, false), dpm = Inputs().key(false, true);
+    CHECK(!(ddpm == ddim) && !(ddpm == dpm) && !(ddim == dpm));
+    CHECK(StepMode{}.rule() == Rule::DDPM);
+  }
+  // 7. the generation of the context's time table
+  CHECK(!(Inputs().key(false, false, false, false, 2) == Inputs().key(false, false)));
+  CHECK(!(Inputs().key(true, false, false, false, 2) == Inputs().key(true, false)));
+  // 8. the padding of the optional structs stays out of the key
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    CHECK(Inputs(0xAA).key(ddim, dpm, true, true) == Inputs(0).key(ddim, dpm, true, true));
+  }
+  if (fails == 0) std::puts("step_mode_check: ok");
+  return fails == 0 ? 0 : 1;
+}
