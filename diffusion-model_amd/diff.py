@@ -361,6 +361,124 @@ class Diffuser:
                              f"(got guidance_scale={guidance_scale!r})")
         return interval, phi
 
+    # ---- composed guidance: K weighted condition branches over a chosen base -------------------
+    COMPOSE_MAX = 4  # extra branches over the base (include/dmx.h DMX_COMPOSE_MAX)
+
+    @staticmethod
+    def _per_sample(v) -> bool:
+        """Is a guidance scale / weight given per sample (a sequence, an array or a tensor with a dimension)?"""
+        return isinstance(v, (list, tuple, np.ndarray)) or (isinstance(v, torch.Tensor) and v.dim() >= 1)
+
+    @classmethod
+    def _weight_row(cls, v, B: int, what: str) -> torch.Tensor:
+        """A float or B floats -> (B,) fp32 on the CPU; not a finite number, or another length: ValueError."""
+        try:
+            if cls._per_sample(v):
+                row = torch.as_tensor(v).detach().to(device="cpu", dtype=torch.float32).reshape(-1)
+            else:
+                row = torch.full((B,), float(v), dtype=torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"{what} must be a float or {B} floats (got {v!r})") from None
+        if row.numel() != B:
+            raise ValueError(f"{what} has {row.numel()} entries for {B} samples")
+        if not bool(torch.isfinite(row).all()):
+            raise ValueError(f"{what} must be finite (got {v!r})")
+        return row
+
+    def _compose_args(self, y_list, vals, msk, guidance_scale, base="null", also=None, guidance_interval=None,
+                      guidance_rescale=0.0, null_label=0, key_order=None, class_keys=None, device="cpu"):
+        """Argument rules of the samplers' (base, also) keywords and of a per-sample guidance_scale ->
+        None (the call is the plain one: base "null", no `also`, a scalar scale) or the branch tables
+        (y_rows (K+1,B) int64, vals_rows (K+1,B,Kc), mask_rows (K+1,B,Kc), weights (K,B) fp32) on
+        `device`.  Branch 0 is the base: "null" = null label with the call's vals / msk, "dropped" = null
+        label with vals = mask = 0 (the input the training's joint dropout produced), a condition spec =
+        a negative condition.  Branch 1 is the call's own condition with weight guidance_scale (a
+        positive float, or B finite floats); branches 2.. are the specs of `also` (at most three).  A
+        spec is a dict: "classes" (an int or B ints), optional "cond" / "cond_mask" (every form
+        _build_cond takes) and, in `also` only, "weight" (a float or B floats, finite).  Every violation
+        raises ValueError; nothing here touches a GPU unless `device` is one."""
+        B = len(y_list)
+        also = [] if also is None else also
+        if not isinstance(also, (list, tuple)):
+            raise ValueError(f"`also` must be a list of condition specs (got {type(also).__name__})")
+        if isinstance(base, str):
+            if base not in ("null", "dropped"):
+                raise ValueError(f'base must be "null", "dropped" or a condition spec (got {base!r})')
+        elif not isinstance(base, dict):
+            raise ValueError(f'base must be "null", "dropped" or a condition spec (got {type(base).__name__})')
+        per_sample = self._per_sample(guidance_scale)
+        if isinstance(base, str) and base == "null" and not also and not per_sample:
+            return None
+        if 1 + len(also) > self.COMPOSE_MAX:
+            raise ValueError(f"at most {self.COMPOSE_MAX} condition branches: the call's own and "
+                             f"{self.COMPOSE_MAX - 1} in `also` (got {len(also)})")
+        if guidance_interval is not None:
+            raise ValueError("composed guidance (base / also / per-sample guidance_scale) takes no guidance_interval")
+        try:
+            phi = float(guidance_rescale)
+        except (TypeError, ValueError):
+            phi = float("nan")
+        if phi != 0.0:
+            raise ValueError("composed guidance (base / also / per-sample guidance_scale) takes no guidance_rescale")
+        if per_sample:
+            w1 = self._weight_row(guidance_scale, B, "guidance_scale")
+        else:
+            try:
+                ok = guidance_scale is not None and float(guidance_scale) > 0 and np.isfinite(float(guidance_scale))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"composed guidance needs guidance_scale > 0 (got {guidance_scale!r})")
+            w1 = self._weight_row(guidance_scale, B, "guidance_scale")
+
+        def spec_rows(spec, where, weighted):
+            if not isinstance(spec, dict):
+                raise ValueError(f"{where}: a condition spec is a dict (got {type(spec).__name__})")
+            allowed = {"classes", "cond", "cond_mask"} | ({"weight"} if weighted else set())
+            unknown = set(spec) - allowed
+            if unknown or "classes" not in spec or (weighted and "weight" not in spec):
+                raise ValueError(f"{where}: a condition spec has the keys {sorted(allowed)}, 'classes' "
+                                 f"{'and weight ' if weighted else ''}required (got {sorted(map(str, spec))})")
+            cl = spec["classes"]
+            if isinstance(cl, (int, np.integer)) and not isinstance(cl, bool):
+                ys = [int(cl)] * B
+            else:
+                try:
+                    ys = [int(c) for c in (cl.tolist() if isinstance(cl, (torch.Tensor, np.ndarray)) else cl)]
+                except (TypeError, ValueError):
+                    raise ValueError(f"{where}: 'classes' must be an int or {B} ints (got {cl!r})") from None
+                if len(ys) != B:
+                    raise ValueError(f"{where}: 'classes' has {len(ys)} entries for {B} samples")
+            v, m = self._build_cond(ys, spec.get("cond"), spec.get("cond_mask"), key_order, class_keys, device)
+            if tuple(v.shape) != tuple(vals.shape) or tuple(m.shape) != tuple(vals.shape):
+                raise ValueError(f"{where}: cond rows {tuple(v.shape)} differ from the call's {tuple(vals.shape)}")
+            w = self._weight_row(spec["weight"], B, f"{where}: 'weight'") if weighted else None
+            return torch.tensor(ys, dtype=torch.long, device=device), v.float(), m.float(), w
+
+        y_call = torch.tensor([int(c) for c in y_list], dtype=torch.long, device=device)
+        v_call, m_call = vals.to(device).float(), msk.to(device).float()
+        if isinstance(base, dict):
+            y0, v0, m0, _ = spec_rows(base, "base", False)
+        else:
+            y0 = torch.full_like(y_call, int(null_label))
+            v0, m0 = (v_call, m_call) if base == "null" else (torch.zeros_like(v_call), torch.zeros_like(m_call))
+        ys, vs, ms, ws = [y0, y_call], [v0, v_call], [m0, m_call], [w1]
+        for i, spec in enumerate(also):
+            yk, vk, mk, wk = spec_rows(spec, f"also[{i}]", True)
+            ys.append(yk), vs.append(vk), ms.append(mk), ws.append(wk)
+        return (torch.stack(ys).contiguous(), torch.stack(vs).contiguous(), torch.stack(ms).contiguous(),
+                torch.stack(ws).to(device).contiguous())
+
+    @staticmethod
+    def _composed_eps(model, x, t, compose):
+        """A foreign model's composed prediction: one call per branch, then the mix (engine.compose_eps)."""
+        y_rows, v_rows, m_rows, w = compose
+        es = []
+        for k in range(y_rows.shape[0]):
+            e = model(x, t, y_rows[k].to(x.device), cond_vals=v_rows[k].to(x.device), cond_mask=m_rows[k].to(x.device))
+            es.append(e[0] if isinstance(e, (tuple, list)) else e)
+        return _engine.compose_eps(es, w)
+
     @staticmethod
     def _guided_run(tau, interval):
         """The positions of the ascending timesteps `tau` (tau_p at index p-1) whose step uses CFG:
@@ -491,7 +609,7 @@ class Diffuser:
         return self._denoise_cond(model, x, t, y, guidance_scale, null_label, cond_vals, cond_mask)
 
     def _denoise_cond(self, model, x, t, y=None, guidance_scale=0.0, null_label=0, cond_vals=None, cond_mask=None,
-                      known=None, unguided=False, rescale=0.0):
+                      known=None, unguided=False, rescale=0.0, compose=None):
         """denoise_cond after the range check — the samplers' own loops build t from a host-known
         step in [1, T] and call this directly, so the host never waits on the device per step.
         known (engine.known_blend's 5-tuple, tables over tau = 1..T): the known-region blend follows
@@ -500,9 +618,22 @@ class Diffuser:
         eps = model(x, t, y, cond_vals, cond_mask), whatever guidance_scale says — the public branch
         for "y without guidance" below mirrors the reference's error instead.
         rescale = phi > 0 (guided steps only): the guided prediction is scaled to the conditional
-        one's per-sample standard deviation before the update (engine.cfg_rescale)."""
+        one's per-sample standard deviation before the update (engine.cfg_rescale).
+        compose (_compose_args' tables): the composed step instead — y, the scale, vals and mask are
+        not read; a foreign model is called once per branch (_composed_eps)."""
         tables = self.coef_tables(x.device, clamp_prev=True)
         with torch.no_grad():
+            if compose is not None:
+                if _native_kind(model) in (1, 2) and x.is_cuda:
+                    noise = self._step_noise(x)
+                    out = torch.empty_like(x)
+                    model.native().step(x.contiguous(), out, t.to(x.device), None, 0, None, None, 0.0, tables, noise,
+                                        seed=self._seed() if noise is None else 0, known=known, compose=compose)
+                    return out
+                eps = self._composed_eps(model, x, t, compose)
+                noise = self._step_noise(x)
+                return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
+                                                       seed=self._seed() if noise is None else 0), t, known)
             if unguided:
                 if _native_kind(model) in (1, 2) and x.is_cuda:
                     noise = self._step_noise(x)
@@ -566,14 +697,27 @@ class Diffuser:
                                guidance_scale, null_label, cond_vals, cond_mask)
 
     def _ddim_step(self, model, x, pos, sched, noisy, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                   cond_mask=None, known=None, rescale=0.0):
+                   cond_mask=None, known=None, rescale=0.0, compose=None):
         """ddim_step after its checks; `noisy`: the schedule has noise (eta > 0).  Host-noise mode then
         draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws.
-        rescale = phi > 0 (CFG steps only): as in _denoise_cond."""
-        cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
+        rescale = phi > 0 (CFG steps only), compose: as in _denoise_cond."""
+        cfg = bool(compose is None and guidance_scale and y is not None and guidance_scale > 0)
         g = float(guidance_scale) if cfg else 0.0
         pos = pos.to(device=x.device, dtype=torch.long)
         with torch.no_grad():
+            if compose is not None:
+                if _native_kind(model) in (1, 2) and x.is_cuda:
+                    noise = self._step_noise(x) if noisy else None
+                    x_in = x.float().contiguous()
+                    out = torch.empty_like(x_in)
+                    model.native().step(x_in, out, pos, None, 0, None, None, 0.0, None, noise,
+                                        seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known,
+                                        compose=compose)
+                    return out
+                eps = self._composed_eps(model, x, sched[0][pos - 1], compose)
+                noise = self._step_noise(x) if noisy else None
+                seed = self._seed() if noisy and noise is None else 0
+                return self._blend(_engine.ddim_update(x, eps, None, 0.0, pos, sched, noise, seed=seed), pos, known)
             if y is None:
                 y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
             if _native_kind(model) in (1, 2) and x.is_cuda:
@@ -613,13 +757,22 @@ class Diffuser:
                               null_label, cond_vals, cond_mask)
 
     def _dpm_step(self, model, x, pos, sched, hist, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                  cond_mask=None, known=None, rescale=0.0):
+                  cond_mask=None, known=None, rescale=0.0, compose=None):
         """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update.
-        rescale = phi > 0 (CFG steps only): as in _denoise_cond."""
-        cfg = bool(guidance_scale and y is not None and guidance_scale > 0)
+        rescale = phi > 0 (CFG steps only), compose: as in _denoise_cond."""
+        cfg = bool(compose is None and guidance_scale and y is not None and guidance_scale > 0)
         g = float(guidance_scale) if cfg else 0.0
         pos = pos.to(device=x.device, dtype=torch.long)
         with torch.no_grad():
+            if compose is not None:
+                if _native_kind(model) in (1, 2) and x.is_cuda:
+                    x_in = x.float().contiguous()
+                    out = torch.empty_like(x_in)
+                    model.native().step(x_in, out, pos, None, 0, None, None, 0.0, None, None, sched=sched, hist=hist,
+                                        known=known, compose=compose)
+                    return out
+                eps = self._composed_eps(model, x, sched[0][pos - 1], compose)
+                return self._blend(_engine.dpm_update(x, eps, None, 0.0, pos, sched, hist), pos, known)
             if y is None:
                 y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
             if _native_kind(model) in (1, 2) and x.is_cuda:
@@ -860,6 +1013,8 @@ class Diffuser:
         strength: Optional[float] = None,
         guidance_interval: Optional[Tuple[int, int]] = None,
         guidance_rescale: float = 0.0,
+        base="null",
+        also=None,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -889,9 +1044,23 @@ class Diffuser:
         interval that holds no timestep of the schedule leaves the whole loop conditional-only; None
         guides every step.  guidance_rescale = phi in [0, 1] (Lin et al. 2023, §3.4), guided steps only:
         the guided prediction eg is scaled per sample by 1 + phi (std(ec) / std(eg) - 1), ec being the
-        conditional prediction.  Both need guidance_scale > 0 and neither changes the draw order."""
+        conditional prediction.  Both need guidance_scale > 0 and neither changes the draw order.
+
+        Composed guidance (Liu et al. 2022), with any sampler, init_latent and mask:
+        eps = e_0 + sum_k w_k (e_k - e_0) over a base branch 0 and up to four condition branches, run as
+        one (K+1) B forward per step.  base = "null" (the default): null label with the call's cond /
+        cond_mask, the reference's unconditional branch; "dropped": null label with cond = cond_mask = 0,
+        the input training's joint condition dropout produced; a condition spec: a negative condition to
+        steer away from.  The call's own condition is branch 1 with weight guidance_scale, which may be
+        B finite floats (a per-sample guidance scale); also = up to three condition specs, each a dict
+        {"classes": int or B ints, "cond": .., "cond_mask": .. (every form `cond` takes), "weight": float
+        or B floats}.  With base "null", no `also` and a scalar guidance_scale the call is the plain one.
+        A composed call takes no guidance_interval / guidance_rescale; the draw order is unchanged."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
-        interval, phi = self._guidance_args(guidance_scale, guidance_interval, guidance_rescale, self.num_timesteps)
+        composed = (not (isinstance(base, str) and base == "null")) or bool(also) or self._per_sample(guidance_scale)
+        interval, phi = self._guidance_args(None if composed else guidance_scale,
+                                            None if composed else guidance_interval,
+                                            0.0 if composed else guidance_rescale, self.num_timesteps)
         device = self.device
         items = self._norm_counts(class_counts)
         y_list: List[int] = []
@@ -900,6 +1069,8 @@ class Diffuser:
         B = len(y_list)
         y = torch.tensor(y_list, device=device, dtype=torch.long)
         vals, msk = self._build_cond(y_list, cond, cond_mask, key_order, class_keys, device)
+        compose = self._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval,
+                                     guidance_rescale, null_label, key_order, class_keys, device)
 
         known = self._known_inputs(init_latent, mask, strength, B, z_shape)
         if known is not None:
@@ -917,6 +1088,8 @@ class Diffuser:
             gkw["interval"] = interval
         if phi > 0:
             gkw["rescale"] = phi
+        if compose is not None:
+            gkw["compose"] = compose
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
                                 **(dict(known=known[:3]) if known is not None else {}), **gkw)
         if vae is None:
@@ -945,7 +1118,7 @@ class Diffuser:
         return x, p0, (z0, e0, kmask.to(x.device), q_a, q_e) if kmask is not None else None
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
-                       interval=None, rescale=0.0):
+                       interval=None, rescale=0.0, compose=None):
         """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
         mode = ("ddim", S, eta) (_sampler_mode): the strided loop instead — the counter walks the S
         positions of ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and
@@ -957,7 +1130,13 @@ class Diffuser:
         interval = (t_lo, t_hi) / rescale = phi (_guidance_args): the positions whose timestep lies
         outside the interval run unguided (one conditional forward), the others with CFG and, for
         phi > 0, the rescaled prediction.  Every chunk is walked segment by segment
-        (_guidance_segments); a replayed chunk walks the same segments."""
+        (_guidance_segments); a replayed chunk walks the same segments.
+        compose (_compose_args' tables; no interval, no rescale): every step on every path is the
+        composed step — y, vals, msk and guidance_scale are then not read."""
+        if compose is not None:
+            compose = tuple(c.to(x.device).contiguous() for c in compose)  # once: a loop's graphs hold their pointers
+            guidance_scale, interval, rescale = 0.0, None, 0.0
+        ckw = dict(compose=compose) if compose is not None else {}
         run_g = self._guided_run(self._mode_timesteps(mode), interval) if interval is not None else True
         rkw = dict(rescale=float(rescale)) if rescale > 0 else {}
 
@@ -975,7 +1154,8 @@ class Diffuser:
                 kkw["known"] = kn
         sched = (self.dpm_tables(mode[1], mode[2], x.device, start) if dpm
                  else self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None)
-        native = _native_kind(model) in (1, 2) and x.is_cuda and guidance_scale and guidance_scale > 0
+        native = _native_kind(model) in (1, 2) and x.is_cuda and (compose is not None or
+                                                                  (guidance_scale and guidance_scale > 0))
         bar = tqdm(total=T, desc="Sampling (cond+numeric)") if progress else None
         if native and self.noise_source == "device":
             # whole loop on the device: Philox noise, hipGraph replay, t decremented in-graph
@@ -996,7 +1176,8 @@ class Diffuser:
             def launch(p, k):  # k steps from position p; the position scalar runs on across the segments
                 for a, b, guided in segments(p, p - k):
                     nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0, tables,
-                                   a - b, seed=seed, use_graph=self.use_graph, **skw, **(rkw if guided else {}))
+                                   a - b, seed=seed, use_graph=self.use_graph, **skw, **(rkw if guided else {}),
+                                   **ckw)
 
             with torch.no_grad():
                 while done < T:
@@ -1034,7 +1215,7 @@ class Diffuser:
                 t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
                 guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
                 gs = guidance_scale if guided else 0.0
-                skw = dict(kkw, **rkw) if guided else kkw
+                skw = dict(kkw, **rkw, **ckw) if guided else kkw
                 if sched is None:  # (the unguided DDPM step: not the public branch, which mirrors an error)
                     x = self._denoise_cond(model, x, t, y, gs, null_label, vals, msk, **skw,
                                            **({} if guided else dict(unguided=True)))

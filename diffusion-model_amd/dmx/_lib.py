@@ -71,6 +71,15 @@ class Guidance(ctypes.Structure):
     _fields_ = [("rescale", ctypes.c_float)]
 
 
+DMX_COMPOSE_MAX = 4
+
+
+class Compose(ctypes.Structure):
+    """dmx_compose (include/dmx.h): the branch tables and weights of a composed-guidance step."""
+    _fields_ = [("K", ctypes.c_int), ("y", ctypes.c_void_p), ("vals", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("weight", ctypes.c_void_p)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -138,6 +147,12 @@ SIGNATURES = [
                                     ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
                                     _I, _I, _P]),
     ("dmx_cfg_rescale", _I, [_P, _P, ctypes.c_float, ctypes.c_float, _P, _P, _I, _I, _I, _I, _P]),
+    ("dmx_step_composed", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                               ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance), ctypes.POINTER(Compose), _P]),
+    ("dmx_sample_loop_composed", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched),
+                                      ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
+                                      ctypes.POINTER(Compose), _I, _I, _P]),
+    ("dmx_compose_eps", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("dmx_model_graph_captures", _I64, [_P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),

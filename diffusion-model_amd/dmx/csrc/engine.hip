@@ -1347,7 +1347,7 @@ static void reduce_norm(Run& R, const Deferred& d, NormParams np, int n_src_samp
   if (R.plan) return;
   np.gexact = gelu_exact_flag(R);
   const int kv = std::max(RN_MIN_KV, cdiv(np.HW * (np.C / 4), 1024));
-  const int n_out = np.n_src > 0 ? 2 * n_src_samples : n_src_samples;
+  const int n_out = np.n_src > 0 ? (np.n_fan > 0 ? np.n_fan : 2) * n_src_samples : n_src_samples;
   const int kvt = kv <= 2 ? 2 : kv <= 4 ? 4 : RN_MAXV;
   R.begin("reduce_norm_kernel<" + std::to_string(kvt) + ">", 0.0,
           4.0 * (double)n_src_samples * np.HW * np.C * (d.splits + (np.res ? 1 : 0)) +
@@ -1401,8 +1401,9 @@ static NormParams norm_params(const float* raw, const float2* rowpart, int nseg,
 // ResBlock (models/unet_cond.py:10-30):
 //   conv1 (+row stats) -> GN+GELU (materialised) -> conv2 (+row stats) -> GN [-> GELU(x + .)] [+ emb]
 // `in` is a plain NHWC tensor (or the NCHW network input for `inc`); it doubles as the residual.
-// n_out > N: the block is computed for N samples and its final GroupNorm (+ emb) writes
-// n_out samples, output n reading sample n % N (the CFG-shared prefix of the trunk).
+// n_out > N (a multiple of N): the block is computed for N samples and its final GroupNorm (+ emb)
+// writes n_out samples, output n reading sample n % N (the shared prefix of the trunk under CFG or
+// composed guidance).
 // in_h / in_l: `in` is available as f16 hi / lo planes (conv1 then reads those).
 // planes_out: the output only feeds the next ResBlock's conv1 — write it as hi / lo planes
 // (same bytes as fp32) when the split GEMM can use them; *wrote_planes reports the choice.
@@ -1482,6 +1483,7 @@ static float* resblock(Run& R, const ResW& w, const SrcDesc& in, int mode, int N
   n2.emb_stride = emb_stride;
   n2.emb_off = emb_off;
   n2.n_src = n_out > N ? N : 0;
+  n2.n_fan = n_out > N ? n_out / N : 0;  // (2: the CFG halves; K + 1: the branches of a composed step)
   const bool pout = planes_out && R.m->prec >= 1 && !R.m->debug && emb == nullptr && n_out == N && w.cout >= 64;
   if (wrote_planes != nullptr) *wrote_planes = pout;
   if (pout) {  // hi | lo halves of the output buffer, as a1
@@ -2444,10 +2446,15 @@ int dmx_step_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* d
 
 int dmx_step_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
                     const dmx_known_sched* known, const dmx_guidance* guidance, void* stream) {
-  return guarded([&] {
-    REQUIRE(guidance != nullptr, "null guidance");
-    sample_step(m, a, StepMode{ddim, dpm, known, guidance}, (hipStream_t)stream);
-  });
+  if (guidance == nullptr) return guarded([&] { REQUIRE(guidance != nullptr, "null guidance"); });
+  return dmx_step_composed(m, a, ddim, dpm, known, guidance, nullptr, stream);
+}
+
+// The general entries: every part optional.
+int dmx_step_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                      const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_compose* compose,
+                      void* stream) {
+  return guarded([&] { sample_step(m, a, StepMode{ddim, dpm, known, guidance, compose}, (hipStream_t)stream); });
 }
 
 int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
@@ -2482,9 +2489,28 @@ int dmx_sample_loop_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_s
 int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
                            const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
                            int steps, int use_graph, void* stream) {
+  if (guidance == nullptr) return guarded([&] { REQUIRE(guidance != nullptr, "null guidance"); });
+  return dmx_sample_loop_composed(m, a, ddim, dpm, known, guidance, nullptr, steps, use_graph, stream);
+}
+
+int dmx_sample_loop_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                             const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                             const dmx_compose* compose, int steps, int use_graph, void* stream) {
   return guarded([&] {
-    REQUIRE(guidance != nullptr, "null guidance");
-    sample_loop(m, a, StepMode{ddim, dpm, known, guidance}, steps, use_graph, (hipStream_t)stream);
+    sample_loop(m, a, StepMode{ddim, dpm, known, guidance, compose}, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_compose_eps(const float* e, const float* weight, int K, int n, int c, int h, int w, float* eps_out,
+                    void* stream) {
+  return guarded([&] {
+    REQUIRE(e && weight && eps_out, "null tensor");
+    REQUIRE(K >= 1 && K <= DMX_COMPOSE_MAX, "compose K must lie in [1, DMX_COMPOSE_MAX]");
+    REQUIRE(n >= 1 && c >= 1 && h >= 1 && w >= 1, "bad shape");
+    const int64_t chw = (int64_t)c * h * w;
+    REQUIRE((double)n * (double)chw < 549755813888.0, "too many elements");
+    launch_compose_eps(e, weight, K, n, chw, eps_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
   });
 }
 

@@ -1,0 +1,18 @@
+// dmx — composed-guidance kernels (compose.h) and their launchers.
+#include "compose.h"
+
+namespace dmx {
+
+void launch_compose_tail4(const StepTailParams& p, const ComposeParams& q, bool ddim, bool dpm, dim3 grid,
+                          hipStream_t st) {
+  if (dpm) compose_tail4_kernel<false, true><<<grid, 256, 0, st>>>(p, q);
+  else if (ddim) compose_tail4_kernel<true><<<grid, 256, 0, st>>>(p, q);
+  else compose_tail4_kernel<false><<<grid, 256, 0, st>>>(p, q);
+}
+
+void launch_compose_eps(const float* e, const float* weight, int K, int n, int64_t chw, float* eps, hipStream_t st) {
+  const int64_t blocks = ((int64_t)n * chw + 255) / 256;
+  compose_eps_kernel<<<(unsigned)blocks, 256, 0, st>>>(e, weight, K, n, chw, eps);
+}
+
+}  // namespace dmx

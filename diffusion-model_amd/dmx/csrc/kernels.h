@@ -273,6 +273,7 @@ struct NormParams {
   int gexact;                      // 1: GELU in the erf form (exact-fp32 mode), 0: gelu()
   const float* emb; int emb_stride; int emb_off;
   int n_src;                       // >0: raw / stats / res of output sample n come from sample n % n_src
+  int n_fan;                       // n_src > 0: outputs per source sample (0 => 2, the CFG halves)
   float* out;                      // fp32 output, or null when only the planes are written
   _Float16* out_h; _Float16* out_l;  // optional fp16 hi/lo planes (split-precision GEMM operand)
 };
@@ -390,7 +391,7 @@ static __global__ __launch_bounds__(256) void norm_kernel(const NormParams p) {
 // held in registers): sums the split slabs in split order (+ bias), reduces the sample's
 // (sum, sum of squares) in double in a fixed order, then applies exactly norm_kernel's
 // GroupNorm (+GELU | +residual GELU) (+emb) and writes fp32 and / or f16 hi/lo planes,
-// including the CFG fan-out (n_src > 0: outputs s and s + n_src both come from source s).
+// including the CFG fan-out (n_src > 0: outputs s, s + n_src, .. all come from source s).
 // Replaces splitk_reduce_kernel + norm_kernel (two launches, two HBM round trips of the
 // conv output) at 8x8 / 4x4 where both are launch-latency bound.
 constexpr int RN_MAXV = 8;  // float4 per thread
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(1024) void reduce_norm_kernel(const float* partial,
   }
   __syncthreads();
   const float2 st = st_s;
-  const int nout = p.n_src > 0 ? 2 : 1;
+  const int nout = p.n_src > 0 ? (p.n_fan > 0 ? p.n_fan : 2) : 1;
   for (int q = 0; q < nout; ++q) {
     const int n = s + q * (p.n_src > 0 ? p.n_src : 0);
     const size_t base = (size_t)n * per * 4;
@@ -711,92 +712,8 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* qkv, float*
   }
 }
 
-// ---------------------------------------------------------------------------
-// Philox4x32-10 counter RNG + Box-Muller -> 4 N(0,1) per counter (perf mode K8).
-// ---------------------------------------------------------------------------
-DMX_DEV uint4 philox4x32(uint4 ctr, uint2 key) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-    key.x += 0x9E3779B9u;
-    key.y += 0xBB67AE85u;
-  }
-  return ctr;
-}
-
-DMX_DEV floatx4 normal4(uint64_t seed, uint64_t stream, uint64_t index) {
-  const uint4 r = philox4x32(make_uint4((uint32_t)index, (uint32_t)(index >> 32), (uint32_t)stream,
-                                        (uint32_t)(stream >> 32)),
-                             make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-  const float k = 2.3283064365386963e-10f;  // 2^-32
-  const float u1 = ((float)r.x + 0.5f) * k, u2 = ((float)r.y + 0.5f) * k;
-  const float u3 = ((float)r.z + 0.5f) * k, u4 = ((float)r.w + 0.5f) * k;
-  const float a = sqrtf(-2.0f * logf(u1)), b = sqrtf(-2.0f * logf(u3));
-  const float t1 = 6.283185307179586f * u2, t2 = 6.283185307179586f * u4;
-  return floatx4{a * cosf(t1), a * sinf(t1), b * cosf(t2), b * sinf(t2)};
-}
-
-// ---------------------------------------------------------------------------
-// K1/K6: out head (conv1x1 64->Co + bias) fused with the CFG mix and the DDPM
-// posterior step.  Reference: unet_cond.py:153 (out), diff.py:151 (CFG),
-// diff.py:141-144,158-162 (update).  The update arithmetic is performed with one
-// rounding per reference op, in the reference's op order, so given the same eps it
-// is bit-identical to torch-CPU:
-//   eps = eu + g*(ec - eu); mu = (x - c1[t]*eps) / c2[t]; x' = mu + noise*sd[t]
-// with c1 = (1-a)/sqrt(1-ab), c2 = sqrt(a), sd = sqrt((1-a)(1-ab_prev)/(1-ab))
-// tabulated on the host by torch.  noise = 0 where t == 1.
-// feat: [2B or B][H][W][64] NHWC; x, x_out, noise: NCHW [B][Co][H][W].
-// ---------------------------------------------------------------------------
-struct StepTailParams {
-  const float* feat; const float* w; const float* b;  // w: [Co][64]
-  int Co, B, HW, cfg;                                 // cfg: feat holds [uncond B | cond B]
-  float guidance;
-  const float* eps_u; const float* eps_c;             // alternative: precomputed eps (NCHW), feat null
-  const float* x; float* x_out;
-  const int64_t* t; int t_stride; int tmax;
-  const float* c1; const float* c2; const float* sd;  // [tmax], index t-1
-  const float* noise;                                 // NCHW or null => Philox
-  uint64_t seed; int64_t sample_offset;
-  int* range_flag;                                    // set to 1 when eps is not finite (or null)
-  // strided (DDIM) form, the <true> instantiations: t holds positions in [1, tmax], row p - 1 of
-  // the tables belongs to position p and t_map[p - 1] is its network timestep (the noise key)
-  const int64_t* t_map;
-  const float* k_e; const float* k_a; const float* k_s; const float* k_d; const float* k_n;
-  // DPM-Solver++(2M) form, the <false, true> instantiations: positions and t_map / k_e / k_a as in
-  // the DDIM form, k_x / k_c / k_p per position, hist (x's shape) read where k_p != 0 and written
-  const float* k_x; const float* k_c; const float* k_p;
-  float* hist;
-};
-
-DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float nz) {
-  const float mu = rnd(x - rnd(c1 * eps)) / c2;
-  return mu + rnd(nz * sd);
-}
-// Strided DDIM update (Song et al. 2021, eq. 12) from position p (timestep t) to p - 1 (timestep s):
-//   x0 = (x - k_e*eps) / k_a;  x' = k_s*x0 + k_d*eps + k_n*nz
-// with k_e = sqrt(1-ab[t]), k_a = sqrt(ab[t]), k_s = sqrt(ab[s]), k_n = sigma, k_d = sqrt(1-ab[s]-sigma^2)
-// tabulated per position on the host; one rounding per op in torch's evaluation order.
-DMX_DEV float ddim_elem(float x, float eps, float ke, float ka, float ks, float kd, float kn, float nz) {
-  const float x0 = rnd(x - rnd(ke * eps)) / ka;
-  return rnd(rnd(ks * x0) + rnd(kd * eps)) + rnd(kn * nz);
-}
-// DPM-Solver++(2M) update (Lu et al. 2022, Alg. 2, data prediction) from position p (timestep t) to
-// p - 1 (timestep s), the previous step having come from u:
-//   x0 = (x - k_e*eps) / k_a;  x' = k_x*x + k_c*x0 + k_p*hist;  hist <- x0
-// with k_x = sigma_s/sigma_t, m = alpha_s - k_x*alpha_t, r = (lam_t - lam_u)/(lam_s - lam_t),
-// k_c = m (1 + 1/(2r)), k_p = -m/(2r) (first-order rows: k_c = m, k_p = 0) tabulated per position on
-// the host; one rounding per op.  hist is read only where k_p != 0: the first step of a schedule may
-// start from an uninitialised buffer.  Each element of hist is read and written by the same lane.
-DMX_DEV float dpm_elem(float x, float eps, float ke, float ka, float kx, float kc, float kp, float* hist) {
-  const float x0 = rnd(x - rnd(ke * eps)) / ka;
-  const float y = rnd(kx * x) + rnd(kc * x0);
-  const float out = kp != 0.f ? y + rnd(kp * *hist) : y;
-  *hist = x0;
-  return out;
-}
-
+// (Philox noise, StepTailParams and the ddpm / ddim / dpm element updates: tail_math.h, shared with
+// the composed tail of compose.h.)
 template <bool DDIM, bool DPM = false>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
   const int pix = blockIdx.x * 256 + threadIdx.x;

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "igemm.h"
 #include "igemm_x3.h"
+#include "tail_math.h"
 #include "tokmlp.h"
 
 namespace dmx {
@@ -73,5 +74,16 @@ void launch_cfg_scale(float* eg, const double* part, int nb, int pixb, int Co, i
 // standalone: one block per sample over its `total` = c*h*w elements
 void launch_cfg_rescale(const float* eu, const float* ec, float g, float phi, float* eps, float* ratio_out, int n,
                         int64_t total, hipStream_t st);
+// Composed guidance (compose.h), k_compose.hip.  K extra branches over the base branch; weight [K][B].
+struct ComposeParams {
+  int K;
+  const float* weight;
+};
+// the step tail over a branch-major feature map [(K+1) B][HW][64] (p as the plain Co = 4 head tail takes
+// it; p.cfg / p.guidance are not read); grid (cdiv(HW, 16), B)
+void launch_compose_tail4(const StepTailParams& p, const ComposeParams& q, bool ddim, bool dpm, dim3 grid,
+                          hipStream_t st);
+// the mix alone: e [(K+1)][n][chw], weight [K][n] -> eps [n][chw]; n * chw < 2^39
+void launch_compose_eps(const float* e, const float* weight, int K, int n, int64_t chw, float* eps, hipStream_t st);
 
 }  // namespace dmx

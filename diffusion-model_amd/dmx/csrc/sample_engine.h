@@ -55,9 +55,13 @@ static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
 }
 
 // The tail's launch: the instance of the update rule; head4 = the network head path with Co = 4
-// (16 pixels per block), else one pixel per thread.
-static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st) {
-  if (!head4) {
+// (16 pixels per block), else one pixel per thread; comp: the composed head4 tail (launch.h).
+static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st,
+                             const ComposeParams* comp = nullptr) {
+  if (comp != nullptr) {
+    if (!head4) throw Error(DMX_E_INTERNAL, "the composed tail is the Co = 4 head tail");
+    launch_compose_tail4(p, *comp, rule == Rule::DDIM, rule == Rule::DPM, grid, st);
+  } else if (!head4) {
     if (rule == Rule::DPM) step_tail_kernel<false, true><<<grid, 256, 0, st>>>(p);
     else if (rule == Rule::DDIM) step_tail_kernel<true><<<grid, 256, 0, st>>>(p);
     else step_tail_kernel<false><<<grid, 256, 0, st>>>(p);
@@ -79,14 +83,24 @@ struct GraphStep {
 // (guidance.h, through launch.h) whose eg and block partials come from the arena, in the dry run as
 // in the real one; they read the position scalar the tail reads, through step_tail_kernel.  The
 // known-region blend follows the tail as a launch of its own, on a.x_out in place, at the position
-// the tail read.
+// the tail read.  A composed step (mode.comp) runs K + 1 branch-major rows through the trunk and the
+// composed tail; with Co < 4 the head, the mix and the update are three launches whose predictions
+// come from the arena.
 static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, GraphStep gs = {}) {
   dmx_model* m = R.m;
-  const bool cfg = m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
+  const dmx_compose* comp = mode.comp;
+  const bool cfg = comp == nullptr && m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
   const bool resc = mode.rescale() > 0.f;
   const Rule rule = mode.rule();
-  const int N = cfg ? 2 * a.n : a.n;
+  const int N = comp != nullptr ? (comp->K + 1) * a.n : cfg ? 2 * a.n : a.n;
   FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
+  if (comp != nullptr) {  // every row of the forward has its own label and condition row
+    in.y = comp->y;
+    in.y_null = 0;
+    in.vals = comp->vals;
+    in.mask = comp->mask;
+    in.cond_rows = N;
+  }
   in.t_next = gs.t_next;
   in.cond_cached = gs.cond_cached;
   if (rule != Rule::DDPM) {
@@ -98,6 +112,9 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   const int nb = cdiv(a.h * a.w, pixb);
   float* eg = resc ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
   double* part = resc ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
+  const bool comp3 = comp != nullptr && m->in_ch != 4;  // head, mix, update as three launches
+  float* eall = comp3 ? R.ws.get<float>((size_t)N * m->in_ch * a.h * a.w) : nullptr;
+  float* emix = comp3 ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
   if (R.plan) return;
   StepTailParams p;
   std::memset(&p, 0, sizeof(p));
@@ -130,7 +147,29 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   R.layer = rule == Rule::DPM ? "out+cfg+dpm" : rule == Rule::DDIM ? "out+cfg+ddim" : "out+cfg+ddpm";
   const double el = (double)a.n * p.Co * p.HW;
   const double head_flops = 2.0 * N * p.HW * 64.0 * p.Co, head_bytes = 4.0 * ((double)N * p.HW * 64 + 3.0 * el);
-  if (resc) {
+  if (comp != nullptr) {
+    const ComposeParams cq{comp->K, comp->weight};
+    p.cfg = 0;
+    p.guidance = 0.f;
+    if (!comp3) {
+      R.begin("compose_tail4_kernel", head_flops, head_bytes);
+      launch_step_tail(p, rule, true, dim3(cdiv(p.HW, 16), a.n), R.st, &cq);
+    } else {
+      R.begin("out_head_kernel", head_flops, 4.0 * ((double)N * p.HW * 64 + (double)N * p.Co * p.HW));
+      out_head_kernel<<<dim3(cdiv(p.HW, 256), N), 256, 0, R.st>>>(feat, m->out_w, m->out_b, eall, p.Co, p.HW,
+                                                                 m->range_flag);
+      R.end();
+      HIPCHK(hipGetLastError());
+      R.begin("compose_eps_kernel", 3.0 * comp->K * el, 4.0 * (comp->K + 2.0) * el);
+      launch_compose_eps(eall, comp->weight, comp->K, a.n, (int64_t)p.Co * p.HW, emix, R.st);
+      R.end();
+      HIPCHK(hipGetLastError());
+      p.feat = nullptr;
+      p.eps_u = emix;
+      R.begin("step_tail_kernel", 8.0 * el, 4.0 * 4.0 * el);
+      launch_step_tail(p, rule, false, dim3(cdiv(p.HW, 256), a.n), R.st);
+    }
+  } else if (resc) {
     R.begin(p.Co == 4 ? "cfg_stats4_kernel" : "cfg_stats_kernel", head_flops, 4.0 * ((double)N * p.HW * 64 + el));
     CfgHeadParams hp{p.feat, p.w, p.b, p.Co, p.B, p.HW, p.guidance, p.range_flag};
     launch_cfg_stats(hp, eg, part, nb, R.st);
@@ -193,6 +232,17 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   REQUIRE(m != nullptr, "null model");
   REQUIRE(a != nullptr, "null step args");
   const bool cfg = m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr;
+  if (mode.comp != nullptr) {
+    const dmx_compose& c = *mode.comp;
+    REQUIRE(c.K >= 1 && c.K <= DMX_COMPOSE_MAX, "compose K must lie in [1, DMX_COMPOSE_MAX]");
+    REQUIRE(c.y != nullptr && c.weight != nullptr, "compose needs y and weight");
+    REQUIRE((c.vals == nullptr) == (c.mask == nullptr), "compose vals and mask must be given together");
+    REQUIRE(m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND, "compose needs a conditional model");
+    REQUIRE(mode.rescale() == 0.f, "composed steps take no guidance rescale");
+    REQUIRE(a->n <= 65535, "composed steps take at most 65535 samples");
+    const void* xo = a->x_out;
+    REQUIRE(c.y != xo && c.vals != xo && c.mask != xo && c.weight != xo, "compose tables must not alias x_out");
+  }
   if (mode.gd != nullptr) {
     REQUIRE(mode.gd->rescale >= 0.f && mode.gd->rescale <= 1.f, "guidance rescale must lie in [0, 1]");
     if (mode.rescale() > 0.f) {
@@ -219,8 +269,8 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
     REQUIRE(a->T >= 1, "T must be >= 1");
   }
   REQUIRE(m->in_ch <= 4, "in_ch must be <= 4");
-  if (m->kind != DMX_UNET && a->guidance > 0.f) REQUIRE(a->y != nullptr, "CFG needs y");
-  if (m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND)
+  if (mode.comp == nullptr && m->kind != DMX_UNET && a->guidance > 0.f) REQUIRE(a->y != nullptr, "CFG needs y");
+  if (mode.comp == nullptr && (m->kind == DMX_UNET_COND_GEOM || m->kind == DMX_UNET_COND))
     REQUIRE((a->vals == nullptr) == (a->mask == nullptr), "vals and mask must be given together");
   if (for_loop) {
     REQUIRE(a->x_in == a->x_out, "sample loop runs in place (x_in == x_out)");

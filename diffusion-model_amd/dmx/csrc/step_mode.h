@@ -16,6 +16,8 @@ struct StepMode {
   const dmx_dpm_sched* dpm = nullptr;      // the same with the DPM-Solver++(2M) update (at most one of ddim / dpm)
   const dmx_known_sched* known = nullptr;  // the known-region blend follows the tail
   const dmx_guidance* gd = nullptr;        // guidance controls beyond the scale
+  const dmx_compose* comp = nullptr;       // composed guidance: K + 1 branches; a.y / vals / mask / guidance /
+                                           // null_label are not read
 
   Rule rule() const { return dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM; }
   // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
@@ -33,13 +35,15 @@ struct GraphKey {
   dmx_dpm_sched dpm;     // DPM-Solver++ loops: tables, history buffer and S (all zero otherwise)
   dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
   dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
+  dmx_compose comp;      // composed loops: K and the four tables (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
 
 // The key of a loop: everything its graphs hold.  The step args enter as the caller's bytes; the
 // optional structs enter member by member, so their padding stays zero.  A validated schedule has
-// S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart.
+// S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart;
+// a validated composition has K >= 1, which keeps composed keys from plain ones.
 inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen) {
   GraphKey key;
   std::memset(&key, 0, sizeof(key));
@@ -76,6 +80,17 @@ inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int
     key.known.S = mode.known->S;
   }
   key.gd.rescale = mode.rescale();
+  if (mode.comp != nullptr) {  // the branch tables stand where these would
+    key.a.y = nullptr;
+    key.a.vals = key.a.mask = nullptr;
+    key.a.guidance = 0.f;
+    key.a.null_label = 0;
+    key.comp.K = mode.comp->K;
+    key.comp.y = mode.comp->y;
+    key.comp.vals = mode.comp->vals;
+    key.comp.mask = mode.comp->mask;
+    key.comp.weight = mode.comp->weight;
+  }
   key.table_gen = table_gen;
   return key;
 }

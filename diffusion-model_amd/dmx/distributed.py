@@ -172,7 +172,7 @@ class ShardedCondSampler:
                steps: Optional[int] = None, eta: float = 0.0, spacing: Optional[str] = None,
                init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                strength: Optional[float] = None, guidance_interval=None,
-               guidance_rescale: float = 0.0) -> Optional[torch.Tensor]:
+               guidance_rescale: float = 0.0, base="null", also=None) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -204,11 +204,18 @@ class ShardedCondSampler:
 
         guidance_interval / guidance_rescale as in Diffuser.sample_latent_cond: every rank cuts each
         chunk into the same unguided / guided segments (they follow from the schedule alone), and the
-        rescale's statistics are per sample, hence shard-local (no collective)."""
+        rescale's statistics are per sample, hence shard-local (no collective).
+
+        base / also and a per-sample guidance_scale as in Diffuser.sample_latent_cond (composed guidance),
+        given for the global batch: every rank takes its columns [:, s:e] of the branch tables, and a
+        sample's result does not depend on the shard it sits in beyond the batch class."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
-        interval, phi = d._guidance_args(guidance_scale, guidance_interval, guidance_rescale, d.num_timesteps)
+        composed = (not (isinstance(base, str) and base == "null")) or bool(also) or d._per_sample(guidance_scale)
+        interval, phi = d._guidance_args(None if composed else guidance_scale,
+                                         None if composed else guidance_interval,
+                                         0.0 if composed else guidance_rescale, d.num_timesteps)
         run_g = d._guided_run(d._mode_timesteps(mode), interval) if interval is not None else True
         rkw = dict(rescale=phi) if phi > 0 else {}  # (with both keywords at their defaults every call stays as it was)
 
@@ -223,7 +230,13 @@ class ShardedCondSampler:
         B = len(y_list)
         dev = torch.device(d.device)
         vals, msk = d._build_cond(y_list, cond, cond_mask, None, None, dev)
+        compose = d._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval, guidance_rescale,
+                                  null_label, None, None, dev)
         s, e = shard_range(B, ws, rank)
+        ckw = {}
+        if compose is not None:  # this shard's rows of every branch, converted once (the graphs hold their pointers)
+            ckw["compose"] = tuple(c[:, s:e].contiguous() for c in compose)
+            guidance_scale = 0.0
         y = torch.tensor(y_list[s:e], device=dev, dtype=torch.long)
         v, m = vals[s:e].float().contiguous(), msk[s:e].float().contiguous()
         known = d._known_inputs(init_latent, mask, strength, B, z_shape)
@@ -269,7 +282,7 @@ class ShardedCondSampler:
                     for a, b, guided in segments(i_from, i_to):  # the position scalar runs on across them
                         nm.sample_loop(xs, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
                                        tables, a - b, seed=seed, sample_offset=s, use_graph=d.use_graph, **skw,
-                                       **(rkw if guided else {}))
+                                       **(rkw if guided else {}), **ckw)
                 return xs
         else:
             def run(i_from, i_to, xs):
@@ -287,7 +300,7 @@ class ShardedCondSampler:
                             tt = torch.full((xs.shape[0],), i, dtype=torch.long, device=dev)
                             guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
                             nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
-                                    tables, noise, **skw, **(rkw if guided else {}))
+                                    tables, noise, **skw, **(rkw if guided else {}), **ckw)
                             xs = out
                 finally:
                     if pf is not None:

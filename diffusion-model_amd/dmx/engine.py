@@ -310,8 +310,38 @@ class NativeModel:
         parts = (None if dpm else sc, sc if dpm else None, kn, gd if gd is not None else Guidance(0.0))
         return tuple(None if s is None else ctypes.byref(s) for s in parts), tables
 
+    def _compose(self, x, compose, rescale):
+        """The C view of compose = (y_rows, vals_rows, mask_rows, weights) for a step on x (n samples):
+        y_rows (K+1, n) int64, row 0 the base branch; vals_rows / mask_rows (K+1, n, 12) or both None;
+        weights (K, n) fp32 -> (dmx_compose, the converted tensors, which the caller keeps alive).
+        Shapes, K and finiteness of nothing are read back here: the library checks K and the pointers."""
+        if float(rescale) > 0:
+            raise ValueError("a composed step takes no guidance rescale")
+        y_rows, vals_rows, mask_rows, weights = compose
+        dev, n = x.device, x.shape[0]
+        y_c = torch.as_tensor(y_rows).to(device=dev, dtype=torch.long).contiguous()
+        w_c = torch.as_tensor(weights).to(device=dev, dtype=torch.float32).contiguous()
+        if y_c.dim() != 2 or y_c.shape[1] != n or not 2 <= y_c.shape[0] <= _lib.DMX_COMPOSE_MAX + 1:
+            raise ValueError(f"compose y_rows must be (K+1, {n}) with 1 <= K <= {_lib.DMX_COMPOSE_MAX} "
+                             f"(got {tuple(y_c.shape)})")
+        K = y_c.shape[0] - 1
+        if tuple(w_c.shape) != (K, n):
+            raise ValueError(f"compose weights must be ({K}, {n}) (got {tuple(w_c.shape)})")
+        if (vals_rows is None) != (mask_rows is None):
+            raise ValueError("compose vals_rows and mask_rows must be given together")
+        v_c = m_c = None
+        if vals_rows is not None:
+            v_c = torch.as_tensor(vals_rows).to(device=dev, dtype=torch.float32).contiguous()
+            m_c = torch.as_tensor(mask_rows).to(device=dev, dtype=torch.float32).contiguous()
+            for r, nm in ((v_c, "vals_rows"), (m_c, "mask_rows")):
+                if tuple(r.shape) != (K + 1, n, 12):
+                    raise ValueError(f"compose {nm} must be ({K + 1}, {n}, 12) (got {tuple(r.shape)})")
+        comp = _lib.Compose(K, y_c.data_ptr(), v_c.data_ptr() if v_c is not None else None,
+                            m_c.data_ptr() if m_c is not None else None, w_c.data_ptr())
+        return comp, (y_c, v_c, m_c, w_c)
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0):
+             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -322,16 +352,27 @@ class NativeModel:
         (the DDPM step: tau = 1..T): the known-region blend follows the step on x_out (known_blend).
         rescale = phi in (0, 1] (a CFG step only; include/dmx.h dmx_guidance): the guided prediction is
         scaled per sample to the conditional one's standard deviation before the update.  0 is the
-        plain step, launched exactly as without the keyword."""
+        plain step, launched exactly as without the keyword.
+        compose = (y_rows, vals_rows, mask_rows, weights) (include/dmx.h dmx_compose; _compose): composed
+        guidance over K + 1 branches in one (K+1) n forward — eps = e_0 + sum_k w_k (e_k - e_0).  y,
+        null_label, vals, mask and guidance are then not read; rescale must be 0."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        if compose is not None:
+            comp, self._live_comp = self._compose(x_in, compose, rescale)
+            y = vals = mask = None
+            null_label, guidance, rescale = 0, 0.0, 0.0
         mode, tables = self._mode(x_in, sched, hist, known, rescale, guidance, y, tables)
         t, y, vals, mask, noise = self._norm_inputs(x_in, t, y, vals, mask, noise)
         a = self._args(x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
                        sample_offset)
         with torch.cuda.device(x_in.device):
-            check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a), *mode,
-                                           ctypes.c_void_p(_stream(x_in.device))))
+            if compose is not None:
+                check(self.lib.dmx_step_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
+                                                 ctypes.c_void_p(_stream(x_in.device))))
+            else:
+                check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a), *mode,
+                                               ctypes.c_void_p(_stream(x_in.device))))
 
     def step_profile(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
                      t_stride=1, cap=1024):
@@ -353,7 +394,7 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0):
+                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -366,8 +407,16 @@ class NativeModel:
         A loop entering below position S starts from known_blend's start latent.
         rescale = phi in (0, 1] as in step(): every step of the loop is a rescaled CFG step.
         The model keeps the captured graphs of the last few distinct loops (graph_captures counts the
-        captures), so alternating guided, unguided and rescaled loops replay instead of recapturing."""
+        captures), so alternating guided, unguided and rescaled loops replay instead of recapturing.
+        compose as in step(): every step of the loop is a composed step.  The captured graphs hold the
+        pointers of the converted tables: pass contiguous int64 / fp32 device tensors to replay them."""
         _check_state(x, "x")
+        comp_live = ()
+        if compose is not None:
+            comp, comp_live = self._compose(x, compose, rescale)
+            self._live_comp = comp_live
+            y = vals = mask = None
+            null_label, guidance, rescale = 0, 0.0, 0.0
         mode, tables = self._mode(x, sched, hist, known, rescale, guidance, y, tables)
         if t_dev.dtype != torch.long or not t_dev.is_contiguous() or t_dev.device != x.device:
             raise ValueError("sample_loop: t_dev must be a contiguous int64 device scalar on x's device "
@@ -378,12 +427,18 @@ class NativeModel:
         side = self.side_stream()
         side.wait_stream(cur)
         live = (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables) + tuple(known or ())
+        live += tuple(comp_live)
         for keep in live:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a), *mode, int(steps), int(use_graph),
-                                                  ctypes.c_void_p(side.cuda_stream)))
+            if compose is not None:
+                check(self.lib.dmx_sample_loop_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
+                                                        int(steps), int(use_graph),
+                                                        ctypes.c_void_p(side.cuda_stream)))
+            else:
+                check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a), *mode, int(steps),
+                                                      int(use_graph), ctypes.c_void_p(side.cuda_stream)))
         cur.wait_stream(side)
 
     # ---- VAE -----------------------------------------------------------------------------
@@ -499,6 +554,33 @@ def cfg_rescale(eu, ec, guidance, phi):
         check(lib.dmx_cfg_rescale(_ptr(eu_c), _ptr(ec_c), float(guidance), phi, _ptr(eps), _ptr(r), n, c, h, w,
                                   ctypes.c_void_p(_stream(dev))))
     return eps, r
+
+
+def compose_eps(e_list, weights):
+    """Standalone composed-guidance mix (include/dmx.h dmx_compose_eps) for duck-typed models -> eps:
+    e_list = [e_0, e_1, .., e_K] (or one stacked (K+1,n,c,h,w) tensor), e_0 the base branch's prediction,
+    each (n,c,h,w) on the GPU with any c, h, w >= 1; weights (K, n) or (K,) finite floats.
+        d_k = e_k - e_0;  s = w_1 d_1;  s = s + w_k d_k (k = 2..K);  eps = e_0 + s
+    one fp32 rounding per operation.  Operands stay bound to locals for the duration of the launch."""
+    lib = _lib.load()
+    e = e_list if isinstance(e_list, torch.Tensor) else torch.stack([t.to(dtype=torch.float32) for t in e_list])
+    require_cuda(e, "e_list")
+    dev = e.device
+    e_c = e.to(dtype=torch.float32).contiguous()
+    if e_c.dim() != 5 or not 2 <= e_c.shape[0] <= _lib.DMX_COMPOSE_MAX + 1 or min(e_c.shape) < 1:
+        raise ValueError(f"e_list must hold 2 .. {_lib.DMX_COMPOSE_MAX + 1} equal (n,c,h,w) tensors "
+                         f"(got {tuple(e_c.shape)})")
+    K, n, c, h, w = e_c.shape[0] - 1, *e_c.shape[1:]
+    w_c = torch.as_tensor(weights, dtype=torch.float32).to(device=dev)
+    if w_c.dim() == 1:
+        w_c = w_c[:, None].expand(-1, n)
+    w_c = w_c.contiguous()
+    if tuple(w_c.shape) != (K, n):
+        raise ValueError(f"weights must be ({K}, {n}) or ({K},) (got {tuple(w_c.shape)})")
+    eps = torch.empty((n, c, h, w), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(lib.dmx_compose_eps(_ptr(e_c), _ptr(w_c), K, n, c, h, w, _ptr(eps), ctypes.c_void_p(_stream(dev))))
+    return eps
 
 
 def _update_operands(x, eu, ec, noise, pos, pos_name):

@@ -54,16 +54,21 @@ class EntityCsvSampler:
     def sample(self, csv_path: str, count: Optional[int] = None, start: int = 0, guidance_scale: float = 3.0,
                sampler: str = "ddpm", steps: Optional[int] = None, eta: float = 0.0,
                spacing: Optional[str] = None, init_latent=None, mask=None, strength: Optional[float] = None,
-               guidance_interval=None, guidance_rescale: float = 0.0):
+               guidance_interval=None, guidance_rescale: float = 0.0, base: str = "null"):
         """entityCsvSampler.py:50-80; sampler / steps / eta / spacing, init_latent / mask / strength and
-        guidance_interval / guidance_rescale as in Diffuser.sample_latent_cond."""
+        guidance_interval / guidance_rescale as in Diffuser.sample_latent_cond.  base = "null" (the
+        default) or "dropped": the base branch of the guidance, as there (a condition spec as the base
+        and `also=` are not offered here)."""
+        if base not in ("null", "dropped"):
+            raise ValueError(f'base must be "null" or "dropped" (got {base!r})')
         vals, cond_mask = self._rows(csv_path, count, start)  # (`mask` is the latent mask of the keywords)
         return self.diffuser.sample_latent_cond(model=self.model, class_counts=(self.class_id, vals.shape[0]),
                                                 vae=self.vae, guidance_scale=guidance_scale, cond=vals,
                                                 cond_mask=cond_mask, sampler=sampler, steps=steps, eta=eta,
                                                 spacing=spacing, init_latent=init_latent, mask=mask,
                                                 strength=strength, guidance_interval=guidance_interval,
-                                                guidance_rescale=guidance_rescale)
+                                                guidance_rescale=guidance_rescale,
+                                                **(dict(base=base) if base != "null" else {}))
 
     def load_cond(self, csv_path: str, count: Optional[int] = None, start: int = 0):
         """entityCsvSampler.py:82-98."""

@@ -289,8 +289,51 @@ int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_
 int dmx_cfg_rescale(const float* eu, const float* ec, float guidance, float rescale, float* eps_out,
                     float* ratio_out, int n, int c, int h, int w, void* stream);
 
+/* ---- Composed guidance: K weighted condition branches over a chosen base branch (Liu et al. 2022,
+ * "Compositional visual generation with composable diffusion models"; no reference counterpart).
+ * Branch 0 is the base, branches 1..K the conditions, 1 <= K <= DMX_COMPOSE_MAX.  Branch k of sample
+ * i has the label y[k][i], the numeric row vals[k][i][:] and the mask row mask[k][i][:] (width 12);
+ * the step runs one (K+1)*n-sample forward whose row k*n + i is branch k of sample i (x and t are
+ * shared by the branches, and so is the part of the network before the first embedding add).  With
+ * e_k the prediction of branch k and w_k[i] = weight[k-1][i] (finite fp32; zero and negative legal)
+ *   d_k = e_k - e_0;  s = w_1*d_1;  s = s + w_k*d_k (k = 2..K);  eps = e_0 + s
+ * one IEEE rounding per operation in that order, then the DDPM / DDIM / DPM update and, if asked
+ * for, the known-region blend, both as in every step.  K = 1 with a constant weight g, base label
+ * null_label and the call's vals / mask is bit for bit the plain CFG step; a weight per sample is
+ * a per-sample guidance scale; a base row (null label, vals = mask = 0) is the input the model's
+ * joint condition dropout trained as unconditional; any other base row is a negative condition.
+ * A non-finite eps raises the range flag.  All members are device pointers owned by the caller;
+ * none may alias the x the step writes. */
+#define DMX_COMPOSE_MAX 4
+typedef struct dmx_compose {
+  int K;               /* 1 .. DMX_COMPOSE_MAX */
+  const int64_t* y;    /* [(K+1)][n], row 0 = base branch */
+  const float* vals;   /* [(K+1)][n][12], or NULL together with mask */
+  const float* mask;
+  const float* weight; /* [K][n] */
+} dmx_compose;
+
+/* The general step and loop entries: at most one of ddim / dpm is non-NULL (both NULL: the DDPM
+ * step); known, guidance and compose may each be NULL.  With compose == NULL they are
+ * dmx_step_guided / dmx_sample_loop_guided (which forward here), guidance == NULL standing for
+ * rescale 0.  With compose given the model must be conditional, a->n <= 65535, guidance must be
+ * NULL or have rescale == 0, and a->y, a->vals, a->mask, a->guidance and a->null_label are not
+ * read.  A composed loop's graphs belong to its dmx_compose (K and the four pointers) as they
+ * belong to a schedule: plain loops never replay them, nor the reverse. */
+int dmx_step_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                      const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_compose* compose,
+                      void* stream);
+int dmx_sample_loop_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                             const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                             const dmx_compose* compose, int steps, int use_graph, void* stream);
+/* The mix alone, for duck-typed foreign models (no model, no arena): e [(K+1)][n][c][h][w] (NCHW per
+ * branch, branch-major), weight [K][n], eps_out (n,c,h,w) with any c, h, w >= 1; eps_out may alias a
+ * branch of e.  Feed eps_out to dmx_*_update with ec = NULL. */
+int dmx_compose_eps(const float* e, const float* weight, int K, int n, int c, int h, int w, float* eps_out,
+                    void* stream);
+
 /* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
- * distinct loops (distinct dmx_step_args / schedule / known region / guidance / time-table
+ * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / time-table
  * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
  * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
  * after another, inside the model's one workspace; whatever reallocates or invalidates it (a

@@ -1,7 +1,8 @@
 """Few-step sampling (strided DDIM, DPM-Solver++(2M)) against the full DDPM walk on one MI355X: prints
 one JSON line.
 
-  python tools/sampler_bench.py [--rounds 5] [--groups loops,known_loops,guidance_loops,end_to_end]
+  python tools/sampler_bench.py [--rounds 5]
+      [--groups loops,known_loops,guidance_loops,composed_loops,end_to_end]
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -19,6 +20,11 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    The guidance controls likewise (legs dpmpp_2m_a, unguided, rescaled, dpmpp_2m_b): the unguided loop
    (guidance 0 with y given: one B-sample forward per step) and the rescaled CFG loop (phi = 0.7: three
    tail launches instead of one), with the unguided / plain ratio.
+   Composed guidance likewise (legs dpmpp_2m_a, composed_k1, composed_k2, composed_k4, unbatched_k2,
+   dpmpp_2m_b): the composed loop with K = 1 (the plain step's rows), K = 2 and K = 4 branches over the
+   base, each as a ratio to the plain step, and what a user would run without the batched step — three
+   B-sample forwards, compose_eps and the standalone update per step, eager — with the model's workspace
+   after the K = 2 and the K = 4 loops.
 2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
    (ddpm, T = 1000), (ddim, S = 50, eta = 0) and (dpmpp_2m, S = 20, log-SNR spacing): the first call (it captures the graphs) and the best of
    the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
@@ -194,6 +200,92 @@ def guidance_legs(nm, d, dev, rounds):
             "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}}
 
 
+def composed_legs(nm, d, dev, rounds):
+    """The DPM-Solver++(2M) loop plain (CFG) and composed with K = 1, 2, 4 branches over the base, and the
+    unbatched K = 2 step (K + 1 forwards, compose_eps, dpm_update): same schedule, buffers and method as
+    loop_legs.  Branch 0 is the null label with the call's rows, branch 1 the call's condition; further
+    branches cycle the labels and reuse the rows; every weight is GUIDANCE."""
+    from dmx import engine
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
+
+    def tables(K):
+        ys = [torch.zeros_like(y), y] + [1 + (y + k) % 3 for k in range(K - 1)]
+        return (torch.stack(ys).contiguous(), torch.stack([vals] * (K + 1)).contiguous(),
+                torch.stack([mask] * (K + 1)).contiguous(), torch.full((K, B), GUIDANCE, device=dev))
+
+    comps = {K: tables(K) for K in (1, 2, 4)}
+
+    def leg(K):  # K = 0: the plain CFG loop
+        kw = dict(sched=sched, hist=hist, **(dict(compose=comps[K]) if K else {}))
+        a = (None, 0, None, None, 0.0) if K else (y, 0, vals, mask, GUIDANCE)
+        x.copy_(x0)
+        t_dev.fill_(S)
+        nm.sample_loop(x, t_dev, *a, None, WARM, **kw)  # captures this loop's graphs once
+        x.copy_(x0)
+        t_dev.fill_(S)
+        torch.cuda.synchronize()
+        e_0, e_1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_0.record()
+        nm.sample_loop(x, t_dev, *a, None, TIMED, **kw)
+        e_1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == S - TIMED and bool(torch.isfinite(x).all())
+        return e_0.elapsed_time(e_1) / TIMED
+
+    def unbatched(K):
+        y_rows, v_rows, m_rows, w = comps[K]
+        xx = x0.clone()
+
+        def steps(n, p):
+            cur = xx
+            for i in range(n):
+                pos = torch.full((B,), p - i, dtype=torch.long, device=dev)
+                tt = sched[0][pos - 1]
+                es = [nm.forward(cur, tt, y_rows[k], v_rows[k], m_rows[k])[0] for k in range(K + 1)]
+                cur = engine.dpm_update(cur, engine.compose_eps(es, w), None, 0.0, pos, sched, hist)
+            return cur
+
+        steps(WARM, S)
+        torch.cuda.synchronize()
+        e_0, e_1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_0.record()
+        out = steps(TIMED, S)
+        e_1.record()
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(out).all())
+        return e_0.elapsed_time(e_1) / TIMED
+
+    ws = {}
+    leg(0)
+    leg(1)
+    leg(2)
+    ws["workspace_bytes_k2"] = nm.workspace_bytes()
+    leg(4)
+    ws["workspace_bytes_k4"] = nm.workspace_bytes()
+    ms = {"dpmpp_2m_a": [], "composed_k1": [], "composed_k2": [], "composed_k4": [], "unbatched_k2": [],
+          "dpmpp_2m_b": []}
+    for _ in range(rounds):
+        ms["dpmpp_2m_a"].append(leg(0))
+        ms["composed_k1"].append(leg(1))
+        ms["composed_k2"].append(leg(2))
+        ms["composed_k4"].append(leg(4))
+        ms["unbatched_k2"].append(unbatched(2))
+        ms["dpmpp_2m_b"].append(leg(0))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    plain_mean = 0.5 * (med["dpmpp_2m_a"] + med["dpmpp_2m_b"])
+    out = {"ms_per_step_" + k: round(v, 4) for k, v in med.items()}
+    out.update({"dpmpp_2m_spread_ms": round(abs(med["dpmpp_2m_a"] - med["dpmpp_2m_b"]), 4),
+                "composed_k1_minus_dpmpp_2m_mean_ms": round(med["composed_k1"] - plain_mean, 4),
+                "composed_k2_over_dpmpp_2m_mean": round(med["composed_k2"] / plain_mean, 4),
+                "composed_k4_over_dpmpp_2m_mean": round(med["composed_k4"] / plain_mean, 4),
+                "unbatched_k2_over_composed_k2": round(med["unbatched_k2"] / med["composed_k2"], 4), **ws,
+                "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}})
+    return out
+
+
 def end_to_end(model, dev):
     import diff
     from dmx import synth
@@ -235,7 +327,7 @@ def end_to_end(model, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--groups", default="loops,known_loops,guidance_loops,end_to_end")
+    ap.add_argument("--groups", default="loops,known_loops,guidance_loops,composed_loops,end_to_end")
     args = ap.parse_args()
     groups = args.groups.split(",")
     if not torch.cuda.is_available():
@@ -250,7 +342,8 @@ def main():
     model.to(dev).eval()
     res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
            "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
-    for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs)):
+    for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs),
+                     ("composed_loops", composed_legs)):
         if name in groups:
             res[name] = fn(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
     if "end_to_end" in groups:

@@ -29,6 +29,7 @@ struct Inputs {
   dmx_dpm_sched dpm;
   dmx_known_sched known;
   dmx_guidance gd;
+  dmx_compose comp;
   explicit Inputs(int fill = 0) {
     std::memset(&a, 0, sizeof(a));  // (the step args enter the key as the caller's bytes)
     a.x_in = a.x_out = mem;
@@ -72,10 +73,18 @@ struct Inputs {
     known.S = 3;
     std::memset(&gd, fill, sizeof(gd));
     gd.rescale = 0.f;
+    std::memset(&comp, fill, sizeof(comp));
+    comp.K = 2;
+    comp.y = imem + 3;
+    comp.vals = mem + 17;
+    comp.mask = mem + 18;
+    comp.weight = mem + 19;
   }
-  GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1) const {
+  GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1,
+               bool use_comp = false) const {
     return make_graph_key(a, StepMode{use_ddim ? &ddim : nullptr, use_dpm ? &dpm : nullptr,
-                                      use_known ? &known : nullptr, use_gd ? &gd : nullptr}, table_gen);
+                                      use_known ? &known : nullptr, use_gd ? &gd : nullptr,
+                                      use_comp ? &comp : nullptr}, table_gen);
   }
 };
 
@@ -161,6 +170,38 @@ int main() {
   for (int mode = 0; mode < 3; ++mode) {
     const bool ddim = mode == 1, dpm = mode == 2;
     CHECK(Inputs(0xAA).key(ddim, dpm, true, true) == Inputs(0).key(ddim, dpm, true, true));
+  }
+  // 9. composed guidance: its own keys, member by member; the step args it replaces stay out
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    const GraphKey plain = Inputs().key(ddim, dpm), composed = Inputs().key(ddim, dpm, false, false, 1, true);
+    CHECK(!(composed == plain));
+    auto moved_c = [&](auto&& edit) {
+      Inputs in;
+      edit(in);
+      return !(in.key(ddim, dpm, false, false, 1, true) == composed);
+    };
+    CHECK(moved_c([](Inputs& in) { in.comp.K = 3; }));
+    CHECK(moved_c([](Inputs& in) { in.comp.y = imem + 5; }));
+    CHECK(moved_c([](Inputs& in) { in.comp.vals = mem + 40; }));
+    CHECK(moved_c([](Inputs& in) { in.comp.mask = mem + 40; }));
+    CHECK(moved_c([](Inputs& in) { in.comp.weight = mem + 40; }));
+    CHECK(!moved_c([](Inputs& in) { in.a.y = imem + 5; }));
+    CHECK(!moved_c([](Inputs& in) { in.a.vals = nullptr; }));
+    CHECK(!moved_c([](Inputs& in) { in.a.mask = mem + 40; }));
+    CHECK(!moved_c([](Inputs& in) { in.a.guidance = 0.f; }));
+    CHECK(!moved_c([](Inputs& in) { in.a.null_label = 0; }));
+    CHECK(moved_c([](Inputs& in) { in.a.x_in = in.a.x_out = mem + 40; }));  // (what it still reads stays in)
+    CHECK(moved_c([](Inputs& in) { in.a.sample_offset = 0; }));
+    // a plain key's compose member is all zero, and so are the other paths'
+    const dmx_compose zero{};
+    for (int kn = 0; kn < 2; ++kn)
+      for (int gd = 0; gd < 2; ++gd) {
+        const GraphKey k = Inputs(0xAA).key(ddim, dpm, kn != 0, gd != 0);
+        CHECK(std::memcmp(&k.comp, &zero, sizeof(zero)) == 0);
+      }
+    // its padding stays out of the key
+    CHECK(Inputs(0xAA).key(ddim, dpm, true, true, 1, true) == Inputs(0).key(ddim, dpm, true, true, 1, true));
   }
   if (fails == 0) std::puts("step_mode_check: ok");
   return fails == 0 ? 0 : 1;
