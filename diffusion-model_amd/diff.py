@@ -33,6 +33,8 @@ What changes is where the work happens:
 """
 from __future__ import annotations
 
+import contextlib
+import dataclasses
 import math
 import os
 import queue
@@ -107,6 +109,64 @@ class _NoisePrefetch:
             except queue.Empty:
                 pass
         self.thread.join()
+
+
+@dataclasses.dataclass
+class _SamplerPlan:
+    """What a sampling call's steps have in common, derived once (Diffuser._plan; the public one-step
+    entries fill in the fields they need): the loops of the single-process and the sharded sampler
+    walk the same plan, a shard's being the plan of its rows."""
+    rule: str                              # "ddpm", "ddim" or "dpm"
+    start: int = 0                         # the loop counter's first value: T, S, or p0 of a known-region loop
+    tables: Optional[tuple] = None         # coef_tables (ddpm)
+    sched: Optional[tuple] = None          # ddim_tables / dpm_tables (the strided rules)
+    draws: bool = True                     # do the steps draw noise (ddpm, or ddim with eta > 0)
+    scale: float = 0.0                     # guidance scale of the guided steps (0 in a composed plan)
+    rescale: float = 0.0                   # CFG rescale phi of the guided steps
+    run_g: object = True                   # guided positions: True (all), (p_lo, p_hi) or None (_guided_run)
+    known: Optional[tuple] = None          # the known-region blend's operands (engine.known_blend)
+    compose: Optional[tuple] = None        # the composed step's branch tables, contiguous on the device
+    rows: Optional[Tuple[int, int]] = None  # a shard: the rows [s, e) of the global batch
+    x_start: Optional[torch.Tensor] = None  # the latent the loop starts from
+
+    def guided(self, i: int) -> bool:
+        return self.run_g is True or (self.run_g is not None and self.run_g[0] <= i <= self.run_g[1])
+
+    def segments(self, i_from: int, i_to: int):
+        """Positions i_from .. i_to + 1 cut where the step kind changes: (a, b, guided) pieces."""
+        if self.run_g is True:
+            return [(i_from, i_to, True)]
+        return Diffuser._guidance_segments(i_from, i_to, self.run_g)
+
+    def guidance(self, guided: bool) -> float:
+        return self.scale if guided else 0.0
+
+    def new_hist(self, x):
+        """The DPM solver's history buffer for x (the loop's first position does not read it)."""
+        return torch.empty_like(x, dtype=torch.float32) if self.rule == "dpm" else None
+
+    def kwargs(self, guided: bool, hist=None, seed=None, use_graph=None) -> dict:
+        """The keywords of NativeModel.step (seed: a drawn Philox seed, else none) and, with
+        use_graph given, NativeModel.sample_loop for a guided or unguided step: a feature that
+        is off passes no keyword."""
+        kw = {}
+        if seed is not None:
+            kw["seed"] = seed
+        if use_graph is not None:
+            kw["use_graph"] = use_graph
+            if self.rows is not None:
+                kw["sample_offset"] = self.rows[0]
+        if self.sched is not None:
+            kw["sched"] = self.sched
+        if hist is not None:
+            kw["hist"] = hist
+        if self.known is not None:
+            kw["known"] = self.known
+        if guided and self.rescale > 0:
+            kw["rescale"] = self.rescale
+        if self.compose is not None:
+            kw["compose"] = self.compose
+        return kw
 
 
 class Diffuser:
@@ -321,12 +381,21 @@ class Diffuser:
     def _sampler_mode(cls, sampler, steps, eta, spacing, T):
         """Argument rules of the samplers' (sampler, steps, eta, spacing) keywords ->
         None (DDPM), ("ddim", S, eta) or ("dpm", S, spacing)."""
-        if sampler != "dpmpp_2m":
-            if spacing is not None:
-                raise ValueError(f'`spacing` belongs to sampler="dpmpp_2m" (got sampler={sampler!r})')
-            return ("ddim", int(steps), float(eta)) if cls._check_sampler(sampler, steps, eta, T) else None
+        if sampler != "dpmpp_2m" and spacing is not None:
+            raise ValueError(f'`spacing` belongs to sampler="dpmpp_2m" (got sampler={sampler!r})')
+        if sampler not in ("ddpm", "ddim", "dpmpp_2m"):
+            raise ValueError(f'sampler must be "ddpm", "ddim" or "dpmpp_2m" (got {sampler!r})')
+        if sampler == "ddpm":
+            if steps is not None:
+                raise ValueError('sampler="ddpm" walks all timesteps and takes no `steps`; strided ancestral '
+                                 'sampling is sampler="ddim", eta=1.0')
+            return None
         if steps is None or not 1 <= int(steps) <= int(T):
-            raise ValueError(f'sampler="dpmpp_2m" needs steps in [1, {T}] (got {steps})')
+            raise ValueError(f'sampler="{sampler}" needs steps in [1, {T}] (got {steps})')
+        if sampler == "ddim":
+            if not 0.0 <= float(eta) <= 1.0:
+                raise ValueError(f"eta must be in [0, 1] (got {eta})")
+            return ("ddim", int(steps), float(eta))
         if float(eta) != 0.0:
             raise ValueError(f'sampler="dpmpp_2m" is deterministic: eta must be 0 (got {eta})')
         spacing = "logsnr" if spacing is None else spacing
@@ -470,14 +539,26 @@ class Diffuser:
                 torch.stack(ws).to(device).contiguous())
 
     @staticmethod
-    def _composed_eps(model, x, t, compose):
-        """A foreign model's composed prediction: one call per branch, then the mix (engine.compose_eps)."""
-        y_rows, v_rows, m_rows, w = compose
-        es = []
-        for k in range(y_rows.shape[0]):
-            e = model(x, t, y_rows[k].to(x.device), cond_vals=v_rows[k].to(x.device), cond_mask=m_rows[k].to(x.device))
-            es.append(e[0] if isinstance(e, (tuple, list)) else e)
-        return _engine.compose_eps(es, w)
+    def _eps(model, x, t, y, null_label, cond_vals, cond_mask, g, rescale, compose):
+        """A foreign model's prediction as the operands (eu, ec, g) of an update.  compose: one call per
+        branch, then the mix (engine.compose_eps).  g > 0: the null-label and the conditional call, left
+        to the update to mix or, with rescale = phi > 0, mixed and rescaled by the standalone kernel
+        (engine.cfg_rescale).  Otherwise one call on y."""
+        def eps_of(labels, v, m):
+            e = model(x, t, labels, cond_vals=v, cond_mask=m)
+            return e[0] if isinstance(e, (tuple, list)) else e
+
+        if compose is not None:
+            y_rows, v_rows, m_rows, w = compose
+            es = [eps_of(y_rows[k].to(x.device), v_rows[k].to(x.device), m_rows[k].to(x.device))
+                  for k in range(y_rows.shape[0])]
+            return _engine.compose_eps(es, w), None, 0.0
+        if g <= 0:
+            return eps_of(y, cond_vals, cond_mask), None, 0.0
+        eu, ec = eps_of(torch.full_like(y, null_label), cond_vals, cond_mask), eps_of(y, cond_vals, cond_mask)
+        if rescale > 0:
+            return _engine.cfg_rescale(eu, ec, g, float(rescale))[0], None, 0.0
+        return eu, ec, g
 
     @staticmethod
     def _guided_run(tau, interval):
@@ -504,22 +585,6 @@ class Diffuser:
         p_lo, p_hi = run
         cuts = sorted({i_from, i_to, min(max(p_hi, i_to), i_from), min(max(p_lo - 1, i_to), i_from)}, reverse=True)
         return [(a, b, p_lo <= a <= p_hi) for a, b in zip(cuts, cuts[1:])]
-
-    @staticmethod
-    def _check_sampler(sampler, steps, eta, T):
-        """Argument rules of the samplers' (sampler, steps, eta) keywords -> True for the strided path."""
-        if sampler == "ddpm":
-            if steps is not None:
-                raise ValueError('sampler="ddpm" walks all timesteps and takes no `steps`; strided ancestral '
-                                 'sampling is sampler="ddim", eta=1.0')
-            return False
-        if sampler != "ddim":
-            raise ValueError(f'sampler must be "ddpm", "ddim" or "dpmpp_2m" (got {sampler!r})')
-        if steps is None or not 1 <= int(steps) <= int(T):
-            raise ValueError(f'sampler="ddim" needs steps in [1, {T}] (got {steps})')
-        if not 0.0 <= float(eta) <= 1.0:
-            raise ValueError(f"eta must be in [0, 1] (got {eta})")
-        return True
 
     # ---- RNG -------------------------------------------------------------------------------
     _NOISE_RING = 3
@@ -606,80 +671,60 @@ class Diffuser:
         """One DDPM step with optional classifier-free guidance (diff.py:127-162)."""
         T = self.num_timesteps
         assert (t >= 1).all() and (t <= T).all()  # (reads t back: a device sync, as in the reference)
-        return self._denoise_cond(model, x, t, y, guidance_scale, null_label, cond_vals, cond_mask)
+        plan = _SamplerPlan("ddpm", tables=self.coef_tables(x.device, clamp_prev=True),
+                            scale=float(guidance_scale) if guidance_scale else 0.0)
+        return self._step(model, x, t, plan, True, y, null_label, cond_vals, cond_mask)
 
-    def _denoise_cond(self, model, x, t, y=None, guidance_scale=0.0, null_label=0, cond_vals=None, cond_mask=None,
-                      known=None, unguided=False, rescale=0.0, compose=None):
-        """denoise_cond after the range check — the samplers' own loops build t from a host-known
-        step in [1, T] and call this directly, so the host never waits on the device per step.
-        known (engine.known_blend's 5-tuple, tables over tau = 1..T): the known-region blend follows
-        the step — inside the native step, or as a launch of its own after a foreign model's update.
-        unguided (the samplers' steps outside a guidance interval; y given): one conditional forward,
-        eps = model(x, t, y, cond_vals, cond_mask), whatever guidance_scale says — the public branch
-        for "y without guidance" below mirrors the reference's error instead.
-        rescale = phi > 0 (guided steps only): the guided prediction is scaled to the conditional
-        one's per-sample standard deviation before the update (engine.cfg_rescale).
-        compose (_compose_args' tables): the composed step instead — y, the scale, vals and mask are
-        not read; a foreign model is called once per branch (_composed_eps)."""
-        tables = self.coef_tables(x.device, clamp_prev=True)
+    def _step(self, model, x, pos, plan, guided, y=None, null_label=0, cond_vals=None, cond_mask=None, hist=None):
+        """One step of plan.rule at `pos` ((B,): timesteps for ddpm, positions of plan.sched otherwise)
+        after the public entries' range checks — the samplers' loops build pos from a host-known
+        counter and call this directly, so the host never waits on the device per step.
+        guided: CFG (plan.scale > 0 and y given; rescaled for plan.rescale > 0), else one conditional
+        forward (the steps outside a guidance interval; y defaults to null_label on the strided
+        rules).  A ddpm step that asks for guidance but cannot have it is the reference's plain branch,
+        mirrored literally.  plan.compose: the composed step, which reads none of y, vals, mask.
+        A dmx network on the GPU runs it as one native step, known-region blend included; any other
+        model is called like the reference and the update and the blend run natively after it.
+        The native step draws its noise (host mode) or seed (device mode) before the step, the
+        foreign one after the model's forwards; a rule that draws nothing consumes neither."""
+        rule, compose = plan.rule, plan.compose
+        g = plan.scale if guided and compose is None and y is not None and plan.scale > 0 else 0.0
+        mirror = rule == "ddpm" and guided and compose is None and g == 0.0
+        if rule != "ddpm":
+            pos = pos.to(device=x.device, dtype=torch.long)
+            if y is None and compose is None:
+                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
+
+        def draw():  # -> (noise, seed): host noise, else a seed where the rule draws at all
+            noise = self._step_noise(x) if plan.draws else None
+            return noise, self._seed() if plan.draws and noise is None else None
+
         with torch.no_grad():
-            if compose is not None:
-                if _native_kind(model) in (1, 2) and x.is_cuda:
-                    noise = self._step_noise(x)
-                    out = torch.empty_like(x)
-                    model.native().step(x.contiguous(), out, t.to(x.device), None, 0, None, None, 0.0, tables, noise,
-                                        seed=self._seed() if noise is None else 0, known=known, compose=compose)
-                    return out
-                eps = self._composed_eps(model, x, t, compose)
-                noise = self._step_noise(x)
-                return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
-                                                       seed=self._seed() if noise is None else 0), t, known)
-            if unguided:
-                if _native_kind(model) in (1, 2) and x.is_cuda:
-                    noise = self._step_noise(x)
-                    out = torch.empty_like(x)
-                    use = cond_vals is not None and cond_mask is not None
-                    model.native().step(x.contiguous(), out, t.to(x.device), y.to(x.device), null_label,
-                                        cond_vals if use else None, cond_mask if use else None, 0.0, tables, noise,
-                                        seed=self._seed() if noise is None else 0, known=known)
-                    return out
-                eps = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-                eps = eps[0] if isinstance(eps, (tuple, list)) else eps
-                noise = self._step_noise(x)
-                return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
-                                                       seed=self._seed() if noise is None else 0), t, known)
-            if guidance_scale and y is not None and guidance_scale > 0:
-                kind = _native_kind(model)
-                if kind in (1, 2) and x.is_cuda:
-                    noise = self._step_noise(x)
-                    out = torch.empty_like(x)
-                    use = cond_vals is not None and cond_mask is not None
-                    model.native().step(x.contiguous(), out, t.to(x.device), y.to(x.device), null_label,
-                                        cond_vals if use else None, cond_mask if use else None,
-                                        float(guidance_scale), tables, noise,
-                                        seed=self._seed() if noise is None else 0, known=known,
-                                        **(dict(rescale=float(rescale)) if rescale > 0 else {}))
-                    return out
-                y_null = torch.full_like(y, null_label)
-                eps_uncond, _ = model(x, t, y_null, cond_vals=cond_vals, cond_mask=cond_mask)
-                eps_cond, _ = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-                if rescale > 0:  # the standalone kernel, then the update on its eps
-                    eps_uncond, _ = _engine.cfg_rescale(eps_uncond, eps_cond, float(guidance_scale), float(rescale))
-                    eps_cond, guidance_scale = None, 0.0
-                noise = self._step_noise(x)
-                return self._blend(_engine.ddpm_update(x, eps_uncond, eps_cond, float(guidance_scale), t, tables,
-                                                       noise, seed=self._seed() if noise is None else 0), t, known)
-            else:
-                # plain conditional/unconditional — mirrors diff.py:152-156 literally, including
-                # its UnboundLocalError when y is given without guidance
-                if y is None:
-                    y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
-                    eps = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-        noise = self._step_noise(x)
-        if not isinstance(eps, torch.Tensor):
-            raise TypeError(f"unsupported operand type(s) for *: 'Tensor' and '{type(eps).__name__}'")
-        return self._blend(_engine.ddpm_update(x, eps, None, 0.0, t, tables, noise,
-                                               seed=self._seed() if noise is None else 0), t, known)
+            if _native_kind(model) in (1, 2) and x.is_cuda and not mirror:
+                noise, seed = draw()
+                x_in = x.contiguous() if rule == "ddpm" else x.float().contiguous()
+                out = torch.empty_like(x_in)
+                use = cond_vals is not None and cond_mask is not None
+                model.native().step(x_in, out, pos.to(x.device), None if y is None else y.to(x.device), null_label,
+                                    cond_vals if use else None, cond_mask if use else None, g, plan.tables, noise,
+                                    **plan.kwargs(g > 0, hist, seed=seed))
+                return out
+            t = pos if rule == "ddpm" else plan.sched[0][pos - 1]
+            if not mirror:
+                eu, ec, g = self._eps(model, x, t, y, null_label, cond_vals, cond_mask, g, plan.rescale, compose)
+            elif y is None:  # diff.py:152-156 literally, including its UnboundLocalError when y is given
+                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
+                eu, ec = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask), None
+        noise, seed = draw()
+        if mirror and not isinstance(eu, torch.Tensor):
+            raise TypeError(f"unsupported operand type(s) for *: 'Tensor' and '{type(eu).__name__}'")
+        if rule == "ddpm":
+            out = _engine.ddpm_update(x, eu, ec, g, pos, plan.tables, noise, seed=seed or 0)
+        elif rule == "ddim":
+            out = _engine.ddim_update(x, eu, ec, g, pos, plan.sched, noise, seed=seed or 0)
+        else:
+            out = _engine.dpm_update(x, eu, ec, g, pos, plan.sched, hist)
+        return self._blend(out, pos, plan.known)
 
     @staticmethod
     def _blend(x, pos, known):
@@ -693,57 +738,9 @@ class Diffuser:
         is given, otherwise one conditional forward (y defaults to null_label)."""
         S = len(self.ddim_timesteps(steps))
         assert (pos >= 1).all() and (pos <= S).all()  # (reads pos back: a device sync, as denoise_cond)
-        return self._ddim_step(model, x, pos, self.ddim_tables(steps, eta, x.device), float(eta) > 0, y,
-                               guidance_scale, null_label, cond_vals, cond_mask)
-
-    def _ddim_step(self, model, x, pos, sched, noisy, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                   cond_mask=None, known=None, rescale=0.0, compose=None):
-        """ddim_step after its checks; `noisy`: the schedule has noise (eta > 0).  Host-noise mode then
-        draws one randn(x.shape) per call and device mode a Philox seed; with eta = 0 neither draws.
-        rescale = phi > 0 (CFG steps only), compose: as in _denoise_cond."""
-        cfg = bool(compose is None and guidance_scale and y is not None and guidance_scale > 0)
-        g = float(guidance_scale) if cfg else 0.0
-        pos = pos.to(device=x.device, dtype=torch.long)
-        with torch.no_grad():
-            if compose is not None:
-                if _native_kind(model) in (1, 2) and x.is_cuda:
-                    noise = self._step_noise(x) if noisy else None
-                    x_in = x.float().contiguous()
-                    out = torch.empty_like(x_in)
-                    model.native().step(x_in, out, pos, None, 0, None, None, 0.0, None, noise,
-                                        seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known,
-                                        compose=compose)
-                    return out
-                eps = self._composed_eps(model, x, sched[0][pos - 1], compose)
-                noise = self._step_noise(x) if noisy else None
-                seed = self._seed() if noisy and noise is None else 0
-                return self._blend(_engine.ddim_update(x, eps, None, 0.0, pos, sched, noise, seed=seed), pos, known)
-            if y is None:
-                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
-            if _native_kind(model) in (1, 2) and x.is_cuda:
-                noise = self._step_noise(x) if noisy else None
-                x_in = x.float().contiguous()
-                out = torch.empty_like(x_in)
-                use = cond_vals is not None and cond_mask is not None
-                model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
-                                    cond_mask if use else None, g, None, noise,
-                                    seed=self._seed() if noisy and noise is None else 0, sched=sched, known=known,
-                                    **(dict(rescale=float(rescale)) if cfg and rescale > 0 else {}))
-                return out
-
-            t = sched[0][pos - 1]
-
-            def eps_of(labels):
-                e = model(x, t, labels, cond_vals=cond_vals, cond_mask=cond_mask)
-                return e[0] if isinstance(e, (tuple, list)) else e
-
-            eu = eps_of(torch.full_like(y, null_label) if cfg else y)
-            ec = eps_of(y) if cfg else None
-            if cfg and rescale > 0:  # the standalone kernel, then the update on its eps
-                eu, ec, g = _engine.cfg_rescale(eu, ec, g, float(rescale))[0], None, 0.0
-        noise = self._step_noise(x) if noisy else None
-        return self._blend(_engine.ddim_update(x, eu, ec, g, pos, sched, noise,
-                                               seed=self._seed() if noisy and noise is None else 0), pos, known)
+        plan = _SamplerPlan("ddim", sched=self.ddim_tables(steps, eta, x.device), draws=float(eta) > 0,
+                            scale=float(guidance_scale) if guidance_scale else 0.0)
+        return self._step(model, x, pos, plan, True, y, null_label, cond_vals, cond_mask)
 
     def dpm_step(self, model, x, pos, hist, steps, spacing="logsnr", y=None, guidance_scale=0.0, null_label=0,
                  cond_vals=None, cond_mask=None):
@@ -753,48 +750,9 @@ class Diffuser:
         pos + 1 left; positions `steps` and 1 do not read it.  Draws nothing.  CFG as in ddim_step."""
         S = len(self.dpm_timesteps(steps, spacing))
         assert (pos >= 1).all() and (pos <= S).all()  # (reads pos back: a device sync, as denoise_cond)
-        return self._dpm_step(model, x, pos, self.dpm_tables(steps, spacing, x.device), hist, y, guidance_scale,
-                              null_label, cond_vals, cond_mask)
-
-    def _dpm_step(self, model, x, pos, sched, hist, y=None, guidance_scale=0.0, null_label=0, cond_vals=None,
-                  cond_mask=None, known=None, rescale=0.0, compose=None):
-        """dpm_step after its checks: the native step, or a foreign model's eps through dpm_update.
-        rescale = phi > 0 (CFG steps only), compose: as in _denoise_cond."""
-        cfg = bool(compose is None and guidance_scale and y is not None and guidance_scale > 0)
-        g = float(guidance_scale) if cfg else 0.0
-        pos = pos.to(device=x.device, dtype=torch.long)
-        with torch.no_grad():
-            if compose is not None:
-                if _native_kind(model) in (1, 2) and x.is_cuda:
-                    x_in = x.float().contiguous()
-                    out = torch.empty_like(x_in)
-                    model.native().step(x_in, out, pos, None, 0, None, None, 0.0, None, None, sched=sched, hist=hist,
-                                        known=known, compose=compose)
-                    return out
-                eps = self._composed_eps(model, x, sched[0][pos - 1], compose)
-                return self._blend(_engine.dpm_update(x, eps, None, 0.0, pos, sched, hist), pos, known)
-            if y is None:
-                y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
-            if _native_kind(model) in (1, 2) and x.is_cuda:
-                x_in = x.float().contiguous()
-                out = torch.empty_like(x_in)
-                use = cond_vals is not None and cond_mask is not None
-                model.native().step(x_in, out, pos, y.to(x.device), null_label, cond_vals if use else None,
-                                    cond_mask if use else None, g, None, None, sched=sched, hist=hist, known=known,
-                                    **(dict(rescale=float(rescale)) if cfg and rescale > 0 else {}))
-                return out
-
-            t = sched[0][pos - 1]
-
-            def eps_of(labels):
-                e = model(x, t, labels, cond_vals=cond_vals, cond_mask=cond_mask)
-                return e[0] if isinstance(e, (tuple, list)) else e
-
-            eu = eps_of(torch.full_like(y, null_label) if cfg else y)
-            ec = eps_of(y) if cfg else None
-            if cfg and rescale > 0:
-                eu, ec, g = _engine.cfg_rescale(eu, ec, g, float(rescale))[0], None, 0.0
-        return self._blend(_engine.dpm_update(x, eu, ec, g, pos, sched, hist), pos, known)
+        plan = _SamplerPlan("dpm", sched=self.dpm_tables(steps, spacing, x.device), draws=False,
+                            scale=float(guidance_scale) if guidance_scale else 0.0)
+        return self._step(model, x, pos, plan, True, y, null_label, cond_vals, cond_mask, hist)
 
     # ---- loops --------------------------------------------------------------------------------
     def sample(self, model, x_shape=(20, 3, 80, 80)):
@@ -821,7 +779,8 @@ class Diffuser:
             return x
 
         with torch.no_grad():
-            x = self._guarded_host_loop(model, x, run)
+            x = self._guarded_loop(self._prefetching(run, model, x), x, self.num_timesteps,
+                                   self._guard_target(model, x))
         if bar is not None:
             bar.close()
         if vae is None:
@@ -832,47 +791,64 @@ class Diffuser:
     GUARD_CHUNK = 50
 
     @staticmethod
-    def _guard_target(model):
-        """The NativeModel whose range flag guards this loop (None: foreign model or exact fp32)."""
-        if not _native_kind(model):
+    def _guard_target(model, x=None):
+        """The NativeModel whose range flag guards this loop (None: foreign model, exact fp32, or a
+        loop on the host tensor x)."""
+        if not _native_kind(model) or (x is not None and not x.is_cuda):
             return None
         nm = model.native()
         return nm if nm.precision != "fp32" else None
 
-    def _guarded_host_loop(self, model, x, run, on_replay=None, total=None, draws=True):
-        """T steps (or `total` positions of a strided schedule) in chunks of GUARD_CHUNK.  After each
-        chunk the model's range flag is read (dmx_model_range_check); if an operand left the f16 range of the split-precision modes
-        the chunk is replayed from its start — same x, same CPU-generator state, hence the same
-        draws — in exact-fp32 MFMA mode.  `run(i_from, i_to, x)` advances t = i_from .. i_to + 1.
-        draws=False: the steps draw no noise (DDIM with eta = 0), so nothing is prefetched."""
-        T = self.num_timesteps if total is None else int(total)
-        nm = self._guard_target(model) if x.is_cuda else None
-        prefetch = draws and x.is_cuda and self.noise_source == "host" and _native_kind(model) != 0
-        i = T
+    def _guarded_loop(self, run, x, start, guard, hist=None, inplace=False, on_replay=None, any_rank=None,
+                      owner=None):
+        """The positions start .. 1 in chunks of GUARD_CHUNK; `run(i_from, i_to, x)` advances
+        i_from .. i_to + 1 and returns x, which it steps in place (`inplace`: the device loop) or
+        replaces.  After each chunk the range flag of `guard` (a NativeModel, or None) is read
+        (dmx_model_range_check) and combined over the ranks by `any_rank` where given; if an operand
+        left the f16 range of the split-precision modes the chunk is replayed from its start — same
+        x, same solver history `hist`, same CPU-generator state, hence the same draws — in exact-fp32
+        MFMA mode (a rank without a guard just reruns it), after `on_replay()`, and `owner`
+        (default: this Diffuser) counts one range_fallbacks.  The chunk's start is kept only where a
+        replay can happen; an in-place runner needs a copy of it."""
+        keep = guard is not None or any_rank is not None
+        i = int(start)
         while i >= 1:
             j = max(i - self.GUARD_CHUNK, 0)
-            x0, rng = x, torch.get_rng_state()
-            x = self._run_chunk(run, i, j, x, prefetch)
-            if nm is not None and nm.range_tripped():
+            if keep:
+                x0, rng = x.clone() if inplace else x, torch.get_rng_state()
+                h0 = hist.clone() if hist is not None else None
+            x = run(i, j, x)
+            tripped = guard is not None and guard.range_tripped()
+            if any_rank(tripped) if any_rank is not None else tripped:
                 if on_replay is not None:
                     on_replay()
                 torch.set_rng_state(rng)
-                with nm.precision_override("fp32"):
-                    x = self._run_chunk(run, i, j, x0, prefetch)
-                nm.range_tripped()  # clear
-                self.range_fallbacks += 1
+                x = x.copy_(x0) if inplace else x0
+                if hist is not None:
+                    hist.copy_(h0)
+                with guard.precision_override("fp32") if guard is not None else contextlib.nullcontext():
+                    x = run(i, j, x)
+                if guard is not None:
+                    guard.range_tripped()  # clear
+                owner = self if owner is None else owner
+                owner.range_fallbacks += 1
             i = j
         return x
 
-    def _run_chunk(self, run, i, j, x, prefetch):
-        if not prefetch:
-            return run(i, j, x)
-        self._prefetch = _NoisePrefetch(x.shape, i - j)
-        try:
-            return run(i, j, x)
-        finally:
-            pf, self._prefetch = self._prefetch, None
-            pf.close()
+    def _prefetching(self, run, model, x, draws=True):
+        """`run` with each chunk's host-noise draws made ahead on a helper thread (_NoisePrefetch),
+        where the chunk's steps draw host noise for a dmx network on the GPU; else `run` itself."""
+        if not (draws and x.is_cuda and self.noise_source == "host" and _native_kind(model) != 0):
+            return run
+
+        def chunk(i, j, x):
+            self._prefetch = _NoisePrefetch(x.shape, i - j)
+            try:
+                return run(i, j, x)
+            finally:
+                pf, self._prefetch = self._prefetch, None
+                pf.close()
+        return chunk
 
     def sample_cond(self, model, x_shape, y, guidance_scale=0.0, null_label=0):
         """diff.py:165-172."""
@@ -1083,153 +1059,107 @@ class Diffuser:
             C, Hlat, Wlat = z_shape
 
         x = self._randn((B, C, Hlat, Wlat), device)
-        gkw = {}  # (with both keywords at their defaults the loop is called as it was)
-        if interval is not None:
-            gkw["interval"] = interval
-        if phi > 0:
-            gkw["rescale"] = phi
-        if compose is not None:
-            gkw["compose"] = compose
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
-                                **(dict(known=known[:3]) if known is not None else {}), **gkw)
+                                known=known[:3] if known is not None else None, interval=interval, rescale=phi,
+                                compose=compose)
         if vae is None:
             return x
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         return self._decode(vae, x, to_pil)
 
-    def _known_setup(self, x, known, mode, total):
-        """The known-region state of a loop over `total` positions whose draw is x:
-        (x_start, p0, blend operands or None).  known = (z0, mask or None, strength) (_known_inputs).
-        p0 = total: x_start holds x's values.  Otherwise it is the blend's kn one table row up (position
-        p0 + 1 arrives at tau_p0), written to a new tensor.  Without a mask no step is blended."""
-        z0, kmask, strength = known
-        p0 = self._known_start(strength, total)
-        if p0 == total and kmask is None:
-            return x, p0, None
-        e0 = x.to(torch.float32).contiguous()
-        z0 = z0.to(x.device)
-        q_a, q_e = self.known_tables(self._mode_timesteps(mode), x.device)
-        if p0 < total:
-            pos = torch.full((1,), p0 + 1, dtype=torch.long, device=x.device)
-            x = _engine.known_blend(z0, pos, (z0, e0, None, q_a, q_e))
+    def _plan(self, x, mode, guidance_scale, known=None, interval=None, rescale=0.0, compose=None,
+              rows=None) -> _SamplerPlan:
+        """The plan of a sampling call whose x_T draw is x, on x's device.
+        mode: _sampler_mode's result.  interval, rescale: _guidance_args' (t_lo, t_hi) or None and phi.
+        compose: _compose_args' tables or None; a composed plan has no scale, interval or rescale.
+        known = (z0, mask or None, strength) (_known_inputs) or None: x is the call's fixed draw e0 and
+        the loop enters at p0 = _known_start.  plan.x_start then holds x's values for p0 = total, else
+        the blend's kn one table row up (position p0 + 1 arrives at tau_p0), written to a new tensor;
+        without a mask no step is blended.
+        rows = (s, e): a shard — x holds the rows [s, e) of the global draw, and the plan takes those
+        rows of z0 and the mask and the columns [:, s:e] of the compose tables."""
+        dev = x.device
+        rule = "ddpm" if mode is None else mode[0]
+        tau = self._mode_timesteps(mode)
+        cut = slice(None) if rows is None else slice(*rows)
+        plan = _SamplerPlan(rule, start=len(tau), draws=rule == "ddpm" or (rule == "ddim" and mode[2] > 0),
+                            rows=rows, x_start=x)
+        if compose is not None:  # converted once: a loop's graphs hold their pointers
+            plan.compose = tuple(c[:, cut].to(dev).contiguous() for c in compose)
         else:
-            x = e0.clone()  # (e0 stays a constant of the loop: in-place steps must not write it)
-        return x, p0, (z0, e0, kmask.to(x.device), q_a, q_e) if kmask is not None else None
+            plan.scale = float(guidance_scale) if guidance_scale else 0.0
+            plan.rescale = float(rescale)
+            plan.run_g = True if interval is None else self._guided_run(tau, interval)
+        if known is not None:
+            z0, kmask, strength = known
+            total, plan.start = len(tau), self._known_start(strength, len(tau))
+            if x.shape[0] > 0 and (plan.start < total or kmask is not None):
+                e0 = x.to(torch.float32).contiguous()
+                z0 = z0[cut].to(dev)
+                q_a, q_e = self.known_tables(tau, dev)
+                if plan.start < total:
+                    pos = torch.full((1,), plan.start + 1, dtype=torch.long, device=dev)
+                    plan.x_start = _engine.known_blend(z0, pos, (z0, e0, None, q_a, q_e))
+                else:  # (e0 stays a constant of the loop: in-place steps must not write it)
+                    plan.x_start = e0.clone()
+                if kmask is not None:
+                    plan.known = (z0, e0, kmask[cut].to(dev), q_a, q_e)
+        if rule == "ddpm":
+            plan.tables = self.coef_tables(dev, clamp_prev=True)
+        elif rule == "ddim":
+            plan.sched = self.ddim_tables(mode[1], mode[2], dev)
+        else:  # (a loop entering at p0 < S: that row is first-order)
+            plan.sched = self.dpm_tables(mode[1], mode[2], dev, plan.start if known is not None else None)
+        return plan
+
+    def _device_chunks(self, nm, plan, x, y, null_label, vals, msk, hist, seed, bar=None):
+        """The chunk runner of the device loop on x: Philox noise, hipGraph replay, the position scalar
+        decremented in-graph — it runs on across a chunk's segments (plan.segments).  An empty shard
+        launches nothing."""
+        t_dev = torch.full((1,), plan.start, device=x.device, dtype=torch.long)
+
+        def run(i_from, i_to, x):
+            if x.shape[0] > 0:
+                t_dev.fill_(i_from)
+                for a, b, guided in plan.segments(i_from, i_to):
+                    nm.sample_loop(x, t_dev, y, null_label, vals, msk, plan.guidance(guided), plan.tables, a - b,
+                                   **plan.kwargs(guided, hist, seed=seed, use_graph=self.use_graph))
+            if bar is not None:
+                bar.update(i_from - i_to)
+            return x
+        return run
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
                        interval=None, rescale=0.0, compose=None):
-        """The T loop (diff.py:328-344), range-guarded in chunks (_guarded_host_loop).
-        mode = ("ddim", S, eta) (_sampler_mode): the strided loop instead — the counter walks the S
-        positions of ddim_tables(S, eta) down exactly as it walks t, with the same chunks, guard and
-        replay.  mode = ("dpm", S, spacing): likewise over dpm_tables(S, spacing); the solver's history
-        buffer lives here, and a replayed chunk restarts from the history it started with.
-        known = (z0, mask or None, strength): x is the call's fixed draw e0; the loop enters at p0
-        (_known_setup) and, with a mask, every step on every path is followed by the known-region
-        blend.  z0, e0 and the mask are constants, so a replayed chunk needs nothing more.
-        interval = (t_lo, t_hi) / rescale = phi (_guidance_args): the positions whose timestep lies
-        outside the interval run unguided (one conditional forward), the others with CFG and, for
-        phi > 0, the rescaled prediction.  Every chunk is walked segment by segment
-        (_guidance_segments); a replayed chunk walks the same segments.
-        compose (_compose_args' tables; no interval, no rescale): every step on every path is the
-        composed step — y, vals, msk and guidance_scale are then not read."""
-        if compose is not None:
-            compose = tuple(c.to(x.device).contiguous() for c in compose)  # once: a loop's graphs hold their pointers
-            guidance_scale, interval, rescale = 0.0, None, 0.0
-        ckw = dict(compose=compose) if compose is not None else {}
-        run_g = self._guided_run(self._mode_timesteps(mode), interval) if interval is not None else True
-        rkw = dict(rescale=float(rescale)) if rescale > 0 else {}
-
-        def segments(i_from, i_to):  # without an interval: the one guided piece every chunk was
-            return [(i_from, i_to, True)] if run_g is True else self._guidance_segments(i_from, i_to, run_g)
-
-        ddim = mode[1:] if mode is not None and mode[0] == "ddim" else None
-        dpm = mode is not None and mode[0] == "dpm"
-        T = self.num_timesteps if mode is None else mode[1]
-        kkw, start = {}, None  # (without `known` every call below is the call it was)
-        if known is not None:
-            x, start, kn = self._known_setup(x, known, mode, T)
-            T = start  # from here: the p0 positions left to walk
-            if kn is not None:
-                kkw["known"] = kn
-        sched = (self.dpm_tables(mode[1], mode[2], x.device, start) if dpm
-                 else self.ddim_tables(ddim[0], ddim[1], x.device) if ddim is not None else None)
-        native = _native_kind(model) in (1, 2) and x.is_cuda and (compose is not None or
-                                                                  (guidance_scale and guidance_scale > 0))
-        bar = tqdm(total=T, desc="Sampling (cond+numeric)") if progress else None
-        if native and self.noise_source == "device":
-            # whole loop on the device: Philox noise, hipGraph replay, t decremented in-graph
-            nm = model.native()
+        """The T loop (diff.py:328-344) over the call's plan (_plan), range-guarded in chunks
+        (_guarded_loop): the counter walks timesteps, or the positions of a strided schedule, down
+        from plan.start, and a replayed chunk restarts from the x and the solver history it started
+        with.  A dmx network with guidance (or a composed call) in device-noise mode runs whole chunks
+        on the device (_device_chunks); every other case steps on the host (_step)."""
+        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose)
+        x = plan.x_start
+        hist = plan.new_hist(x)
+        guard = self._guard_target(model, x)
+        native = _native_kind(model) in (1, 2) and x.is_cuda and (plan.compose is not None or plan.scale > 0)
+        device_loop = native and self.noise_source == "device"
+        bar = tqdm(total=plan.start, desc="Sampling (cond+numeric)") if progress else None
+        if device_loop:
             x = x.contiguous().clone()
-            t_dev = torch.full((1,), T, device=x.device, dtype=torch.long)
-            tables = self.coef_tables(x.device, clamp_prev=True) if sched is None else None
-            skw = dict(sched=sched) if sched is not None else {}  # (the DDPM calls stay as they were)
-            skw.update(kkw)
-            hist = None
-            if dpm:  # position S does not read it: no initial value needed
-                hist = skw["hist"] = torch.empty_like(x, dtype=torch.float32)
-            seed = 0 if dpm else self._seed()  # the DPM solver draws nothing
-            v, m = vals.float().contiguous(), msk.float().contiguous()
-            guard = self._guard_target(model)
-            done = 0
-
-            def launch(p, k):  # k steps from position p; the position scalar runs on across the segments
-                for a, b, guided in segments(p, p - k):
-                    nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0, tables,
-                                   a - b, seed=seed, use_graph=self.use_graph, **skw, **(rkw if guided else {}),
-                                   **ckw)
-
-            with torch.no_grad():
-                while done < T:
-                    k = min(self.GUARD_CHUNK, T - done)
-                    x0 = x.clone() if guard is not None else None
-                    h0 = hist.clone() if guard is not None and dpm else None
-                    launch(T - done, k)
-                    if guard is not None and guard.range_tripped():
-                        x.copy_(x0)
-                        if dpm:
-                            hist.copy_(h0)
-                        t_dev.fill_(T - done)
-                        with guard.precision_override("fp32"):
-                            launch(T - done, k)
-                        guard.range_tripped()
-                        self.range_fallbacks += 1
-                    done += k
+            seed = 0 if plan.rule == "dpm" else self._seed()  # the DPM solver draws nothing
+            run = self._device_chunks(model.native(), plan, x, y, null_label, vals.float().contiguous(),
+                                      msk.float().contiguous(), hist, seed, bar)
+        else:
+            def step_chunk(i_from, i_to, x):
+                for i in range(i_from, i_to, -1):  # i in [1, T]: the public steps' asserts hold by construction
+                    t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
+                    x = self._step(model, x, t, plan, plan.guided(i), y, null_label, vals, msk, hist)
                     if bar is not None:
-                        bar.update(k)
-            if bar is not None:
-                bar.close()
-            return x
-
-        hist = torch.empty_like(x, dtype=torch.float32) if dpm else None
-        snap = [None]  # hist at the start of the running chunk (guarded models only)
-        guarded = dpm and x.is_cuda and self._guard_target(model) is not None
-
-        def restore_hist():
-            hist.copy_(snap[0])
-
-        def run(i_from, i_to, x):
-            if guarded:
-                snap[0] = hist.clone()
-            for i in range(i_from, i_to, -1):  # i in [1, T]: denoise_cond's assert holds by construction
-                t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
-                guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
-                gs = guidance_scale if guided else 0.0
-                skw = dict(kkw, **rkw, **ckw) if guided else kkw
-                if sched is None:  # (the unguided DDPM step: not the public branch, which mirrors an error)
-                    x = self._denoise_cond(model, x, t, y, gs, null_label, vals, msk, **skw,
-                                           **({} if guided else dict(unguided=True)))
-                elif dpm:  # t holds the position
-                    x = self._dpm_step(model, x, t, sched, hist, y, gs, null_label, vals, msk, **skw)
-                else:
-                    x = self._ddim_step(model, x, t, sched, ddim[1] > 0, y, gs, null_label, vals, msk, **skw)
-                if bar is not None:
-                    bar.update(1)
-            return x
-
+                        bar.update(1)
+                return x
+            run = self._prefetching(step_chunk, model, x, plan.draws)
         with torch.no_grad():
-            x = self._guarded_host_loop(model, x, run, on_replay=restore_hist if guarded else None, total=T,
-                                        draws=mode is None or (ddim is not None and ddim[1] > 0))
+            x = self._guarded_loop(run, x, plan.start, guard, hist, inplace=device_loop)
         if bar is not None:
             bar.close()
         return x

@@ -216,13 +216,6 @@ class ShardedCondSampler:
         interval, phi = d._guidance_args(None if composed else guidance_scale,
                                          None if composed else guidance_interval,
                                          0.0 if composed else guidance_rescale, d.num_timesteps)
-        run_g = d._guided_run(d._mode_timesteps(mode), interval) if interval is not None else True
-        rkw = dict(rescale=phi) if phi > 0 else {}  # (with both keywords at their defaults every call stays as it was)
-
-        def segments(i_from, i_to):
-            return [(i_from, i_to, True)] if run_g is True else d._guidance_segments(i_from, i_to, run_g)
-        ddim = mode is not None and mode[0] == "ddim"
-        dpm = mode is not None and mode[0] == "dpm"
         items = d._norm_counts(class_counts)
         y_list: List[int] = []
         for cls, num in items:
@@ -233,10 +226,6 @@ class ShardedCondSampler:
         compose = d._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval, guidance_rescale,
                                   null_label, None, None, dev)
         s, e = shard_range(B, ws, rank)
-        ckw = {}
-        if compose is not None:  # this shard's rows of every branch, converted once (the graphs hold their pointers)
-            ckw["compose"] = tuple(c[:, s:e].contiguous() for c in compose)
-            guidance_scale = 0.0
         y = torch.tensor(y_list[s:e], device=dev, dtype=torch.long)
         v, m = vals[s:e].float().contiguous(), msk[s:e].float().contiguous()
         known = d._known_inputs(init_latent, mask, strength, B, z_shape)
@@ -249,58 +238,37 @@ class ShardedCondSampler:
         C, H, W = z_shape
         nm = self.model.native() if e > s else None
         guard = d._guard_target(self.model) if nm is not None else None
-        tables = d.coef_tables(dev, clamp_prev=True) if mode is None else None
-        T = int(steps) if mode is not None else d.num_timesteps  # the loop counter: timesteps, or positions
-        p0 = d._known_start(known[2], T) if known is not None else T  # the position the loop enters at
-        sched = (d.dpm_tables(mode[1], mode[2], dev, p0 if known is not None else None) if dpm
-                 else d.ddim_tables(steps, eta, dev) if ddim else None)
-        draws = mode is None or (ddim and float(eta) > 0)  # DDIM with eta = 0 and DPM draw no per-step noise
-        skw = dict(sched=sched) if mode is not None else {}  # (the DDPM calls stay exactly as they were)
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
-        if known is not None and e > s:  # this shard's rows of z0 / mask; x is its rows of e0
-            rows = (known[0][s:e], known[1][s:e] if known[1] is not None else None, known[2])
-            x, _, kn = d._known_setup(x, rows, mode, T)
-            if kn is not None:
-                skw["known"] = kn
-        T = p0
-        hist = None
-        if dpm:  # this shard's rows; position S does not read it, so it needs no initial value
-            hist = skw["hist"] = torch.empty_like(x)
+        # the single-process sampler's plan for this shard's rows; x is its rows of e0
+        plan = d._plan(x, mode, guidance_scale, known[:3] if known is not None else None, interval, phi, compose,
+                       rows=(s, e))
+        x = plan.x_start
+        hist = plan.new_hist(x)  # shard-local
         if d.noise_source == "device":
             # drawn after x_T, as _run_cond_loop does (the DPM solver draws nothing: no seed)
-            seed = torch.tensor([0 if dpm else d._seed()], dtype=torch.long)
-            if ws > 1 and not dpm:
+            seed = torch.tensor([0 if plan.rule == "dpm" else d._seed()], dtype=torch.long)
+            if ws > 1 and plan.rule != "dpm":
                 if dist.get_backend() != "gloo":
                     seed = seed.to(dev)
                 dist.broadcast(seed, src=0)
-            seed = int(seed.item())
-            t_dev = torch.full((1,), T, dtype=torch.long, device=dev)
-
-            def run(i_from, i_to, xs):  # device Philox loop, graph-replayed, t decremented in-graph
-                if xs.shape[0] > 0:
-                    t_dev.fill_(i_from)
-                    for a, b, guided in segments(i_from, i_to):  # the position scalar runs on across them
-                        nm.sample_loop(xs, t_dev, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
-                                       tables, a - b, seed=seed, sample_offset=s, use_graph=d.use_graph, **skw,
-                                       **(rkw if guided else {}), **ckw)
-                return xs
+            run = d._device_chunks(nm, plan, x, y, null_label, v, m, hist, int(seed.item()))
         else:
             def run(i_from, i_to, xs):
                 """One global CPU-generator draw per step (this shard's rows kept), made one step
                 ahead on a helper thread into pinned buffers (diff._NoisePrefetch: same generator,
                 same order), so the host draw of the global tensor overlaps the GPU step."""
                 pf = (self._prefetch((B, C, H, W), i_from - i_to, rows=(s, e))
-                      if dev.type == "cuda" and draws else None)
+                      if dev.type == "cuda" and plan.draws else None)
                 try:
                     for i in range(i_from, i_to, -1):
-                        noise = (None if not draws else pf.next(dev) if pf is not None
+                        noise = (None if not plan.draws else pf.next(dev) if pf is not None
                                  else host_noise_slice((B, C, H, W), s, e, dev))
                         if xs.shape[0] > 0:  # an empty shard (B < world size) only keeps the draw order
                             out = torch.empty_like(xs)
                             tt = torch.full((xs.shape[0],), i, dtype=torch.long, device=dev)
-                            guided = run_g is True or (run_g is not None and run_g[0] <= i <= run_g[1])
-                            nm.step(xs, out, tt, y, null_label, v, m, float(guidance_scale) if guided else 0.0,
-                                    tables, noise, **skw, **(rkw if guided else {}), **ckw)
+                            guided = plan.guided(i)
+                            nm.step(xs, out, tt, y, null_label, v, m, plan.guidance(guided), plan.tables, noise,
+                                    **plan.kwargs(guided, hist))
                             xs = out
                 finally:
                     if pf is not None:
@@ -308,26 +276,8 @@ class ShardedCondSampler:
                 return xs
 
         with torch.no_grad():
-            i = T
-            while i >= 1:
-                j = max(i - d.GUARD_CHUNK, 0)
-                x0, rng = x.clone(), torch.get_rng_state()
-                h0 = hist.clone() if dpm else None
-                x = run(i, j, x)
-                tripped = guard.range_tripped() if guard is not None else False
-                if any_rank(tripped, dev):
-                    torch.set_rng_state(rng)
-                    x = x0
-                    if dpm:
-                        hist.copy_(h0)
-                    if guard is not None:
-                        with guard.precision_override("fp32"):
-                            x = run(i, j, x)
-                        guard.range_tripped()  # clear
-                    else:
-                        x = run(i, j, x)
-                    self.range_fallbacks += 1
-                i = j
+            x = d._guarded_loop(run, x, plan.start, guard, hist, inplace=d.noise_source == "device",
+                                any_rank=lambda tripped: any_rank(tripped, dev), owner=self)
         if decode and self.vae is not None:
             if e > s:
                 _, u8 = self.vae.native().decode(x, want_img=False, want_u8=True)

@@ -220,19 +220,13 @@ def save_reverse_steps_for_csv_row(
         writer = FrameWriter(device_t, (8 * H, 8 * W, 3), (z_shape[1], H, W), pixel_dir, latent_dir)
     bar = tqdm(total=num_timesteps, desc=f"Reverse diffusion (row={row_index})") if progress else None
     device_loop = native and noise_source == "device" and guidance_scale and guidance_scale > 0
+    plan = diffuser._plan(x, None, guidance_scale)  # the DDPM walk with CFG
     if device_loop:
-        nm = model_noise.native()
-        x_state = x.contiguous().clone()  # stepped in place: the captured graph keeps its pointer
-        t_dev = torch.full((1,), num_timesteps, device=device_t, dtype=torch.long)
-        tables = diffuser.coef_tables(device_t, clamp_prev=True)
-        seed = diffuser._seed()
-        v, m = vals.float().contiguous(), mask.float().contiguous()
+        x = x.contiguous().clone()  # stepped in place: the captured graph keeps its pointer
+        step_one = diffuser._device_chunks(model_noise.native(), plan, x, y, null_label, vals.float().contiguous(),
+                                           mask.float().contiguous(), None, diffuser._seed())
 
     def run(i_from, i_to, x):
-        if device_loop:
-            if x is not x_state:
-                x_state.copy_(x)
-            x = x_state
         for i in range(i_from, i_to, -1):
             # save (before denoising = x_t), generate_steps.py:162-174
             if i in save_set:
@@ -241,17 +235,18 @@ def save_reverse_steps_for_csv_row(
                 else:
                     _save_sync(x, vae, diffuser, i, pixel_dir, latent_dir)
             if device_loop:  # one graph-replayed step, t decremented on the device
-                t_dev.fill_(i)
-                nm.sample_loop(x, t_dev, y, null_label, v, m, float(guidance_scale), tables, 1, seed=seed)
+                x = step_one(i, i - 1, x)
             else:  # generate_steps.py:179-189 (i in [1, T]: denoise_cond's range assert holds)
                 t = torch.full((B,), i, device=device_t, dtype=torch.long)
-                x = diffuser._denoise_cond(model_noise, x, t, y, guidance_scale, null_label, vals, mask)
+                x = diffuser._step(model_noise, x, t, plan, True, y, null_label, vals, mask)
             if bar is not None:
                 bar.update(1)
-        return x.clone() if device_loop else x  # the guard keeps the chunk's input for a replay
+        return x
 
     try:
-        x = diffuser._guarded_host_loop(model_noise, x, run, on_replay=writer.drain if writer else None)
+        x = diffuser._guarded_loop(diffuser._prefetching(run, model_noise, x), x, num_timesteps,
+                                   diffuser._guard_target(model_noise, x), inplace=device_loop,
+                                   on_replay=writer.drain if writer else None)
     finally:
         if writer is not None:
             writer.close()

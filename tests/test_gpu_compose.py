@@ -572,14 +572,17 @@ def test_foreign_model_composed_step_vs_oracle(model, cuda, unet_sd, kind):
     if kind == "ddpm":
         _, a, ab = ref.schedule(1000)
         exp = ref.ddpm_update(x, eps, t, a, ab, nz)
-        out = d._denoise_cond(Foreign(), x.to(cuda), t.to(cuda), compose=to(comp, cuda))
+        plan = diff._SamplerPlan("ddpm", tables=d.coef_tables(cuda, clamp_prev=True), compose=to(comp, cuda))
+        out = d._step(Foreign(), x.to(cuda), t.to(cuda), plan, True)
     elif kind == "ddim":
         exp = ddim_update_ref(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
-        out = d._ddim_step(Foreign(), x.to(cuda), pos.to(cuda), d.ddim_tables(5, 0.5, cuda), True, compose=to(comp, cuda))
+        plan = diff._SamplerPlan("ddim", sched=d.ddim_tables(5, 0.5, cuda), draws=True, compose=to(comp, cuda))
+        out = d._step(Foreign(), x.to(cuda), pos.to(cuda), plan, True)
     else:
         exp, exp_h = dpm_update_ref(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
         h = hist.to(cuda)
-        out = d._dpm_step(Foreign(), x.to(cuda), pos.to(cuda), d.dpm_tables(5, "uniform", cuda), h, compose=to(comp, cuda))
+        plan = diff._SamplerPlan("dpm", sched=d.dpm_tables(5, "uniform", cuda), draws=False, compose=to(comp, cuda))
+        out = d._step(Foreign(), x.to(cuda), pos.to(cuda), plan, True, hist=h)
         assert rel(h, exp_h) <= TOL
     assert calls == comp[0].tolist()    # K + 1 calls, one per branch, in branch order
     err = rel(out, exp)
