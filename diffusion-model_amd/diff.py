@@ -30,6 +30,9 @@ What changes is where the work happens:
   guidance_rescale=phi)`` applies CFG only to the steps whose timestep lies in the interval — the others
   are one conditional forward — and scales the guided prediction to the conditional one's per-sample
   standard deviation (libdmx ``dmx_step_guided`` / ``dmx_cfg_rescale``).
+* Geometry guidance (not in the reference): ``sample_latent_cond(..., geom_scale=s)`` adds the input
+  gradient of the GeomHead's masked regression loss against the call's own condition to every step's
+  guided prediction (classifier guidance; libdmx ``dmx_step_geom`` / ``dmx_geom_mix``).
 """
 from __future__ import annotations
 
@@ -126,6 +129,7 @@ class _SamplerPlan:
     run_g: object = True                   # guided positions: True (all), (p_lo, p_hi) or None (_guided_run)
     known: Optional[tuple] = None          # the known-region blend's operands (engine.known_blend)
     compose: Optional[tuple] = None        # the composed step's branch tables, contiguous on the device
+    geom: Optional[tuple] = None           # geometry guidance: (scale row (B,), sig table) on the device
     rows: Optional[Tuple[int, int]] = None  # a shard: the rows [s, e) of the global batch
     x_start: Optional[torch.Tensor] = None  # the latent the loop starts from
 
@@ -166,6 +170,8 @@ class _SamplerPlan:
             kw["rescale"] = self.rescale
         if self.compose is not None:
             kw["compose"] = self.compose
+        if guided and self.geom is not None:
+            kw["geom"] = self.geom
         return kw
 
 
@@ -429,6 +435,68 @@ class Diffuser:
             raise ValueError("guidance_interval / guidance_rescale need guidance_scale > 0 "
                              f"(got guidance_scale={guidance_scale!r})")
         return interval, phi
+
+    # ---- geometry guidance: the GeomHead's input gradient joins the guided prediction -----------
+    @classmethod
+    def _geom_args(cls, geom_scale, B, model=None, guidance_scale=None, guidance_interval=None,
+                   guidance_rescale=0.0, base="null", also=None, cond=None):
+        """Argument rules of the samplers' geom_scale keyword -> None (0, or B zeros: the call is the
+        plain one) or the (B,) fp32 scale row on the CPU.  geom_scale is a float or B finite floats,
+        all >= 0.  A non-zero scale needs a model with a GeomHead (a dmx network must be
+        UnetCondWithGeomHead; a foreign model is asked at its first step), a scalar guidance_scale > 0,
+        no guidance_interval / guidance_rescale / base / also, and a condition (`cond`) to aim at — a
+        row whose mask is all zero is allowed and takes no guidance.  Every violation raises ValueError."""
+        row = cls._weight_row(geom_scale, B, "geom_scale")
+        if bool((row < 0).any()):
+            raise ValueError(f"geom_scale must be >= 0 (got {geom_scale!r})")
+        if not bool((row != 0).any()):
+            return None
+        if model is not None and hasattr(model, "native") and _native_kind(model) != 1:
+            raise ValueError("geom_scale needs a model with a GeomHead (UnetCondWithGeomHead)")
+        if cls._per_sample(guidance_scale):
+            raise ValueError("geom_scale takes a scalar guidance_scale (no per-sample scale)")
+        try:
+            ok = guidance_scale is not None and float(guidance_scale) > 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"geom_scale needs guidance_scale > 0 (got guidance_scale={guidance_scale!r})")
+        try:
+            phi = float(guidance_rescale)
+        except (TypeError, ValueError):
+            phi = float("nan")
+        if guidance_interval is not None or phi != 0.0:
+            raise ValueError("geom_scale takes no guidance_interval / guidance_rescale")
+        if not (isinstance(base, str) and base == "null") or also:
+            raise ValueError("geom_scale takes no composed guidance (base / also)")
+        if cond is None:
+            raise ValueError("geom_scale needs a condition to aim at (cond is None)")
+        return row
+
+    def geom_sig(self, device):
+        """sqrt(1 - alpha_bar[t]) at index t - 1, fp32 from the fp32 alpha_bars: the sig table of a
+        geometry-guided DDPM step (the strided rules use their schedule's k_e, the same quantity per position)."""
+        cache = self.__dict__.setdefault("_geom_sig", {})
+        if str(device) not in cache:
+            cache[str(device)] = torch.sqrt(1 - self._host[1]).contiguous().to(device)
+        return cache[str(device)]
+
+    @staticmethod
+    def _geom_loss_grad(model, x, t, y, cond_vals, cond_mask):
+        """A foreign model's geometry-guidance gradient dL/dx, from torch autograd over its own forward
+        (x a leaf, grad mode on): L = sum_n sum_j m_nj (geom_nj - v_nj)^2 / max(sum_j m_nj, 1e-6).  The
+        forward must return (eps, geom)."""
+        if cond_vals is None or cond_mask is None:
+            raise ValueError("geom_scale needs cond_vals and cond_mask")
+        with torch.enable_grad():
+            xl = x.detach().clone().requires_grad_(True)
+            out = model(xl, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
+            if not isinstance(out, (tuple, list)) or len(out) < 2 or not isinstance(out[1], torch.Tensor):
+                raise ValueError("geom_scale needs a model whose forward returns (eps, geom)")
+            m = cond_mask.to(out[1].dtype)
+            loss = ((m * (out[1] - cond_vals).pow(2)).sum(-1) / m.sum(-1).clamp_min(1e-6)).sum()
+            grad, = torch.autograd.grad(loss, xl)
+        return grad.detach()
 
     # ---- composed guidance: K weighted condition branches over a chosen base -------------------
     COMPOSE_MAX = 4  # extra branches over the base (include/dmx.h DMX_COMPOSE_MAX)
@@ -712,6 +780,9 @@ class Diffuser:
             t = pos if rule == "ddpm" else plan.sched[0][pos - 1]
             if not mirror:
                 eu, ec, g = self._eps(model, x, t, y, null_label, cond_vals, cond_mask, g, plan.rescale, compose)
+                if plan.geom is not None and ec is not None:  # the guided eps, then the gradient's share
+                    grad = self._geom_loss_grad(model, x, t, y, cond_vals, cond_mask)
+                    eu, ec, g = _engine.geom_mix(eu + g * (ec - eu), grad, plan.geom[0], plan.geom[1], pos), None, 0.0
             elif y is None:  # diff.py:152-156 literally, including its UnboundLocalError when y is given
                 y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
                 eu, ec = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask), None
@@ -991,6 +1062,7 @@ class Diffuser:
         guidance_rescale: float = 0.0,
         base="null",
         also=None,
+        geom_scale=0.0,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -1031,7 +1103,17 @@ class Diffuser:
         B finite floats (a per-sample guidance scale); also = up to three condition specs, each a dict
         {"classes": int or B ints, "cond": .., "cond_mask": .. (every form `cond` takes), "weight": float
         or B floats}.  With base "null", no `also` and a scalar guidance_scale the call is the plain one.
-        A composed call takes no guidance_interval / guidance_rescale; the draw order is unchanged."""
+        A composed call takes no guidance_interval / guidance_rescale; the draw order is unchanged.
+
+        geom_scale = s (a float or B finite floats, >= 0; UnetCondWithGeomHead, or a foreign model whose
+        forward returns (eps, geom)), with any sampler, init_latent and mask: geometry guidance
+        (classifier guidance, Dhariwal & Nichol 2021 §4.1).  Every step adds s sqrt(1 - ab_t) dL/dx_t
+        to its CFG-guided prediction, L the GeomHead's masked squared error against the call's own
+        cond / cond_mask per sample — it pulls the sample towards the numbers it is conditioned on.  A
+        step then costs the CFG forward plus a taped forward and a data-only backward of B rows.  It
+        needs a scalar guidance_scale > 0 and `cond`, and takes no guidance_interval, guidance_rescale,
+        base or also; a row whose mask is all zero is not guided.  0 (the default) is the call without
+        the keyword; the draw order is unchanged."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         composed = (not (isinstance(base, str) and base == "null")) or bool(also) or self._per_sample(guidance_scale)
         interval, phi = self._guidance_args(None if composed else guidance_scale,
@@ -1043,6 +1125,8 @@ class Diffuser:
         for cls, num in items:
             y_list += [cls] * num
         B = len(y_list)
+        geom = self._geom_args(geom_scale, B, model, guidance_scale, guidance_interval, guidance_rescale, base, also,
+                               cond)
         y = torch.tensor(y_list, device=device, dtype=torch.long)
         vals, msk = self._build_cond(y_list, cond, cond_mask, key_order, class_keys, device)
         compose = self._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval,
@@ -1061,7 +1145,7 @@ class Diffuser:
         x = self._randn((B, C, Hlat, Wlat), device)
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
                                 known=known[:3] if known is not None else None, interval=interval, rescale=phi,
-                                compose=compose)
+                                compose=compose, **({} if geom is None else dict(geom=geom)))
         if vae is None:
             return x
         if torch.cuda.is_available():
@@ -1069,7 +1153,7 @@ class Diffuser:
         return self._decode(vae, x, to_pil)
 
     def _plan(self, x, mode, guidance_scale, known=None, interval=None, rescale=0.0, compose=None,
-              rows=None) -> _SamplerPlan:
+              rows=None, geom=None) -> _SamplerPlan:
         """The plan of a sampling call whose x_T draw is x, on x's device.
         mode: _sampler_mode's result.  interval, rescale: _guidance_args' (t_lo, t_hi) or None and phi.
         compose: _compose_args' tables or None; a composed plan has no scale, interval or rescale.
@@ -1078,7 +1162,9 @@ class Diffuser:
         the blend's kn one table row up (position p0 + 1 arrives at tau_p0), written to a new tensor;
         without a mask no step is blended.
         rows = (s, e): a shard — x holds the rows [s, e) of the global draw, and the plan takes those
-        rows of z0 and the mask and the columns [:, s:e] of the compose tables."""
+        rows of z0 and the mask and the columns [:, s:e] of the compose tables.
+        geom: _geom_args' scale row or None; the plan carries its rows and the sig table of the rule
+        (geom_sig for ddpm, the schedule's k_e otherwise), converted once: a loop's graphs hold their pointers."""
         dev = x.device
         rule = "ddpm" if mode is None else mode[0]
         tau = self._mode_timesteps(mode)
@@ -1111,6 +1197,9 @@ class Diffuser:
             plan.sched = self.ddim_tables(mode[1], mode[2], dev)
         else:  # (a loop entering at p0 < S: that row is first-order)
             plan.sched = self.dpm_tables(mode[1], mode[2], dev, plan.start if known is not None else None)
+        if geom is not None:
+            sig = self.geom_sig(dev) if rule == "ddpm" else plan.sched[1]
+            plan.geom = (geom[cut].to(device=dev, dtype=torch.float32).contiguous(), sig)
         return plan
 
     def _device_chunks(self, nm, plan, x, y, null_label, vals, msk, hist, seed, bar=None):
@@ -1131,13 +1220,13 @@ class Diffuser:
         return run
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
-                       interval=None, rescale=0.0, compose=None):
+                       interval=None, rescale=0.0, compose=None, geom=None):
         """The T loop (diff.py:328-344) over the call's plan (_plan), range-guarded in chunks
         (_guarded_loop): the counter walks timesteps, or the positions of a strided schedule, down
         from plan.start, and a replayed chunk restarts from the x and the solver history it started
         with.  A dmx network with guidance (or a composed call) in device-noise mode runs whole chunks
         on the device (_device_chunks); every other case steps on the host (_step)."""
-        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose)
+        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom)
         x = plan.x_start
         hist = plan.new_hist(x)
         guard = self._guard_target(model, x)

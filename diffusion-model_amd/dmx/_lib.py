@@ -80,6 +80,11 @@ class Compose(ctypes.Structure):
                 ("weight", ctypes.c_void_p)]
 
 
+class GeomGuide(ctypes.Structure):
+    """dmx_geom_guide (include/dmx.h): per-sample scales and the per-position sqrt(1 - ab) table of geometry guidance."""
+    _fields_ = [("scale", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("S", ctypes.c_int)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -121,6 +126,7 @@ SIGNATURES = [
     ("dmx_model_refresh", _I, [_P, _P]),
     ("dmx_train_forward", _I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, ctypes.POINTER(_I64), _P]),
     ("dmx_train_backward", _I, [_P, _I64, _P, _P, ctypes.POINTER(_P), _I, _P]),
+    ("dmx_train_backward_input", _I, [_P, _I64, _P, _P, _P, _P]),
     ("dmx_model_set_precision", _I, [_P, _I]),
     ("dmx_model_get_precision", _I, [_P]),
     ("dmx_model_range_check", _I, [_P, _I, ctypes.POINTER(_I), _P]),
@@ -153,6 +159,12 @@ SIGNATURES = [
                                       ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
                                       ctypes.POINTER(Compose), _I, _I, _P]),
     ("dmx_compose_eps", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("dmx_step_geom", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                           ctypes.POINTER(KnownSched), ctypes.POINTER(GeomGuide), _P]),
+    ("dmx_sample_loop_geom", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                                  ctypes.POINTER(KnownSched), ctypes.POINTER(GeomGuide), _I, _I, _P]),
+    ("dmx_geom_mix", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    ("dmx_geom_seed", _I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     ("dmx_model_graph_captures", _I64, [_P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -796,6 +796,7 @@ struct Run {
   // non-null: the next gemm() runs the split-precision implicit GEMM with A scaled on the device by
   // this max|A| slot (training data gradients, train_engine.h dgrad)
   bool fwd_x3 = false;  // training forward: weights with device-split planes (ConvW::inv_dev) run the split GEMM
+  bool data_only = false;  // training backward: data gradients alone, down to the input (train_engine.h)
   bool colsum_defer = false;               // training backward: final-level column sums batched (train_engine.h)
   std::vector<ColsumJob> colsums;
   const unsigned* a_amax = nullptr;
@@ -2053,8 +2054,8 @@ static void vae_enc_body(Run& R, const float* x, const float* eps, float* z, flo
 
 }  // namespace dmx
 
+#include "train_engine.h"  // (before the sampler: a geometry-guided step runs the taped forward and backward)
 #include "sample_engine.h"
-#include "train_engine.h"
 #include "vae_train_engine.h"
 
 // ===========================================================================
@@ -2286,6 +2287,22 @@ int dmx_train_backward(dmx_model* m, int64_t tape_id, const float* d_eps, const 
   });
 }
 
+int dmx_train_backward_input(dmx_model* m, int64_t tape_id, const float* d_eps, const float* d_geom, float* d_x,
+                             void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr && d_x != nullptr, "null argument");
+    REQUIRE(m->tape != nullptr && m->tape->id != 0, "no training forward recorded (dmx_train_forward)");
+    REQUIRE(tape_id == m->tape->id,
+            "stale tape: another dmx_train_forward ran after the one this backward belongs to");
+    REQUIRE(d_geom == nullptr || m->kind == DMX_UNET_COND_GEOM, "d_geom only for UnetCondWithGeomHead");
+    hipStream_t st = (hipStream_t)stream;
+    with_fp32(m, [&] {
+      run_arena(m, st, m->bws, m->bws_mem, m->bws_cap,
+                [&](Run& R) { train_bwd_body(R, *m->tape, GradMap{}, d_eps, d_geom, d_x); });
+    });
+  });
+}
+
 int dmx_vae_train_forward(dmx_model* m, const float* x, const float* eps, int n, int h, int w, float* x_recon, float* z,
                           float* kl, int64_t* tape_id, void* stream) {
   return guarded([&] {
@@ -2510,6 +2527,48 @@ int dmx_compose_eps(const float* e, const float* weight, int K, int n, int c, in
     const int64_t chw = (int64_t)c * h * w;
     REQUIRE((double)n * (double)chw < 549755813888.0, "too many elements");
     launch_compose_eps(e, weight, K, n, chw, eps_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_step_geom(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                  const dmx_known_sched* known, const dmx_geom_guide* geom, void* stream) {
+  return guarded([&] {
+    REQUIRE(geom != nullptr, "null geometry guidance");
+    sample_step(m, a, StepMode{ddim, dpm, known, nullptr, nullptr, geom}, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop_geom(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                         const dmx_known_sched* known, const dmx_geom_guide* geom, int steps, int use_graph,
+                         void* stream) {
+  return guarded([&] {
+    REQUIRE(geom != nullptr, "null geometry guidance");
+    sample_loop(m, a, StepMode{ddim, dpm, known, nullptr, nullptr, geom}, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_geom_mix(const float* eps, const float* grad, const float* scale, const float* sig, int S,
+                 const int64_t* pos, int pos_stride, float* eps_out, int n, int c, int h, int w, void* stream) {
+  return guarded([&] {
+    REQUIRE(eps && grad && scale && sig && pos && eps_out, "null tensor");
+    REQUIRE(S >= 1, "sig needs S >= 1 positions");
+    REQUIRE(n >= 1 && c >= 1 && h >= 1 && w >= 1, "bad shape");
+    REQUIRE(pos_stride == 0 || pos_stride == 1, "pos_stride must be 0 or 1");
+    const int64_t chw = (int64_t)c * h * w;
+    REQUIRE((double)n * (double)chw < 549755813888.0, "too many elements");
+    launch_geom_mix(eps, grad, dmx_geom_guide{scale, sig, S}, pos, pos_stride, n, chw, eps_out, nullptr,
+                    (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_geom_seed(const float* geom, const float* vals, const float* mask, int n, int gd, float* loss_out,
+                  float* seed_out, void* stream) {
+  return guarded([&] {
+    REQUIRE(geom && vals && mask && seed_out, "null tensor");
+    REQUIRE(n >= 1 && gd >= 1, "bad shape");
+    launch_geom_seed(geom, vals, mask, n, gd, loss_out, seed_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
   });
 }

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dmx.h"
 #include "igemm.h"
 #include "igemm_x3.h"
 #include "tail_math.h"
@@ -85,5 +86,14 @@ void launch_compose_tail4(const StepTailParams& p, const ComposeParams& q, bool 
                           hipStream_t st);
 // the mix alone: e [(K+1)][n][chw], weight [K][n] -> eps [n][chw]; n * chw < 2^39
 void launch_compose_eps(const float* e, const float* weight, int K, int n, int64_t chw, float* eps, hipStream_t st);
+// Geometry guidance (geom.h), k_geom.hip.
+// loss [n] (or null) and seed [n][gd] = dL_n / dgeom of the masked regression loss on geom against vals / mask [n][gd]
+void launch_geom_seed(const float* geom, const float* vals, const float* mask, int n, int gd, float* loss, float* seed,
+                      hipStream_t st);
+// eps_out = eps + (scale[n] * sig[pos - 1]) * grad over [n][chw]; n * chw < 2^39; eps_out may alias eps
+void launch_geom_mix(const float* eps, const float* grad, const dmx_geom_guide& gg, const int64_t* pos, int pos_stride,
+                     int n, int64_t chw, float* eps_out, int* range_flag, hipStream_t st);
+// dx (NCHW [n][Ci][H][W]) = the data gradient of the first 3x3 conv (weight [64][Ci][3][3]) from dr (NHWC, 64 channels)
+void launch_conv0_dgrad(const float* dr, const float* w, int Ci, int n, int H, int W, float* dx, hipStream_t st);
 
 }  // namespace dmx

@@ -85,12 +85,17 @@ struct GraphStep {
 // known-region blend follows the tail as a launch of its own, on a.x_out in place, at the position
 // the tail read.  A composed step (mode.comp) runs K + 1 branch-major rows through the trunk and the
 // composed tail; with Co < 4 the head, the mix and the update are three launches whose predictions
-// come from the arena.
+// come from the arena.  A geometry-guided step (mode.geom; geom.h) runs, after the trunk, the taped
+// training forward of the B conditional rows, the loss seed and the data-only backward
+// (train_engine.h) in the same arena — nothing is allocated outside the plan, so the step captures
+// like any other — then materialises the CFG eps as the rescaled step does, mixes the input
+// gradient into it and runs the rule's tail on the mixed eps.
 static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, GraphStep gs = {}) {
   dmx_model* m = R.m;
   const dmx_compose* comp = mode.comp;
   const bool cfg = comp == nullptr && m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
   const bool resc = mode.rescale() > 0.f;
+  const dmx_geom_guide* gg = mode.geom;
   const Rule rule = mode.rule();
   const int N = comp != nullptr ? (comp->K + 1) * a.n : cfg ? 2 * a.n : a.n;
   FwdIn in{a.x_in, a.n, a.t, a.t_stride, a.y, cfg ? 1 : 0, a.null_label, a.vals, a.mask, a.n};
@@ -110,11 +115,44 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   float* feat = unet_trunk(R, in, N, a.h, a.w);
   const int pixb = m->in_ch == 4 ? 16 : 256;  // pixels per block of the rescaled tail's first stage
   const int nb = cdiv(a.h * a.w, pixb);
-  float* eg = resc ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
-  double* part = resc ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
+  const bool mat = resc || gg != nullptr;  // the guided eps goes through the arena
+  float* eg = mat ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
+  double* part = mat ? R.ws.get<double>((size_t)a.n * nb * 4) : nullptr;
   const bool comp3 = comp != nullptr && m->in_ch != 4;  // head, mix, update as three launches
   float* eall = comp3 ? R.ws.get<float>((size_t)N * m->in_ch * a.h * a.w) : nullptr;
   float* emix = comp3 ? R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w) : nullptr;
+  float* gx = nullptr;  // dL/dx of a geometry-guided step
+  if (gg != nullptr) {
+    const int gd = m->cfg.gdim;
+    gx = R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w);
+    float* teps = R.ws.get<float>((size_t)a.n * m->in_ch * a.h * a.w);
+    float* geom = R.ws.get<float>((size_t)a.n * gd);
+    float* seed = R.ws.get<float>((size_t)a.n * gd);
+    // The model's training tape is replaced (its record now points into this arena) under an id no
+    // caller holds: a backward pending on an earlier forward is refused as stale.
+    if (m->tape == nullptr) m->tape = new Tape();
+    Tape& T = *m->tape;
+    T.id = 0;
+    TrainArgs ta{a.x_in, a.t, a.y, a.vals, a.mask, a.n, a.h, a.w, teps, geom, a.t_stride, mode.t_map(),
+                 mode.positions(a)};
+    const std::string layer = R.layer;
+    with_fp32(m, [&] {
+      train_fwd_body(R, T, ta);
+      R.fwd_x3 = false;
+      if (!R.plan) {
+        R.layer = "geom.seed";
+        R.begin("geom_seed_kernel", 6.0 * a.n * gd, 4.0 * 5.0 * a.n * gd);
+        launch_geom_seed(geom, a.vals, a.mask, a.n, gd, nullptr, seed, R.st);
+        R.end();
+        HIPCHK(hipGetLastError());
+      }
+      train_bwd_body(R, T, GradMap{}, nullptr, seed, gx);
+    });
+    R.amax_src = nullptr;
+    R.amax_uses = 0;
+    R.layer = layer;
+    if (!R.plan) T.id = ++m->tape_id;
+  }
   if (R.plan) return;
   StepTailParams p;
   std::memset(&p, 0, sizeof(p));
@@ -169,14 +207,19 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
       R.begin("step_tail_kernel", 8.0 * el, 4.0 * 4.0 * el);
       launch_step_tail(p, rule, false, dim3(cdiv(p.HW, 256), a.n), R.st);
     }
-  } else if (resc) {
+  } else if (mat) {
     R.begin(p.Co == 4 ? "cfg_stats4_kernel" : "cfg_stats_kernel", head_flops, 4.0 * ((double)N * p.HW * 64 + el));
     CfgHeadParams hp{p.feat, p.w, p.b, p.Co, p.B, p.HW, p.guidance, p.range_flag};
     launch_cfg_stats(hp, eg, part, nb, R.st);
     R.end();
     HIPCHK(hipGetLastError());
-    R.begin("cfg_scale_kernel", el, 8.0 * el);
-    launch_cfg_scale(eg, part, nb, pixb, p.Co, p.HW, a.n, mode.rescale(), nullptr, R.st);
+    if (resc) {
+      R.begin("cfg_scale_kernel", el, 8.0 * el);
+      launch_cfg_scale(eg, part, nb, pixb, p.Co, p.HW, a.n, mode.rescale(), nullptr, R.st);
+    } else {  // (the block moments of the stats kernel are not read here)
+      R.begin("geom_mix_kernel", 3.0 * el, 12.0 * el);
+      launch_geom_mix(eg, gx, *gg, a.t, a.t_stride, a.n, (int64_t)p.Co * p.HW, eg, p.range_flag, R.st);
+    }
     R.end();
     HIPCHK(hipGetLastError());
     // the update on the scaled eg: the tail's precomputed-eps form (it raises the range flag on it)
@@ -250,6 +293,19 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
       REQUIRE(a->n <= 65535, "rescaled steps take at most 65535 samples");
     }
   }
+  if (mode.geom != nullptr) {
+    const dmx_geom_guide& g = *mode.geom;
+    REQUIRE(g.scale != nullptr && g.sig != nullptr, "geometry guidance needs the scale and sig tables");
+    REQUIRE(m->kind == DMX_UNET_COND_GEOM, "geometry guidance needs a model with a GeomHead");
+    REQUIRE(mode.comp == nullptr, "geometry guidance takes no composition");
+    REQUIRE(mode.rescale() == 0.f, "geometry guidance takes no guidance rescale");
+    REQUIRE(a->guidance > 0.f && a->y != nullptr, "geometry guidance needs a CFG step (guidance > 0, y given)");
+    REQUIRE(a->vals != nullptr && a->mask != nullptr, "geometry guidance needs vals and mask (its target)");
+    REQUIRE(g.S == mode.positions(*a), "geometry guidance S differs from the schedule's");
+    REQUIRE(a->n <= 65535, "geometry-guided steps take at most 65535 samples");
+    const void* xo = a->x_out;
+    REQUIRE(g.scale != xo && g.sig != xo, "geometry guidance tables must not alias x_out");
+  }
   REQUIRE(mode.ddim == nullptr || mode.dpm == nullptr, "at most one of the DDIM and DPM schedules");
   if (mode.ddim != nullptr) check_sched(mode.ddim);
   if (mode.dpm != nullptr) check_sched(mode.dpm);
@@ -285,6 +341,7 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
 static void sample_step(dmx_model* m, const dmx_step_args* a, const StepMode& mode, hipStream_t st) {
   validate(m, a, mode, false);
   ensure_planes(m, st);
+  if (mode.geom != nullptr) ensure_train(m, st);
   run_planned(m, st, [&](Run& R) { step_body(R, *a, mode); });
 }
 
@@ -321,6 +378,7 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
   validate(m, a, mode, true);
   REQUIRE(steps >= 0, "steps must be >= 0");
   ensure_planes(m, st);
+  if (mode.geom != nullptr) ensure_train(m, st);  // (packs and synchronises: before any capture)
   int64_t* tdev = const_cast<int64_t*>(a->t);
   if (!use_graph) {
     for (int i = 0; i < steps; ++i) {

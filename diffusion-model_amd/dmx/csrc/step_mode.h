@@ -18,6 +18,7 @@ struct StepMode {
   const dmx_guidance* gd = nullptr;        // guidance controls beyond the scale
   const dmx_compose* comp = nullptr;       // composed guidance: K + 1 branches; a.y / vals / mask / guidance /
                                            // null_label are not read
+  const dmx_geom_guide* geom = nullptr;    // geometry guidance: the GeomHead's input gradient joins the CFG eps
 
   Rule rule() const { return dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM; }
   // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
@@ -36,6 +37,7 @@ struct GraphKey {
   dmx_known_sched known; // known-region loops: z0, e0, mask, tables and S (all zero otherwise)
   dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
   dmx_compose comp;      // composed loops: K and the four tables (all zero otherwise)
+  dmx_geom_guide geom;   // geometry-guided loops: the two tables and S (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
@@ -43,7 +45,8 @@ struct GraphKey {
 // The key of a loop: everything its graphs hold.  The step args enter as the caller's bytes; the
 // optional structs enter member by member, so their padding stays zero.  A validated schedule has
 // S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart;
-// a validated composition has K >= 1, which keeps composed keys from plain ones.
+// a validated composition has K >= 1, which keeps composed keys from plain ones; validated geometry
+// guidance has non-null tables and S >= 1, which keeps its keys from plain ones.
 inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen) {
   GraphKey key;
   std::memset(&key, 0, sizeof(key));
@@ -90,6 +93,11 @@ inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int
     key.comp.vals = mode.comp->vals;
     key.comp.mask = mode.comp->mask;
     key.comp.weight = mode.comp->weight;
+  }
+  if (mode.geom != nullptr) {  // the seed, backward and mix launches are in the graphs too
+    key.geom.scale = mode.geom->scale;
+    key.geom.sig = mode.geom->sig;
+    key.geom.S = mode.geom->S;
   }
   key.table_gen = table_gen;
   return key;

@@ -1141,10 +1141,17 @@ static __global__ void gap_bwd_kernel(const float* dg, int N, int HW, float* dfe
 
 // Embedding (models/unet_cond.py:155-167): emb[n] = pos(t_n) + class_emb[y_n] (+ cond, added by the
 // host sequence); dclass[c][k] = sum over samples with y_n == c of demb[n][k] (sample order).
-static __global__ void embed_base_kernel(const int64_t* t, const int64_t* y, const float* pos_table, int tmax,
+// t_map non-null: t holds positions in [1, n_pos] of a strided schedule and the timestep is
+// t_map[position - 1]; t_stride 0: one value for every sample (the samplers' position scalar).
+static __global__ void embed_base_kernel(const int64_t* t, int t_stride, const int64_t* t_map, int n_pos,
+                                         const int64_t* y, const float* pos_table, int tmax,
                                          const float* class_emb, int ncls, float* emb) {
   const int n = blockIdx.x, k = threadIdx.x;
-  int64_t tt = t[n];
+  int64_t tt = t[(size_t)n * t_stride];
+  if (t_map != nullptr) {
+    tt = tt < 1 ? 1 : (tt > n_pos ? n_pos : tt);
+    tt = t_map[tt - 1];
+  }
   tt = tt < 1 ? 1 : (tt > tmax ? tmax : tt);
   float v = pos_table[(size_t)(tt - 1) * 256 + k];
   if (y != nullptr) {

@@ -78,6 +78,12 @@ struct GradMap {
     return it->second;
   }
 };
+// The destination of a parameter gradient, or null in the data-only backward (Run::data_only), which
+// never consults the map: wgrad / dense_dw / zero_grad launch nothing there, and the adjoint kernels
+// that produce affine sums as a by-product leave them in their arena scratch.
+static float* gdst(const Run& R, const GradMap& G, const std::string& name) {
+  return R.data_only ? nullptr : G(name);
+}
 
 // Workspace run twice (plan: sizes only, then real) in a dedicated arena.
 template <typename F>
@@ -331,6 +337,9 @@ struct TrainArgs {
   int n, h, w;
   float* eps;   // NCHW out
   float* geom;  // [n][geom_dim] out (UnetCondWithGeomHead) or null
+  int t_stride = 1;                 // 0: t is one scalar for every sample
+  const int64_t* t_map = nullptr;   // non-null: t holds positions in [1, n_pos], the timestep is
+  int n_pos = 0;                    // t_map[position - 1] (a geometry-guided step of a strided sampler)
 };
 
 static const char* kEmbHeads[6] = {"down1", "down2", "down3", "up1", "up2", "up3"};
@@ -370,8 +379,8 @@ static void train_fwd_body(Run& R, Tape& T, const TrainArgs& a) {
     nchw_to_nhwc_kernel<<<ew_blocks((size_t)N * HW * m->inc.cin), 256, 0, R.st>>>(a.x, T.xin, N, m->in_ch,
                                                                                  m->inc.cin, HW);
     HIPCHK(hipMemcpyAsync(T.y, a.y, (size_t)N * sizeof(int64_t), hipMemcpyDeviceToDevice, R.st));
-    embed_base_kernel<<<N, 256, 0, R.st>>>(a.t, T.y, m->ctx->pos_table, m->ctx->tmax, srcp(m, "class_emb.weight"),
-                                           m->cfg.ncls, T.v0);
+    embed_base_kernel<<<N, 256, 0, R.st>>>(a.t, a.t_stride, a.t_map, a.n_pos, T.y, m->ctx->pos_table, m->ctx->tmax,
+                                           srcp(m, "class_emb.weight"), m->cfg.ncls, T.v0);
     HIPCHK(hipGetLastError());
   }
   if (T.cond) {
@@ -596,6 +605,7 @@ static bool wgrad_fast(int Cin, int Cout) { return Cin % 64 == 0 && Cout % 64 ==
 // H x W map, x on the 2H x 2W map; geo 2 swaps the operands' roles (dy = the layer input, x = dY)
 static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, int Cin, int Cout, int taps,
                   int cin_real, float* grad, float* bias_grad_out = nullptr, int geo = 0) {
+  if (R.data_only) return;  // (no parameter gradient: neither the launches nor their workspace)
   const int M = N * H * W, K = taps * Cin;
   const size_t xel = (size_t)M * Cin * (geo != 0 ? 4 : 1);  // elements of the gathered operand
   if ((geo != 0) != (taps == 16)) throw Error(DMX_E_INTERNAL, "wgrad: 16 taps go with the stride-2 geometries");
@@ -656,6 +666,10 @@ static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, 
 static void dgrad(Run& R, const float* dy, int Cy, int N, int H, int W, const ConvW& dw, float* dx, bool accumulate) {
   int parts = 0;
   const unsigned* amax = dy_amax(R, dy, (size_t)N * H * W * Cy, &parts);
+  if (R.data_only) {  // no wgrad shares the measurement: a later call on this buffer measures again
+    R.amax_src = nullptr;
+    R.amax_uses = 0;
+  }
   R.a_amax = amax;
   R.a_nparts = parts;
   try {
@@ -701,7 +715,7 @@ static void gn_bwd(Run& R, const float* r, const float2* rp, int nseg, int rrows
     R.amax_parts = N * achunks;
     R.amax_uses = amax_uses;
   }
-  colsum_pair(R, chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
+  if (!R.data_only) colsum_pair(R, chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
 }
 
 static void gn_bwd_launch(Run& R, const float* r, const float2* rp, int nseg, int rrows, const Vec& g, const Vec& b,
@@ -758,7 +772,7 @@ static void ln_bwd(Run& R, const float* x, const Vec& w, const float* dy, float*
     R.end();
     HIPCHK(hipGetLastError());
   }
-  colsum_pair(R, part, blocks, C, 2 * (size_t)C, gw, gb);
+  if (!R.data_only) colsum_pair(R, part, blocks, C, 2 * (size_t)C, gw, gb);
 }
 
 // the two MFMA attention-backward launches (train.h); st: [N][4][L][3] — with have_stats, slots 0 / 1
@@ -793,25 +807,27 @@ static void attn_core_bwd(Run& R, const float* qkv, const float* o, const float*
 
 // ResBlock backward: dout -> dx (x's gradient; accumulated when dx_acc), parameter gradients,
 // and the emb slice's per-sample sums into demb (Down / Up second block).
+// dr1_out: where the first conv's output gradient is left for the caller (the input conv's data gradient).
 static void res_bwd(Run& R, const TRes& t, const GradMap& G, const float* dout, float* dx, bool dx_acc, float* demb,
-                    int demb_stride) {
+                    int demb_stride, float** dr1_out = nullptr) {
   const ResW& w = *t.w;
   const int N = t.N, H = t.H, W = t.W, M = N * H * W, HW = H * W, seg = 32;
   const std::string& p = w.prefix;
   float* dr2 = R.ws.get<float>((size_t)M * w.cout);
   gn_bwd(R, t.r2, t.rp2, w.cout / seg, t.rr2, w.g2, w.b2, t.residual ? t.x : nullptr, 0, dout, N, w.cout, HW, dr2,
-         t.residual ? dx : nullptr, t.residual ? (dx_acc ? 2 : 1) : 0, G(p + ".double_conv.4.weight"),
-         G(p + ".double_conv.4.bias"), t.emb_off >= 0 ? demb : nullptr, demb_stride, t.emb_off,
-         (wgrad_fast(w.mid, w.cout) ? 1 : 0) + 1);
-  wgrad(R, dr2, t.a1, N, H, W, w.mid, w.cout, 9, w.mid, G(p + ".double_conv.3.weight"));
+         t.residual ? dx : nullptr, t.residual ? (dx_acc ? 2 : 1) : 0, gdst(R, G, p + ".double_conv.4.weight"),
+         gdst(R, G, p + ".double_conv.4.bias"), t.emb_off >= 0 ? demb : nullptr, demb_stride, t.emb_off,
+         (!R.data_only && wgrad_fast(w.mid, w.cout) ? 1 : 0) + 1);
+  wgrad(R, dr2, t.a1, N, H, W, w.mid, w.cout, 9, w.mid, gdst(R, G, p + ".double_conv.3.weight"));
   float* da1 = R.ws.get<float>((size_t)M * w.mid);
   dgrad(R, dr2, w.cout, N, H, W, w.d2, da1, false);
   float* dr1 = R.ws.get<float>((size_t)M * w.mid);
   gn_bwd(R, t.r1, t.rp1, w.mid / seg, t.rr1, w.g1, w.b1, nullptr, 1, da1, N, w.mid, HW, dr1, nullptr, 0,
-         G(p + ".double_conv.1.weight"), G(p + ".double_conv.1.bias"), nullptr, 0, 0,
-         (wgrad_fast(w.cin, w.mid) ? 1 : 0) + (dx != nullptr ? 1 : 0));
-  wgrad(R, dr1, t.x, N, H, W, w.cin, w.mid, 9, w.cin_real, G(p + ".double_conv.0.weight"));
+         gdst(R, G, p + ".double_conv.1.weight"), gdst(R, G, p + ".double_conv.1.bias"), nullptr, 0, 0,
+         (!R.data_only && wgrad_fast(w.cin, w.mid) ? 1 : 0) + (dx != nullptr ? 1 : 0));
+  wgrad(R, dr1, t.x, N, H, W, w.cin, w.mid, 9, w.cin_real, gdst(R, G, p + ".double_conv.0.weight"));
   if (dx != nullptr) dgrad(R, dr1, w.mid, N, H, W, w.d1, dx, t.residual || dx_acc);
+  if (dr1_out != nullptr) *dr1_out = dr1;
 }
 
 // AttenionBlock backward; dout (the block output's gradient) is consumed (used as scratch).
@@ -820,32 +836,32 @@ static void attn_bwd(Run& R, const TAttn& t, const GradMap& G, float* dout, floa
   const int C = a.c, N = t.N, H = t.H, W = t.W, M = N * H * W, L = H * W;
   const std::string& p = a.prefix;
   // out = ff2(gelu(ff1(al))) + av
-  wgrad(R, dout, t.f, N, H, W, C, C, 1, C, G(p + ".ff_self.3.weight"), G(p + ".ff_self.3.bias"));
+  wgrad(R, dout, t.f, N, H, W, C, C, 1, C, gdst(R, G, p + ".ff_self.3.weight"), gdst(R, G, p + ".ff_self.3.bias"));
   float* dh = R.ws.get<float>((size_t)M * C);
   dgrad(R, dout, C, N, H, W, a.df2, dh, false);
   if (!R.plan) {
     gelu_bwd_kernel<<<ew_blocks((size_t)M * C), 256, 0, R.st>>>(dh, t.h1, dh, (size_t)M * C);
     HIPCHK(hipGetLastError());
   }
-  wgrad(R, dh, t.al, N, H, W, C, C, 1, C, G(p + ".ff_self.1.weight"), G(p + ".ff_self.1.bias"));
+  wgrad(R, dh, t.al, N, H, W, C, C, 1, C, gdst(R, G, p + ".ff_self.1.weight"), gdst(R, G, p + ".ff_self.1.bias"));
   float* dal = R.ws.get<float>((size_t)M * C);
   dgrad(R, dh, C, N, H, W, a.df1, dal, false);
   // al = LN2(av): dav = dout + LN2^T(dal)
-  ln_bwd(R, t.av, a.l2w, dal, dout, true, M, C, G(p + ".ff_self.0.weight"), G(p + ".ff_self.0.bias"));
+  ln_bwd(R, t.av, a.l2w, dal, dout, true, M, C, gdst(R, G, p + ".ff_self.0.weight"), gdst(R, G, p + ".ff_self.0.bias"));
   float* dav = dout;
   // av = out_proj(attn(xl)) + xl
-  wgrad(R, dav, t.ao, N, H, W, C, C, 1, C, G(p + ".mha.out_proj.weight"), G(p + ".mha.out_proj.bias"));
+  wgrad(R, dav, t.ao, N, H, W, C, C, 1, C, gdst(R, G, p + ".mha.out_proj.weight"), gdst(R, G, p + ".mha.out_proj.bias"));
   float* dao = R.ws.get<float>((size_t)M * C);
   dgrad(R, dav, C, N, H, W, a.dout, dao, false);
   float* dqkv = R.ws.get<float>((size_t)M * 3 * C);
   attn_core_bwd(R, t.qkv, t.ao, dao, dqkv, t.st, N, L, C);
-  wgrad(R, dqkv, t.xl, N, H, W, C, 3 * C, 1, C, G(p + ".mha.in_proj_weight"), G(p + ".mha.in_proj_bias"));
+  wgrad(R, dqkv, t.xl, N, H, W, C, 3 * C, 1, C, gdst(R, G, p + ".mha.in_proj_weight"), gdst(R, G, p + ".mha.in_proj_bias"));
   dgrad(R, dqkv, 3 * C, N, H, W, a.dqkv, dav, true);  // dxl = dav + in_proj^T(dqkv)
-  ln_bwd(R, t.x, a.l1w, dav, dx, false, M, C, G(p + ".ln.weight"), G(p + ".ln.bias"));
+  ln_bwd(R, t.x, a.l1w, dav, dx, false, M, C, gdst(R, G, p + ".ln.weight"), gdst(R, G, p + ".ln.bias"));
 }
 
 static void zero_grad(Run& R, const GradMap& G, dmx_model* m, const std::string& name) {
-  if (R.plan) return;
+  if (R.plan || R.data_only) return;
   for (auto& k : m->keys)
     if (k.name == name) {
       size_t n = 1;
@@ -857,6 +873,7 @@ static void zero_grad(Run& R, const GradMap& G, dmx_model* m, const std::string&
 // dW[o][k] = sum_r dY[r][o] x[r][k], db[o] = sum_r dY[r][o]
 static void dense_dw(Run& R, const float* dy, int ldy, const float* x, int ldx, int rows, int O, int K, float* dw,
                      float* db) {
+  if (R.data_only) return;
   small_gemm(R, SmallGemm{dy, x, 1, ldy, ldx, 1, O, K, rows, 0, dw, K, nullptr, 0});
   if (R.plan || db == nullptr) return;
   dense_db_kernel<<<cdiv(O, 256), 256, 0, R.st>>>(dy, ldy, rows, O, db);
@@ -868,9 +885,15 @@ static void dense_dx(Run& R, const float* dy, int ldy, const float* w, int rows,
   small_gemm(R, SmallGemm{dy, w, ldy, 1, K, 1, rows, K, O, 0, dx, ldx, nullptr, accumulate ? 1 : 0});
 }
 
-static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps, const float* d_geom) {
+// d_x == nullptr: every parameter gradient into G.  d_x given (NCHW, the taped x's shape): the
+// data-only backward — the same data-gradient launches in the same order, none of the parameter
+// work (wgrad, dense_dw, zero_grad, the affine and bias column sums, the embedding backward), G never
+// consulted, and the input conv's data gradient (geom.h conv0_dgrad_kernel) at the end.
+static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps, const float* d_geom,
+                           float* d_x = nullptr) {
   dmx_model* m = R.m;
-  R.colsum_defer = !R.plan;  // the final-level column sums run batched at the end (colsum_flush)
+  R.data_only = d_x != nullptr;
+  R.colsum_defer = !R.plan && !R.data_only;  // the final-level column sums run batched at the end (colsum_flush)
   const int N = T.n, H = T.h, W = T.w, HW = H * W, M = N * HW, Co = m->in_ch;
   // heads
   R.layer = "train.heads.bwd";
@@ -884,20 +907,22 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     }
     HIPCHK(hipGetLastError());
   }
-  wgrad(R, dyo, T.feat, N, H, W, 64, Co, 1, 64, G("out.weight"), G("out.bias"));
+  wgrad(R, dyo, T.feat, N, H, W, 64, Co, 1, 64, gdst(R, G, "out.weight"), gdst(R, G, "out.bias"));
   dense_dx(R, dyo, Co, srcp(m, "out.weight"), M, Co, 64, dfeat, 64, false);
   if (m->kind == DMX_UNET_COND_GEOM) {
     const int gh = m->cfg.ghid, gd = m->cfg.gdim;
     float* dhs = R.ws.get<float>((size_t)N * gh);
     float* dg = R.ws.get<float>((size_t)N * 64);
     if (d_geom != nullptr) {
-      dense_dw(R, d_geom, gd, T.hs, gh, N, gd, gh, G("geom_head.mlp.2.weight"), G("geom_head.mlp.2.bias"));
+      dense_dw(R, d_geom, gd, T.hs, gh, N, gd, gh, gdst(R, G, "geom_head.mlp.2.weight"),
+               gdst(R, G, "geom_head.mlp.2.bias"));
       dense_dx(R, d_geom, gd, srcp(m, "geom_head.mlp.2.weight"), N, gd, gh, dhs, gh, false);
       if (!R.plan) {
         silu_bwd_kernel<<<ew_blocks((size_t)N * gh), 256, 0, R.st>>>(dhs, T.hpre, dhs, (size_t)N * gh, 0);
         HIPCHK(hipGetLastError());
       }
-      dense_dw(R, dhs, gh, T.g, 64, N, gh, 64, G("geom_head.mlp.0.weight"), G("geom_head.mlp.0.bias"));
+      dense_dw(R, dhs, gh, T.g, 64, N, gh, 64, gdst(R, G, "geom_head.mlp.0.weight"),
+               gdst(R, G, "geom_head.mlp.0.bias"));
       dense_dx(R, dhs, gh, srcp(m, "geom_head.mlp.0.weight"), N, gh, 64, dg, 64, false);
       if (!R.plan) {
         gap_bwd_kernel<<<ew_blocks((size_t)M * 64), 256, 0, R.st>>>(dg, N, HW, dfeat);
@@ -909,7 +934,8 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
         zero_grad(R, G, m, k);
     }
   }
-  float* demb = R.ws.get<float>((size_t)N * m->hsum);
+  // (the data-only backward needs no embedding gradient: the blocks' emb sums are not formed)
+  float* demb = R.data_only ? nullptr : R.ws.get<float>((size_t)N * m->hsum);
   float* dskip[3];
   for (int i = 0; i < 3; ++i) dskip[i] = R.ws.get<float>((size_t)N * T.sh[i] * T.sw[i] * T.sc[i]);
   // up path, last block first
@@ -959,7 +985,18 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     dcur = dskip[i];
   }
   R.layer = "train.inc.bwd";
-  res_bwd(R, T.inc, G, dcur, nullptr, false, nullptr, 0);
+  float* dr1 = nullptr;
+  res_bwd(R, T.inc, G, dcur, nullptr, false, nullptr, 0, &dr1);
+  if (R.data_only) {
+    if (!R.plan) {
+      R.begin("conv0_dgrad_kernel", 2.0 * M * 9.0 * 64 * Co, 4.0 * ((double)M * 64 + (double)M * Co));
+      launch_conv0_dgrad(dr1, srcp(m, "inc.double_conv.0.weight"), Co, N, H, W, d_x, R.st);
+      R.end();
+      HIPCHK(hipGetLastError());
+    }
+    R.data_only = false;
+    return;
+  }
   // embedding
   R.layer = "train.embed.bwd";
   float* ds = R.ws.get<float>((size_t)N * 256);

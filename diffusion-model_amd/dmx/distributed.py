@@ -172,7 +172,7 @@ class ShardedCondSampler:
                steps: Optional[int] = None, eta: float = 0.0, spacing: Optional[str] = None,
                init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                strength: Optional[float] = None, guidance_interval=None,
-               guidance_rescale: float = 0.0, base="null", also=None) -> Optional[torch.Tensor]:
+               guidance_rescale: float = 0.0, base="null", also=None, geom_scale=0.0) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -208,7 +208,11 @@ class ShardedCondSampler:
 
         base / also and a per-sample guidance_scale as in Diffuser.sample_latent_cond (composed guidance),
         given for the global batch: every rank takes its columns [:, s:e] of the branch tables, and a
-        sample's result does not depend on the shard it sits in beyond the batch class."""
+        sample's result does not depend on the shard it sits in beyond the batch class.
+
+        geom_scale as in Diffuser.sample_latent_cond (geometry guidance), a float or B floats for the
+        global batch: every rank takes its rows of the scale table; the loss and its gradient are per
+        sample, hence shard-local (no collective)."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
@@ -221,6 +225,8 @@ class ShardedCondSampler:
         for cls, num in items:
             y_list += [cls] * num
         B = len(y_list)
+        geom = d._geom_args(geom_scale, B, self.model, guidance_scale, guidance_interval, guidance_rescale, base, also,
+                            cond)
         dev = torch.device(d.device)
         vals, msk = d._build_cond(y_list, cond, cond_mask, None, None, dev)
         compose = d._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval, guidance_rescale,
@@ -241,7 +247,7 @@ class ShardedCondSampler:
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
         # the single-process sampler's plan for this shard's rows; x is its rows of e0
         plan = d._plan(x, mode, guidance_scale, known[:3] if known is not None else None, interval, phi, compose,
-                       rows=(s, e))
+                       rows=(s, e), **({} if geom is None else dict(geom=geom)))
         x = plan.x_start
         hist = plan.new_hist(x)  # shard-local
         if d.noise_source == "device":

@@ -194,6 +194,44 @@ class NativeModel:
         self._live_bwd = (d_eps, d_geom)
         return grads
 
+    def input_grad(self, tape_id: int, d_eps=None, d_geom=None) -> torch.Tensor:
+        """dLoss/dx (n,c,h,w) of the taped forward's x, given dLoss/deps and dLoss/dgeom (None = 0): the
+        data-only backward (include/dmx.h dmx_train_backward_input).  No parameter gradient is computed;
+        a train_backward on the same tape afterwards is unaffected."""
+        live = getattr(self, "_live_train", None)
+        if live is None:
+            raise _lib.DmxError(_lib.DMX_E_ARG, "no training forward recorded (train_forward)")
+        dev = self.device
+        if d_eps is not None:
+            d_eps = d_eps.to(device=dev, dtype=torch.float32).contiguous()
+        if d_geom is not None:
+            d_geom = d_geom.to(device=dev, dtype=torch.float32).contiguous()
+        d_x = torch.empty_like(live[0])
+        with torch.cuda.device(dev):
+            check(self.lib.dmx_train_backward_input(self.handle, int(tape_id), _ptr(d_eps), _ptr(d_geom), _ptr(d_x),
+                                                    ctypes.c_void_p(_stream(dev))))
+        self._live_bwd = (d_eps, d_geom)
+        return d_x
+
+    def geom_grad(self, x, t, y, vals, mask):
+        """The geometry-guidance loss of x at timesteps t and its input gradient ->
+        (loss (n,), grad (n,c,h,w), geom (n,geom_dim), eps): the taped forward of (x, t, y, vals, mask),
+        L_n = sum_j m_nj (geom_nj - v_nj)^2 / max(sum_j m_nj, 1e-6) against the same vals / mask
+        (include/dmx.h dmx_geom_seed) and dL_n/dx by the data-only backward.  Replaces the training tape."""
+        if self.kind != _lib.DMX_UNET_COND_GEOM:
+            raise ValueError("geom_grad needs a model with a GeomHead (UnetCondWithGeomHead)")
+        if vals is None or mask is None:
+            raise ValueError("geom_grad needs cond_vals and cond_mask (the loss's target)")
+        eps, geom, tape = self.train_forward(x, t, y, vals, mask)
+        _, _, _, vals_c, mask_c = self._live_train
+        n = geom.shape[0]
+        loss = torch.empty((n,), device=geom.device, dtype=torch.float32)
+        seed = torch.empty_like(geom)
+        with torch.cuda.device(geom.device):
+            check(self.lib.dmx_geom_seed(_ptr(geom), _ptr(vals_c), _ptr(mask_c), n, self.geom_dim, _ptr(loss),
+                                         _ptr(seed), ctypes.c_void_p(_stream(geom.device))))
+        return loss, self.input_grad(tape, None, seed), geom, eps
+
     def workspace_bytes(self) -> int:
         return int(self.lib.dmx_model_workspace_bytes(self.handle))
 
@@ -340,8 +378,29 @@ class NativeModel:
                             m_c.data_ptr() if m_c is not None else None, w_c.data_ptr())
         return comp, (y_c, v_c, m_c, w_c)
 
+    def _geom(self, x, geom, sched, tables, rescale, compose, guidance, y, vals, mask):
+        """The C view of geom = (scale, sig) for a step on x (n samples): scale (n,) and sig (S,) contiguous
+        fp32 on x's device, S the positions of the step's schedule (the DDPM step: T); nothing is
+        converted, the kernels (and a loop's graphs) read the caller's tensors."""
+        if self.kind != _lib.DMX_UNET_COND_GEOM:
+            raise ValueError("geometry guidance needs a model with a GeomHead (UnetCondWithGeomHead)")
+        if compose is not None or float(rescale) > 0:
+            raise ValueError("a geometry-guided step takes no composition and no guidance rescale")
+        if y is None or not float(guidance) > 0 or vals is None or mask is None:
+            raise ValueError("a geometry-guided step is a CFG step with a condition: it needs y, guidance > 0, "
+                             "vals and mask")
+        if not isinstance(geom, (tuple, list)) or len(geom) != 2:
+            raise ValueError("geom must be the pair (scale, sig)")
+        scale, sig = geom
+        S = int(sched[0].numel()) if sched is not None else int(tables[0].numel())
+        for v, nm, cnt in ((scale, "scale", x.shape[0]), (sig, "sig", S)):
+            if (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 1 or v.numel() != cnt
+                    or not v.is_contiguous() or v.device != x.device):
+                raise ValueError(f"geom {nm} must be a contiguous 1-D fp32 tensor of {cnt} entries on {x.device}")
+        return _lib.GeomGuide(scale.data_ptr(), sig.data_ptr(), S)
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None):
+             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -355,9 +414,17 @@ class NativeModel:
         plain step, launched exactly as without the keyword.
         compose = (y_rows, vals_rows, mask_rows, weights) (include/dmx.h dmx_compose; _compose): composed
         guidance over K + 1 branches in one (K+1) n forward — eps = e_0 + sum_k w_k (e_k - e_0).  y,
-        null_label, vals, mask and guidance are then not read; rescale must be 0."""
+        null_label, vals, mask and guidance are then not read; rescale must be 0.
+        geom = (scale (n,), sig (S,)) (include/dmx.h dmx_geom_guide; _geom): geometry guidance — a CFG step
+        whose prediction gains (scale[n] sig[p-1]) dL_n/dx, L_n the GeomHead's masked regression loss
+        against the step's own vals / mask.  UnetCondWithGeomHead only; no rescale, no compose.  The
+        step replaces the training tape.  None is the plain step, launched exactly as without the keyword."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        gg = None
+        if geom is not None:
+            gg = self._geom(x_in, geom, sched, tables, rescale, compose, guidance, y, vals, mask)
+            self._live_geom = tuple(geom)
         if compose is not None:
             comp, self._live_comp = self._compose(x_in, compose, rescale)
             y = vals = mask = None
@@ -367,7 +434,10 @@ class NativeModel:
         a = self._args(x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
                        sample_offset)
         with torch.cuda.device(x_in.device):
-            if compose is not None:
+            if gg is not None:
+                check(self.lib.dmx_step_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
+                                             ctypes.c_void_p(_stream(x_in.device))))
+            elif compose is not None:
                 check(self.lib.dmx_step_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                  ctypes.c_void_p(_stream(x_in.device))))
             else:
@@ -394,7 +464,7 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None):
+                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -409,8 +479,14 @@ class NativeModel:
         The model keeps the captured graphs of the last few distinct loops (graph_captures counts the
         captures), so alternating guided, unguided and rescaled loops replay instead of recapturing.
         compose as in step(): every step of the loop is a composed step.  The captured graphs hold the
-        pointers of the converted tables: pass contiguous int64 / fp32 device tensors to replay them."""
+        pointers of the converted tables: pass contiguous int64 / fp32 device tensors to replay them.
+        geom as in step(): every step of the loop is a geometry-guided step; the graphs hold the pointers
+        of its two tables."""
         _check_state(x, "x")
+        gg = None
+        if geom is not None:
+            gg = self._geom(x, geom, sched, tables, rescale, compose, guidance, y, vals, mask)
+            self._live_geom = tuple(geom)
         comp_live = ()
         if compose is not None:
             comp, comp_live = self._compose(x, compose, rescale)
@@ -427,12 +503,15 @@ class NativeModel:
         side = self.side_stream()
         side.wait_stream(cur)
         live = (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables) + tuple(known or ())
-        live += tuple(comp_live)
+        live += tuple(comp_live) + (tuple(geom) if geom is not None else ())
         for keep in live:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if compose is not None:
+            if gg is not None:
+                check(self.lib.dmx_sample_loop_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
+                                                    int(steps), int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            elif compose is not None:
                 check(self.lib.dmx_sample_loop_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                         int(steps), int(use_graph),
                                                         ctypes.c_void_p(side.cuda_stream)))
@@ -581,6 +660,41 @@ def compose_eps(e_list, weights):
     with torch.cuda.device(dev):
         check(lib.dmx_compose_eps(_ptr(e_c), _ptr(w_c), K, n, c, h, w, _ptr(eps), ctypes.c_void_p(_stream(dev))))
     return eps
+
+
+def geom_mix(eps, grad, scale, sig, pos):
+    """Standalone geometry-guidance mix (include/dmx.h dmx_geom_mix) for duck-typed models -> eps':
+        eps' = eps + (scale[n] sig[pos[n] - 1]) grad
+    one fp32 rounding per operation; where scale[n] == 0 or grad == 0 the element keeps eps's bits.
+    eps, grad: (n,c,h,w) on the GPU, any c, h, w >= 1; scale: a float or (n,) floats; sig: (S,) fp32
+    (sqrt(1 - ab) per position); pos: (n,) positions in [1, S] or one value for every sample.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(eps, "eps")
+    dev = eps.device
+    e_c = eps.to(dtype=torch.float32).contiguous()
+    g_c = grad.to(device=dev, dtype=torch.float32).contiguous()
+    if e_c.dim() != 4 or tuple(g_c.shape) != tuple(e_c.shape) or min(e_c.shape) < 1:
+        raise ValueError(f"eps / grad must be equal (n,c,h,w) tensors (got {tuple(eps.shape)}, {tuple(grad.shape)})")
+    n, c, h, w = e_c.shape
+    s_c = torch.as_tensor(scale, dtype=torch.float32).to(device=dev).reshape(-1)
+    if s_c.numel() == 1:
+        s_c = s_c.expand(n)
+    s_c = s_c.contiguous()
+    if s_c.numel() != n:
+        raise ValueError(f"scale has {s_c.numel()} entries for a batch of {n}")
+    sig_c = sig.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    if sig_c.numel() < 1:
+        raise ValueError("sig is empty")
+    p_c = torch.as_tensor(pos).to(device=dev, dtype=torch.long).contiguous().reshape(-1)
+    if p_c.numel() not in (1, n):
+        raise ValueError(f"pos has {p_c.numel()} entries for a batch of {n}")
+    out = torch.empty_like(e_c)
+    with torch.cuda.device(dev):
+        check(lib.dmx_geom_mix(_ptr(e_c), _ptr(g_c), _ptr(s_c), _ptr(sig_c), int(sig_c.numel()), _ptr(p_c),
+                               0 if p_c.numel() == 1 and n > 1 else 1, _ptr(out), n, c, h, w,
+                               ctypes.c_void_p(_stream(dev))))
+    return out
 
 
 def _update_operands(x, eu, ec, noise, pos, pos_name):

@@ -4,6 +4,7 @@ from __future__ import annotations
 import torch
 
 from dmx import _lib
+from dmx import engine as _engine
 from models._modules import GeomHead
 from models.unet_cond import UnetCond
 
@@ -27,3 +28,18 @@ class UnetCondWithGeomHead(UnetCond):
                 cond_mask: torch.Tensor = None, cond_drop_prob: float = 0.0):
         use = cond_vals is not None and cond_mask is not None  # unet_cond_geom.py:91 (no dropout here)
         return self._run(x, t, y, cond_vals if use else None, cond_mask if use else None, want_geom=True)
+
+    def geom_grad(self, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cond_vals: torch.Tensor,
+                  cond_mask: torch.Tensor):
+        """The geometry-guidance loss and its gradient with respect to x ->
+        (loss (n,), grad (n,c,h,w), geom (n,geom_dim), eps): per sample
+        L_n = sum_j m_nj (geom_nj - v_nj)^2 / max(sum_j m_nj, 1e-6) with geom the GeomHead's output on
+        (x, t, y, cond_vals, cond_mask) and v, m the same cond_vals / cond_mask, and dL_n/dx by the
+        native data-only backward (NativeModel.geom_grad).  Works in eval mode and under no_grad: no
+        autograd graph is built, nothing here is differentiable further, and no parameter gets a
+        gradient.  forward() with an x that requires grad keeps raising NotImplementedError."""
+        if cond_vals is None or cond_mask is None:
+            raise ValueError("geom_grad needs cond_vals and cond_mask (the loss's target)")
+        _engine.require_cuda(x, "x")
+        with torch.no_grad():
+            return self.native().geom_grad(x, t, y, cond_vals, cond_mask)

@@ -332,8 +332,53 @@ int dmx_sample_loop_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddi
 int dmx_compose_eps(const float* e, const float* weight, int K, int n, int c, int h, int w, float* eps_out,
                     void* stream);
 
+/* ---- Geometry guidance: classifier guidance by the GeomHead's input gradient (Dhariwal & Nichol
+ * 2021, §4.1, DDIM form; no reference counterpart).  DMX_UNET_COND_GEOM regresses the geom_dim
+ * geometry values from the noisy latent at every timestep; with geom = its output on the step's
+ * conditional input (a->y, a->vals, a->mask) and the target the step's own a->vals / a->mask,
+ *   L_n = sum_j m_nj (geom_nj - v_nj)^2 / max(sum_j m_nj, 1e-6)
+ *   eps' = eps + (scale[n] * sig[p-1]) * dL_n/dx
+ * where eps is the CFG-guided prediction, p the step's position and sig[p-1] = sqrt(1 - ab[t]) of
+ * its timestep (per position, as the schedule's tables; the DDPM step: per timestep, S = T).  One
+ * IEEE rounding per operation: the scale product, its product with the gradient, the sum.  Where
+ * scale[n] == 0 or the gradient element is exactly zero, eps' has eps's bits; a row whose mask is
+ * all zero has an exactly zero gradient.  A non-finite eps' raises the range flag.  Both tables are
+ * device pointers owned by the caller. */
+typedef struct dmx_geom_guide {
+  const float* scale; /* (n,) device */
+  const float* sig;   /* per position */
+  int S;
+} dmx_geom_guide;
+
+/* dmx_step* / dmx_sample_loop* with geometry guidance: at most one of ddim / dpm is non-NULL (both
+ * NULL: the DDPM step), known may be NULL, geom must be given with S equal to the schedule's
+ * (a->T for DDPM).  The model must be DMX_UNET_COND_GEOM and the step a CFG step with a condition
+ * (a->guidance > 0, a->y, a->vals and a->mask given); there is no rescale and no composition.
+ * Every step runs the 2n CFG forward, the taped training forward of the n conditional rows (fp32
+ * semantics, as dmx_train_forward; it reads the step's position scalar), the loss seed, the
+ * data-only backward to x (dmx_train_backward_input's launches), the mix and the rule's update on
+ * the mixed prediction, then the blend if asked for; all of it inside the model's planned arena,
+ * so the loop is captured like every other.  The model's training tape is replaced: a
+ * dmx_train_backward still pending on an earlier dmx_train_forward is refused as stale. */
+int dmx_step_geom(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                  const dmx_known_sched* known, const dmx_geom_guide* geom, void* stream);
+int dmx_sample_loop_geom(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                         const dmx_known_sched* known, const dmx_geom_guide* geom, int steps, int use_graph,
+                         void* stream);
+/* The mix alone, for duck-typed foreign models (no model, no arena): eps, grad, eps_out (n,c,h,w)
+ * with any c, h, w >= 1; scale (n,); sig [S]; pos: device int64 positions clamped to [1, S],
+ * pos_stride 0 => one value for every sample.  eps_out may alias eps.  Feed eps_out to
+ * dmx_*_update with ec = NULL. */
+int dmx_geom_mix(const float* eps, const float* grad, const float* scale, const float* sig, int S,
+                 const int64_t* pos, int pos_stride, float* eps_out, int n, int c, int h, int w, void* stream);
+/* The loss and its seed alone: geom, vals, mask, seed_out (n,gd); loss_out (n,) or NULL.
+ * seed_out[n][j] = dL_n/dgeom_nj = 2 m_nj (geom_nj - v_nj) / max(sum_j m_nj, 1e-6) — what
+ * dmx_train_backward_input takes as d_geom. */
+int dmx_geom_seed(const float* geom, const float* vals, const float* mask, int n, int gd, float* loss_out,
+                  float* seed_out, void* stream);
+
 /* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
- * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / time-table
+ * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / geometry guidance / time-table
  * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
  * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
  * after another, inside the model's one workspace; whatever reallocates or invalidates it (a
@@ -378,12 +423,20 @@ int dmx_vae_encode(dmx_model* m, const float* x, const float* eps, float* z, flo
  * dmx_train_backward: d_eps (n,in_ch,h,w) = dLoss/deps, d_geom (n,geom_dim) = dLoss/dgeom
  * (either may be NULL = zero); writes dLoss/dparam for every state_dict key into grads[i]
  * (one device pointer per key in dmx_model_cfg_key order, each of that key's shape; keys whose
- * branch did not run — cond_mlp without vals — receive zeros).  No gradient for x. */
+ * branch did not run — cond_mlp without vals — receive zeros).  The gradient for x is
+ * dmx_train_backward_input's.
+ * dmx_train_backward_input: the same tape rules and cotangents; writes d_x (n,in_ch,h,w) = the
+ * vector-Jacobian product with respect to the taped forward's x and nothing else — no parameter
+ * gradient is computed and no gradient buffer is needed (the weight-gradient GEMMs, bias and
+ * affine sums and the whole embedding backward are not launched).  It leaves the tape as it found
+ * it: a dmx_train_backward on the same tape afterwards gives the bits it gives without. */
 int dmx_train_forward(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
                       const float* mask, int n, int h, int w, float* eps, float* geom, int64_t* tape_id,
                       void* stream);
 int dmx_train_backward(dmx_model* m, int64_t tape_id, const float* d_eps, const float* d_geom, float* const* grads,
                        int n_grads, void* stream);
+int dmx_train_backward_input(dmx_model* m, int64_t tape_id, const float* d_eps, const float* d_geom, float* d_x,
+                             void* stream);
 
 /* ---- VAE training step (replaces the forward + loss.backward() of VAE.forward in train_vae.py,
  * models/vae.py:51-76; widths 3 / 4 / 64, image sides multiples of 8) -------------------------------

@@ -30,6 +30,7 @@ struct Inputs {
   dmx_known_sched known;
   dmx_guidance gd;
   dmx_compose comp;
+  dmx_geom_guide geom;
   explicit Inputs(int fill = 0) {
     std::memset(&a, 0, sizeof(a));  // (the step args enter the key as the caller's bytes)
     a.x_in = a.x_out = mem;
@@ -79,12 +80,16 @@ struct Inputs {
     comp.vals = mem + 17;
     comp.mask = mem + 18;
     comp.weight = mem + 19;
+    std::memset(&geom, fill, sizeof(geom));
+    geom.scale = mem + 20;
+    geom.sig = mem + 21;
+    geom.S = 3;
   }
   GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1,
-               bool use_comp = false) const {
+               bool use_comp = false, bool use_geom = false) const {
     return make_graph_key(a, StepMode{use_ddim ? &ddim : nullptr, use_dpm ? &dpm : nullptr,
                                       use_known ? &known : nullptr, use_gd ? &gd : nullptr,
-                                      use_comp ? &comp : nullptr}, table_gen);
+                                      use_comp ? &comp : nullptr, use_geom ? &geom : nullptr}, table_gen);
   }
 };
 
@@ -203,6 +208,38 @@ int main() {
     // its padding stays out of the key
     CHECK(Inputs(0xAA).key(ddim, dpm, true, true, 1, true) == Inputs(0).key(ddim, dpm, true, true, 1, true));
   }
+  // 10. geometry guidance: its own keys, member by member; all zero when absent
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    const GraphKey plain = Inputs().key(ddim, dpm), guided = Inputs().key(ddim, dpm, false, false, 1, false, true);
+    CHECK(!(guided == plain));
+    CHECK(!(guided == Inputs().key(ddim, dpm, false, false, 1, true)));  // (nor a composed loop's)
+    auto moved_g = [&](auto&& edit) {
+      Inputs in;
+      edit(in);
+      return !(in.key(ddim, dpm, false, false, 1, false, true) == guided);
+    };
+    CHECK(moved_g([](Inputs& in) { in.geom.scale = mem + 40; }));
+    CHECK(moved_g([](Inputs& in) { in.geom.sig = mem + 40; }));
+    CHECK(moved_g([](Inputs& in) { in.geom.S = 4; }));
+    // the step args it reads stay in: the target is the call's own condition
+    CHECK(moved_g([](Inputs& in) { in.a.y = imem + 5; }));
+    CHECK(moved_g([](Inputs& in) { in.a.vals = mem + 40; }));
+    CHECK(moved_g([](Inputs& in) { in.a.mask = mem + 40; }));
+    CHECK(moved_g([](Inputs& in) { in.a.guidance = 2.f; }));
+    // with a known region it is still its own key
+    CHECK(!(Inputs().key(ddim, dpm, true, false, 1, false, true) == Inputs().key(ddim, dpm, true)));
+    // a key without it holds zeros there, whatever the other paths
+    const dmx_geom_guide zero{};
+    for (int kn = 0; kn < 2; ++kn)
+      for (int cp = 0; cp < 2; ++cp) {
+        const GraphKey k = Inputs(0xAA).key(ddim, dpm, kn != 0, true, 1, cp != 0);
+        CHECK(std::memcmp(&k.geom, &zero, sizeof(zero)) == 0);
+      }
+    // its padding stays out of the key
+    CHECK(Inputs(0xAA).key(ddim, dpm, true, false, 1, false, true) == Inputs(0).key(ddim, dpm, true, false, 1, false, true));
+  }
+  CHECK(StepMode{}.geom == nullptr);
   if (fails == 0) std::puts("step_mode_check: ok");
   return fails == 0 ? 0 : 1;
 }
