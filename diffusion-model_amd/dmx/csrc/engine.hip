@@ -2,6 +2,7 @@
 // include/dmx.h (the sampling step and its hipGraph loop: sample_engine.h).
 #include "dmx.h"
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -221,21 +222,23 @@ struct DownUpW {
 // Workspace: bump allocator run twice (plan: sizes only, then real).
 struct Arena {
   char* base = nullptr;
-  size_t cap = 0, off = 0;
+  size_t off = 0;
   bool plan = true;
-  // DMX_CHECK: allocation sizes of the plan pass, compared one by one in the real pass
-  std::vector<size_t>* trace = nullptr;
+  // DMX_CHECK: allocation sizes of the plan pass, compared one by one in every real pass after it
+  bool trace = false;
+  std::vector<size_t> sizes;
   size_t n = 0;
-  const std::string* layer = nullptr;
+  const std::string* layer = nullptr;  // the live Run's layer name (set and cleared by Run)
+  void rewind() { off = n = 0; }
   template <typename T>
   T* get(size_t count) {
     const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    if (trace != nullptr) {
+    if (trace) {
       if (plan) {
-        trace->push_back(bytes);
-      } else if (n >= trace->size() || (*trace)[n] != bytes) {
+        sizes.push_back(bytes);
+      } else if (n >= sizes.size() || sizes[n] != bytes) {
         throw std::runtime_error("workspace allocation " + std::to_string(n) + " differs between plan and run (" +
-                                 std::to_string(n < trace->size() ? (*trace)[n] : 0) + " vs " +
+                                 std::to_string(n < sizes.size() ? sizes[n] : 0) + " vs " +
                                  std::to_string(bytes) + " bytes, layer '" + (layer ? *layer : std::string()) + "')");
       }
       ++n;
@@ -246,6 +249,12 @@ struct Arena {
     // same branch (and allocates the same) in both passes; it is never dereferenced
     return reinterpret_cast<T*>(plan ? reinterpret_cast<char*>(static_cast<uintptr_t>(4096) + off) : p);
   }
+};
+// An arena and the device memory behind it (grown to the largest plan so far; plan_ws / run_ws).
+struct Workspace {
+  Arena a;
+  void* mem = nullptr;
+  size_t cap = 0;
 };
 
 // One captured loop: the one-step graph and the same step captured kGraphSteps times back to back.
@@ -298,13 +307,13 @@ struct dmx_model {
   // VAE training (vae_train_engine.h), per stage: the forward weight with device-split planes, and the
   // data-gradient GEMM weight (none for enc.0 / dec.0)
   dmx::ConvW venc_t[6], venc_d[6], vdec_t[6], vdec_d[6];
-  // workspace + graph
-  dmx::Arena ws;
-  void* ws_mem = nullptr;
-  size_t ws_cap = 0;
+  // workspaces + graph: inference, the tape of the last training forward, the backward pass
+  // (train_engine.h; a geometry-guided step runs all three kinds of work in ws)
+  dmx::Workspace ws, tws, bws;
+  std::array<const dmx::Workspace*, 3> workspaces() const { return {&ws, &tws, &bws}; }
   // The graph pairs of the last kGraphSlots distinct loops (graph_slots.h: least recently used is
-  // replaced).  All of them point into ws_mem and replay one after another on one stream; that is
-  // safe only while ws_mem is never reallocated under a live slot (ensure_ws drops them all first).
+  // replaced).  All of them point into ws.mem and replay one after another on one stream; that is
+  // safe only while ws.mem is never reallocated under a live slot (plan_ws drops them all first).
   dmx::LruSlots<dmx::GraphKey, dmx::GraphPair, dmx::kGraphSlots> graphs;
   int64_t graph_captures = 0;  // pairs captured so far (dmx_model_graph_captures)
   // debug taps: (name, device pointer into the workspace, element count, C)
@@ -328,14 +337,10 @@ struct dmx_model {
   size_t copy_chunks = 0, repack_chunks = 0, repack_tiles = 0;  // BatchChunk / RepackTile entries (kernels.h)
   bool planes_stale = false;
   unsigned* amax = nullptr;  // absmax scratch of split_planes
-  // training (train_engine.h): tape of the last dmx_train_forward, its workspace and the
-  // backward pass's workspace
+  // training (train_engine.h): tape of the last dmx_train_forward (it points into tws)
   bool train_ready = false;
   dmx::Tape* tape = nullptr;
   dmx::VaeTape* vtape = nullptr;
-  dmx::Arena tws, bws;
-  void *tws_mem = nullptr, *bws_mem = nullptr;
-  size_t tws_cap = 0, bws_cap = 0;
   int64_t tape_id = 0;
 };
 
@@ -781,6 +786,14 @@ static Cksum& cksum_state() {
   return c;
 }
 
+// Per-block partial maxima of |x| over one tensor, in absmax_part_kernel's format (non-negative floats as
+// their bits): the device-side operand scale of an f16-core GEMM whose operand has no host-known range
+// (the partials that X3Params and WgradParams point to).  Empty: no such scale.
+struct AbsMax {
+  const unsigned* part = nullptr;
+  int n = 0;
+};
+
 struct Run {
   dmx_model* m;
   hipStream_t st;
@@ -788,25 +801,17 @@ struct Run {
   Arena& ws;
   Prof* prof = nullptr;
   std::string layer;
+  Run(dmx_model* m, hipStream_t st, bool plan, Arena& ws, Prof* prof = nullptr)
+      : m(m), st(st), plan(plan), ws(ws), prof(prof) {
+    ws.layer = &layer;
+  }
+  Run(const Run&) = delete;
+  ~Run() { ws.layer = nullptr; }
   // > 0: gemm() takes its tile / split-K / kernel decisions as if the batch had this many
   // samples (the grid still covers the real batch).  The VAE decoder sets 1, so a sample's
   // decoded bytes do not depend on the batch or chunk it is decoded in (summation order is a
   // function of the per-sample geometry only).
   int tile_n = 0;
-  // non-null: the next gemm() runs the split-precision implicit GEMM with A scaled on the device by
-  // this max|A| slot (training data gradients, train_engine.h dgrad)
-  bool fwd_x3 = false;  // training forward: weights with device-split planes (ConvW::inv_dev) run the split GEMM
-  bool data_only = false;  // training backward: data gradients alone, down to the input (train_engine.h)
-  bool colsum_defer = false;               // training backward: final-level column sums batched (train_engine.h)
-  std::vector<ColsumJob> colsums;
-  const unsigned* a_amax = nullptr;
-  int a_nparts = 0;  // a_amax: that many per-block partial maxima (absmax_part_kernel)
-  // train_engine.h dy_amax: the last tensor whose |max| partials were taken
-  const float* amax_src = nullptr;
-  size_t amax_n = 0;
-  unsigned* amax_slot = nullptr;
-  int amax_parts = 0;
-  int amax_uses = 0;  // remaining reuses of that measurement
   void tap(const std::string& name, const float* p, size_t count);
   std::string ck_layer;
   // DMX_CKSUM: one workspace checksum per layer, taken when the next layer's first kernel begins
@@ -816,9 +821,9 @@ struct Run {
   bool cksum = false;
   void ck() {
     Cksum& c = cksum_state();
-    if (!cksum || plan || c.dev == nullptr || m->ws_mem == nullptr || ck_layer.empty() || c.names.size() >= 1024)
+    if (!cksum || plan || c.dev == nullptr || m->ws.mem == nullptr || ck_layer.empty() || c.names.size() >= 1024)
       return;
-    cksum_kernel<<<1024, 256, 0, st>>>(static_cast<const unsigned*>(m->ws_mem), ws.off / 4, c.dev + c.names.size());
+    cksum_kernel<<<1024, 256, 0, st>>>(static_cast<const unsigned*>(m->ws.mem), ws.off / 4, c.dev + c.names.size());
     c.names.push_back(ck_layer);
   }
   void begin(const std::string& kernel, double flops, double bytes) {
@@ -875,23 +880,21 @@ static void check_range(Run& R, const void* p, size_t bytes, const char* what) {
   if (!check_args() || p == nullptr || bytes == 0) return;
   const char* a = static_cast<const char*>(p);
   const dmx_model* m = R.m;
-  auto inside = [&](const void* base, size_t cap) {
-    const char* b = static_cast<const char*>(base);
-    return base != nullptr && a >= b && a + bytes <= b + cap;
-  };
-  if (inside(m->ws_mem, m->ws_cap) || inside(m->tws_mem, m->tws_cap) || inside(m->bws_mem, m->bws_cap)) return;
+  for (const Workspace* w : m->workspaces()) {
+    const char* b = static_cast<const char*>(w->mem);
+    if (b != nullptr && a >= b && a + bytes <= b + w->cap) return;
+  }
   auto it = m->owned_bytes.upper_bound(a);
   if (it != m->owned_bytes.begin()) {
     --it;
     if (a >= it->first && a + bytes <= it->first + it->second) return;
   }
   char msg[512];
-  std::snprintf(msg, sizeof msg,
-                "DMX_CHECK: %s operand [%p, +%zu) of layer '%s' lies outside every model allocation "
-                "(ws %p +%zu, tws %p +%zu, bws %p +%zu, arena off %zu)",
-                what, p, bytes, R.layer.c_str(), m->ws_mem, m->ws_cap, m->tws_mem, m->tws_cap, m->bws_mem, m->bws_cap,
-                R.ws.off);
-  throw Error(DMX_E_INTERNAL, msg);
+  int len = std::snprintf(msg, sizeof msg, "DMX_CHECK: %s operand [%p, +%zu) of layer '%s' lies outside every model "
+                          "allocation (arena off %zu; ws, tws, bws:", what, p, bytes, R.layer.c_str(), R.ws.off);
+  for (const Workspace* w : m->workspaces())
+    if (len < (int)sizeof msg) len += std::snprintf(msg + len, sizeof msg - len, " %p +%zu", w->mem, w->cap);
+  throw Error(DMX_E_INTERNAL, std::string(msg) + ")");
 }
 
 // GroupNorm(1, C) + GELU applied by the halo conv while it stages its raw fp32 source (the
@@ -986,7 +989,9 @@ struct ConvPlan {
   }
 };
 
-static ConvPlan conv_plan(const Run& R, const ConvW& cw, ConvSrc src, int N, int H, int W, int epi, int seg) {
+// a_scaled: the A operand comes with a device-side scale (gemm()'s a_scale: a training data gradient)
+static ConvPlan conv_plan(const Run& R, const ConvW& cw, ConvSrc src, int N, int H, int W, int epi, int seg,
+                          bool a_scaled = false) {
   ConvPlan p;
   p.cout = cw.cout;
   const int prec = R.m->prec, C = cw.cin;
@@ -1007,10 +1012,11 @@ static ConvPlan conv_plan(const Run& R, const ConvW& cw, ConvSrc src, int N, int
   const int tiles128 = cdiv(Md, 128) * cdiv(cw.cout, p.bn) * cw.phases;
   p.bm = tiles128 >= 256 ? 128 : 64;  // 128-row tiles (split K if the grid is then small) from 256 tiles
   const int blocks = cdiv(Md, p.bm) * cdiv(cw.cout, p.bn) * cw.phases;
-  // (R.a_amax: a training data gradient on the split GEMM with device-side operand scales; R.fwd_x3:
-  // the training forward's weights with device-split planes — whatever the model's precision mode,
-  // only the implicit-GEMM kernels below carry those scales)
-  p.x3 = (prec >= 1 || R.a_amax != nullptr || (R.fwd_x3 && cw.inv_dev != nullptr)) && nhwc && cw.Bh != nullptr;
+  // (a_scaled: a training data gradient on the split GEMM with device-side operand scales; cw.inv_dev:
+  // a weight with device-split planes — the training forward's copies and the data-gradient weights,
+  // which exist for this kernel alone — whatever the model's precision mode; only the implicit-GEMM
+  // kernels below carry those scales)
+  p.x3 = (prec >= 1 || a_scaled || cw.inv_dev != nullptr) && nhwc && cw.Bh != nullptr;
   p.x1 = p.x3 && prec == 2;
   // 512-thread ping-pong kernel (256-row tiles) for the large f16-plane convs (measured +1.3 % over
   // the two-block kernel, same-box A/B)
@@ -1126,10 +1132,13 @@ static void splitk_reduce(Run& R, const ConvPlan& pl, const float* partial, int 
 // (taps 16), linear (taps 1).  Sources are plain NHWC (or the NCHW network input); grids too small to
 // fill the 256 CUs are split along K into deterministic slabs reduced by splitk_reduce_kernel
 // (or, in a ResBlock, by the caller's fused reduce_norm_kernel).
+// a_scale (training data gradients, train_engine.h dgrad): the split-precision implicit GEMM with A
+// scaled on the device from these maxima of |A|.
 // Returns the GroupNorm partial rows per sample it wrote (EPI_STATS).
 static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, const ConvW& cw, int epi, float* out,
                 const float* res, float2* rowpart, int seg, const _Float16* ash = nullptr,
-                const _Float16* asl = nullptr, Deferred* defer = nullptr, const GnLoad* gn = nullptr) {
+                const _Float16* asl = nullptr, Deferred* defer = nullptr, const GnLoad* gn = nullptr,
+                AbsMax a_scale = {}) {
   const int M = N * H * W;
   if (cw.cout % 32 != 0) throw Error(DMX_E_INTERNAL, "gemm: Cout must be a multiple of 32");
   // ---- the plan ----
@@ -1137,13 +1146,14 @@ static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, con
                        : src_mode == SRC_NCHW      ? CONV_SRC_NCHW
                        : ash != nullptr            ? CONV_SRC_PLANES
                                                    : CONV_SRC_PLAIN;
-  const ConvPlan pl = conv_plan(R, cw, kind, N, H, W, epi, seg);
+  const bool a_scaled = a_scale.part != nullptr;
+  const ConvPlan pl = conv_plan(R, cw, kind, N, H, W, epi, seg, a_scaled);
   const bool x3 = pl.x3, wino = pl.path == CONV_WINO;
   const int bm = pl.bm, bn = pl.bn, splits = pl.splits, x1 = pl.x1 ? 1 : 0;
   if (pl.path == CONV_INPUT) {
     if (res != nullptr) throw Error(DMX_E_INTERNAL, "gemm: the direct input conv takes no residual");
     if (ash != nullptr || asl != nullptr) throw Error(DMX_E_INTERNAL, "gemm: the direct input conv reads fp32 NCHW");
-  } else if (R.a_amax != nullptr && (!x3 || ash != nullptr || epi == EPI_STATS || gn != nullptr || R.m->prec == 2)) {
+  } else if (a_scaled && (!x3 || ash != nullptr || epi == EPI_STATS || gn != nullptr || R.m->prec == 2)) {
     throw Error(DMX_E_INTERNAL, "gemm: device-scaled operands only on the plain split implicit GEMM");
   }
   if (gn != nullptr && ((pl.path != CONV_HALO && !wino) || ash != nullptr || src_mode != SRC_PLAIN))
@@ -1216,8 +1226,8 @@ static int gemm(Run& R, const SrcDesc& s, int src_mode, int N, int H, int W, con
   xp.gn_res = nullptr;
   xp.Uh = xp.Ul = nullptr;
   xp.u_bytes = 0;
-  xp.a_amax = R.a_amax;
-  xp.a_nparts = R.a_nparts;
+  xp.a_amax = a_scale.part;
+  xp.a_nparts = a_scale.n;
   xp.w_inv = cw.inv_dev;
   {
     const size_t a_el = (size_t)N * p.Hin * p.Win * s.C;
@@ -1519,8 +1529,8 @@ static void attention_core(Run& R, const float* qkv, float* out, int N, int L, i
   if (R.plan) return;
   const int D = C / 4;
   if (D != 16 && D != 32 && D != 64) throw Error(DMX_E_INTERNAL, "attention: unsupported head dim");
-  // the split-precision cores: inference in modes 1 / 2, and the training forward (R.fwd_x3, with stats)
-  const bool x3 = R.m->prec >= 1 || (R.fwd_x3 && stats != nullptr);
+  // the split-precision cores: inference in modes 1 / 2, and the training forward (the one caller with stats)
+  const bool x3 = R.m->prec >= 1 || stats != nullptr;
   if (stats != nullptr && R.m->prec == 2) throw Error(DMX_E_INTERNAL, "attention stats: not in fp16 mode");
   if (x3 && D == 16 && att16_lds_bytes(L, 0) <= 160 * 1024) {
     // head resident in LDS (sa5 / sa6): one block per (sample, head), no per-chunk staging
@@ -1891,72 +1901,79 @@ static bool poison_ws() {
   }();
   return v;
 }
-static void poison(void* mem, size_t bytes, hipStream_t st) {
-  if (poison_ws() && mem != nullptr && bytes > 0) HIPCHK(hipMemsetAsync(mem, 0xFF, bytes, st));
+static void poison(void* mem, size_t bytes, hipStream_t st) {  // (DMX_CKSUM sums the same fill: see run_planned)
+  if ((poison_ws() || cksum_enabled()) && mem != nullptr && bytes > 0) HIPCHK(hipMemsetAsync(mem, 0xFF, bytes, st));
 }
 
-static void ensure_ws(dmx_model* m) {
-  if (m->ws.off > m->ws_cap) {
-    if (m->ws_mem) HIPCHK(hipFree(m->ws_mem));
-    m->ws_mem = nullptr;
-    m->ws_cap = 0;
-    drop_graph(m);
-    HIPCHK(hipMalloc(&m->ws_mem, m->ws.off));
-    m->ws_cap = m->ws.off;
-  }
-}
-
-// The dry run of `body`, then an arena of the size it asked for (returned), ready for the real pass.
+// The dry run of `body` in W's arena (sizes only), then memory of at least the size it asked for
+// (returned) and the arena ready for the real pass.  Growing waits for the stream's earlier work,
+// and a grown inference workspace drops every captured graph: they point into the old one.
 template <typename F>
-static size_t plan_ws(dmx_model* m, hipStream_t st, F&& body) {
-  m->ws.base = nullptr;
-  m->ws.off = 0;
-  m->ws.plan = true;
+static size_t plan_ws(dmx_model* m, hipStream_t st, Workspace& W, F&& body) {
+  Arena& A = W.a;
+  A.base = nullptr;
+  A.plan = true;
+  A.trace = check_args();
+  A.sizes.clear();
+  A.rewind();
   {
-    Run R{m, st, true, m->ws};
+    Run R{m, st, true, A};
     body(R);
   }
-  ensure_ws(m);
-  const size_t planned = m->ws.off;
-  poison(m->ws_mem, planned, st);
-  m->ws.base = static_cast<char*>(m->ws_mem);
-  m->ws.off = 0;
-  m->ws.plan = false;
+  const size_t planned = A.off;
+  if (planned > W.cap) {
+    if (W.mem) {
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipFree(W.mem));
+    }
+    W.mem = nullptr;
+    W.cap = 0;
+    if (&W == &m->ws) drop_graph(m);
+    HIPCHK(hipMalloc(&W.mem, planned));
+    W.cap = planned;
+  }
+  poison(W.mem, planned, st);
+  A.base = static_cast<char*>(W.mem);
+  A.plan = false;
+  A.rewind();
   return planned;
 }
 
-// prof: event timing of every launch of the real pass (dmx_step_profile)
+// `body` twice in W: planned (plan_ws), then for real.  prof: event timing of every launch of the real
+// pass; cksum: the DMX_CKSUM layer sums (run_planned)
+template <typename F>
+static void run_ws(dmx_model* m, hipStream_t st, Workspace& W, F&& body, Prof* prof = nullptr, bool cksum = false) {
+  const size_t planned = plan_ws(m, st, W, body);
+  Run R{m, st, false, W.a, prof};
+  R.cksum = cksum;
+  body(R);
+  if (W.a.off != planned) throw Error(DMX_E_INTERNAL, "workspace plan / run mismatch");
+  R.ck();
+}
+
+// run_ws in the inference workspace (dmx_step_profile: with prof)
 template <typename F>
 static void run_planned(dmx_model* m, hipStream_t st, F&& body, Prof* prof = nullptr) {
-  const size_t planned = plan_ws(m, st, body);
+  if (!cksum_enabled()) return run_ws(m, st, m->ws, body, prof);
   Cksum& ck = cksum_state();
-  if (cksum_enabled()) {
-    if (ck.dev == nullptr) HIPCHK(hipMalloc(&ck.dev, 1024 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(ck.dev, 0, 1024 * sizeof(unsigned long long), st));
-    HIPCHK(hipMemsetAsync(m->ws_mem, 0xFF, planned, st));
-    ck.names.clear();
+  if (ck.dev == nullptr) HIPCHK(hipMalloc(&ck.dev, 1024 * sizeof(unsigned long long)));
+  HIPCHK(hipMemsetAsync(ck.dev, 0, 1024 * sizeof(unsigned long long), st));
+  ck.names.clear();
+  run_ws(m, st, m->ws, body, prof, true);
+  std::vector<unsigned long long> h(ck.names.size());
+  HIPCHK(hipMemcpyAsync(h.data(), ck.dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (ck.names == ck.prev_names) {
+    for (size_t k = 0; k < h.size(); ++k)
+      if (h[k] != ck.prev[k]) {
+        std::fprintf(stderr, "[dmx cksum] run %d: first difference after kernel %zu (%s)\n", ck.runs, k,
+                     ck.names[k].c_str());
+        break;
+      }
   }
-  Run R{m, st, false, m->ws, prof};
-  R.cksum = cksum_enabled();
-  body(R);
-  if (m->ws.off != planned) throw Error(DMX_E_INTERNAL, "workspace plan / run mismatch");
-  if (cksum_enabled()) {
-    R.ck();
-    std::vector<unsigned long long> h(ck.names.size());
-    HIPCHK(hipMemcpyAsync(h.data(), ck.dev, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ck.names == ck.prev_names) {
-      for (size_t k = 0; k < h.size(); ++k)
-        if (h[k] != ck.prev[k]) {
-          std::fprintf(stderr, "[dmx cksum] run %d: first difference after kernel %zu (%s)\n", ck.runs, k,
-                       ck.names[k].c_str());
-          break;
-        }
-    }
-    ck.prev = h;
-    ck.prev_names = ck.names;
-    ++ck.runs;
-  }
+  ck.prev = h;
+  ck.prev_names = ck.names;
+  ++ck.runs;
 }
 
 // VAE decoder (models/vae.py:35-49,64-69) on one chunk of n latents:
@@ -2204,9 +2221,8 @@ int dmx_model_destroy(dmx_model* m) {
     for (void* p : m->owned) (void)hipFree(p);
     if (m->job_tables) (void)hipFree(m->job_tables);
     if (m->split_table) (void)hipFree(m->split_table);
-    if (m->ws_mem) (void)hipFree(m->ws_mem);
-    if (m->tws_mem) (void)hipFree(m->tws_mem);
-    if (m->bws_mem) (void)hipFree(m->bws_mem);
+    for (const Workspace* w : m->workspaces())
+      if (w->mem) (void)hipFree(w->mem);
     delete m->tape;
     delete m->vtape;
     delete m;
@@ -2237,7 +2253,10 @@ int dmx_model_finalize(dmx_model* m, void* stream) {
 }
 
 int64_t dmx_model_workspace_bytes(const dmx_model* m) {
-  return m ? (int64_t)(m->ws_cap + m->tws_cap + m->bws_cap) : -1;
+  if (!m) return -1;
+  int64_t total = 0;
+  for (const dmx::Workspace* w : m->workspaces()) total += (int64_t)w->cap;
+  return total;
 }
 
 int dmx_model_refresh(dmx_model* m, void* stream) {
@@ -2263,7 +2282,7 @@ int dmx_train_forward(dmx_model* m, const float* x, const int64_t* t, const int6
     T.id = 0;  // invalid until the forward below has been enqueued
     TrainArgs a{x, t, y, vals, mask, n, h, w, eps, geom};
     with_fp32(m, [&] {
-      run_arena(m, st, m->tws, m->tws_mem, m->tws_cap, [&](Run& R) { train_fwd_body(R, T, a); });
+      run_ws(m, st, m->tws, [&](Run& R) { train_fwd_body(R, T, a); });
     });
     T.id = ++m->tape_id;
     *tape_id = T.id;
@@ -2282,7 +2301,7 @@ int dmx_train_backward(dmx_model* m, int64_t tape_id, const float* d_eps, const 
     for (int i = 0; i < n_grads; ++i) G.g[m->keys[i].name] = grads[i];
     hipStream_t st = (hipStream_t)stream;
     with_fp32(m, [&] {
-      run_arena(m, st, m->bws, m->bws_mem, m->bws_cap, [&](Run& R) { train_bwd_body(R, *m->tape, G, d_eps, d_geom); });
+      run_ws(m, st, m->bws, [&](Run& R) { train_bwd_body(R, *m->tape, G, d_eps, d_geom); });
     });
   });
 }
@@ -2297,8 +2316,7 @@ int dmx_train_backward_input(dmx_model* m, int64_t tape_id, const float* d_eps, 
     REQUIRE(d_geom == nullptr || m->kind == DMX_UNET_COND_GEOM, "d_geom only for UnetCondWithGeomHead");
     hipStream_t st = (hipStream_t)stream;
     with_fp32(m, [&] {
-      run_arena(m, st, m->bws, m->bws_mem, m->bws_cap,
-                [&](Run& R) { train_bwd_body(R, *m->tape, GradMap{}, d_eps, d_geom, d_x); });
+      run_ws(m, st, m->bws, [&](Run& R) { train_bwd_body(R, *m->tape, GradMap{}, d_eps, d_geom, d_x); });
     });
   });
 }
@@ -2318,8 +2336,7 @@ int dmx_vae_train_forward(dmx_model* m, const float* x, const float* eps, int n,
     VaeTape& T = *m->vtape;
     T.id = 0;  // invalid until the forward below has been enqueued
     with_fp32(m, [&] {
-      run_arena(m, st, m->tws, m->tws_mem, m->tws_cap,
-                [&](Run& R) { vae_train_fwd_body(R, T, x, eps, x_recon, z, kl, n, h, w); });
+      run_ws(m, st, m->tws, [&](Run& R) { vae_train_fwd_body(R, T, x, eps, x_recon, z, kl, n, h, w); });
     });
     T.id = ++m->tape_id;
     *tape_id = T.id;
@@ -2339,8 +2356,7 @@ int dmx_vae_train_backward(dmx_model* m, int64_t tape_id, const float* d_recon, 
     for (int i = 0; i < n_grads; ++i) G.g[m->keys[i].name] = grads[i];
     hipStream_t st = (hipStream_t)stream;
     with_fp32(m, [&] {
-      run_arena(m, st, m->bws, m->bws_mem, m->bws_cap,
-                [&](Run& R) { vae_train_bwd_body(R, *m->vtape, G, d_recon, d_z, d_kl); });
+      run_ws(m, st, m->bws, [&](Run& R) { vae_train_bwd_body(R, *m->vtape, G, d_recon, d_z, d_kl); });
     });
   });
 }

@@ -138,7 +138,6 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
     const std::string layer = R.layer;
     with_fp32(m, [&] {
       train_fwd_body(R, T, ta);
-      R.fwd_x3 = false;
       if (!R.plan) {
         R.layer = "geom.seed";
         R.begin("geom_seed_kernel", 6.0 * a.n * gd, 4.0 * 5.0 * a.n * gd);
@@ -148,8 +147,6 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
       }
       train_bwd_body(R, T, GradMap{}, nullptr, seed, gx);
     });
-    R.amax_src = nullptr;
-    R.amax_uses = 0;
     R.layer = layer;
     if (!R.plan) T.id = ++m->tape_id;
   }
@@ -393,12 +390,12 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
   if (slot == nullptr) {
     // plan + allocate outside capture (a grown arena drops every slot: their graphs point into the
     // old one), then capture the real launches
-    plan_ws(m, st, [&](Run& R) { step_body(R, *a, mode); });
+    plan_ws(m, st, m->ws, [&](Run& R) { step_body(R, *a, mode); });
     slot = m->graphs.victim();
     drop_slot(m, slot);  // a free slot, or the least recently used pair makes room
     GraphPair& gp = slot->val;
     capture(m, st, [&] {
-      Run R{m, st, false, m->ws};
+      Run R{m, st, false, m->ws.a};
       step_body(R, *a, mode);
       decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
     }, &gp.graph, &gp.gexec);
@@ -412,8 +409,8 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
     int64_t* tscr = m->t_scratch;
     capture(m, st, [&] {
       for (int k = 0; k < kGraphSteps; ++k) {
-        m->ws.off = 0;
-        Run R{m, st, false, m->ws};
+        m->ws.a.rewind();
+        Run R{m, st, false, m->ws.a};
         dmx_step_args ak = *a;
         ak.t = (k & 1) ? tscr : tdev;
         step_body(R, ak, mode, {(k & 1) ? tdev : tscr, k > 0});  // cond MLP rows from step 0 of the graph

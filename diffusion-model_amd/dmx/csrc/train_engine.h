@@ -6,12 +6,16 @@
 // Forward = the inference trunk's kernels in exact-fp32 mode (fp32 MFMA implicit GEMMs, no
 // deferred split-K fusion so every raw conv output is materialised) plus the few values the
 // backward needs that inference never stores (pre-GELU FF activations, embedding MLP inputs).
-// The tape lives in its own workspace (m->tws) until the matching dmx_train_backward.
+// The tape lives in its own workspace (dmx_model::tws) until the matching dmx_train_backward.
 // Backward (train.h kernels + the same fp32 implicit GEMM for data gradients):
 //   GroupNorm / LayerNorm / GELU / SiLU / max-pool / bilinear-upsample adjoints, conv and Linear
 //   data gradients as implicit GEMMs over flipped / transposed weights (packed once, refreshed
 //   with the weights), weight gradients on fp32 MFMA (wgrad_kernel), attention core backward by
 //   recomputation.  Parameter gradients are written in the reference's state_dict layout.
+// What a pass needs beyond its Run travels as values: one Bwd per backward pass (gradient
+// destinations, data-only mode, the deferred column sums), and the device-side scale of each dY as
+// an AbsMax handed from where it is measured (measure_absmax, gn_bwd) to the x3 GEMMs that read it
+// (wgrad, dgrad).  Run carries nothing of training's.
 //
 // Included by engine.hip after the inference engine (same translation unit).
 #pragma once
@@ -78,56 +82,20 @@ struct GradMap {
     return it->second;
   }
 };
-// The destination of a parameter gradient, or null in the data-only backward (Run::data_only), which
-// never consults the map: wgrad / dense_dw / zero_grad launch nothing there, and the adjoint kernels
-// that produce affine sums as a by-product leave them in their arena scratch.
-static float* gdst(const Run& R, const GradMap& G, const std::string& name) {
-  return R.data_only ? nullptr : G(name);
-}
 
-// Workspace run twice (plan: sizes only, then real) in a dedicated arena.
-template <typename F>
-static void run_arena(dmx_model* m, hipStream_t st, Arena& A, void*& mem, size_t& cap, F&& body) {
-  A.base = nullptr;
-  A.off = 0;
-  A.plan = true;
-  std::vector<size_t> trace;
-  A.trace = check_args() ? &trace : nullptr;
-  A.n = 0;
-  {
-    Run R{m, st, true, A};
-    A.layer = &R.layer;
-    body(R);
-  }
-  if (A.off > cap) {
-    if (mem) {
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipFree(mem));
-    }
-    mem = nullptr;
-    cap = 0;
-    HIPCHK(hipMalloc(&mem, A.off));
-    cap = A.off;
-  }
-  const size_t planned = A.off;
-  poison(mem, A.off, st);
-  A.base = static_cast<char*>(mem);
-  A.off = 0;
-  A.plan = false;
-  A.n = 0;
-  Run R{m, st, false, A};
-  A.layer = &R.layer;
-  try {
-    body(R);
-  } catch (...) {
-    A.trace = nullptr;
-    A.layer = nullptr;
-    throw;
-  }
-  A.trace = nullptr;
-  A.layer = nullptr;
-  if (A.off != planned) throw Error(DMX_E_INTERNAL, "workspace plan / run mismatch");
-}
+// One backward pass: built by its body (train_bwd_body / vae_train_bwd_body, once per arena pass) and
+// gone with it.
+struct Bwd {
+  const GradMap& G;
+  // the data-only backward: data gradients alone, down to the input.  G is never consulted: wgrad /
+  // dense_dw / zero_grad launch nothing, and the adjoint kernels that produce affine sums as a
+  // by-product leave them in their arena scratch.
+  bool data_only = false;
+  bool defer = false;  // the final-level column sums run batched at the pass's end (colsum_flush)
+  std::vector<ColsumJob> colsums;
+  // the destination of a parameter gradient (null in the data-only backward)
+  float* grad(const std::string& name) const { return data_only ? nullptr : G(name); }
+};
 
 // ---------------------------------------------------------------------------
 // data-gradient weights (packed once on the first training call, refreshed with the rest)
@@ -355,7 +323,6 @@ static void emb_head_slices(dmx_model* m, int off[6], int hc[6]) {
 
 static void train_fwd_body(Run& R, Tape& T, const TrainArgs& a) {
   dmx_model* m = R.m;
-  R.fwd_x3 = true;  // the ResW::t* / AttnW::t* weights (device-split planes) on the split GEMM
   const int N = a.n, H = a.h, W = a.w, HW = H * W;
   T.n = N;
   T.h = H;
@@ -513,89 +480,77 @@ static void train_fwd_body(Run& R, Tape& T, const TrainArgs& a) {
 // ---------------------------------------------------------------------------
 // out[c] = sum over `rows` rows of in[r * stride + c]: one pass for <= 256 rows, else row
 // blocks of 256 into a partial table, then that table's column sums (fixed order).
-// the final level of a column sum: deferred to colsum_flush (train_bwd_body's end) when R.colsum_defer
-static void colsum_final(Run& R, const float* in, int rows, int C, size_t stride, float* outa, float* outb, int cb) {
-  if (R.colsum_defer) {
-    R.colsums.push_back(ColsumJob{in, outa, outb, stride, rows, C, cb});
+// the final level of a column sum: deferred to colsum_flush (the pass's end) when B.defer
+static void colsum_final(Run& R, Bwd& B, const float* in, int rows, int C, size_t stride, float* outa, float* outb,
+                         int cb) {
+  if (B.defer) {
+    B.colsums.push_back(ColsumJob{in, outa, outb, stride, rows, C, cb});
     return;
   }
   colsum_kernel<<<dim3(cdiv(C, 64), 1), 256, 0, R.st>>>(in, rows, C, stride, rows, outa, 0, outb, cb);
   HIPCHK(hipGetLastError());
 }
 
-static void colsum_flush(Run& R) {
-  for (size_t k = 0; k < R.colsums.size(); k += COLSUM_BATCH) {
+static void colsum_flush(Run& R, Bwd& B) {
+  for (size_t k = 0; k < B.colsums.size(); k += COLSUM_BATCH) {
     ColsumBatch b;
     std::memset(&b, 0, sizeof(b));
-    const int nj = (int)std::min<size_t>(COLSUM_BATCH, R.colsums.size() - k);
+    const int nj = (int)std::min<size_t>(COLSUM_BATCH, B.colsums.size() - k);
     int cmax = 0;
     for (int i = 0; i < nj; ++i) {
-      b.j[i] = R.colsums[k + i];
+      b.j[i] = B.colsums[k + i];
       cmax = std::max(cmax, b.j[i].C);
     }
     colsum_batch_kernel<<<dim3(cdiv(cmax, 64), nj), 256, 0, R.st>>>(b);
     HIPCHK(hipGetLastError());
   }
-  R.colsums.clear();
+  B.colsums.clear();
 }
 
-static void colsum(Run& R, const float* in, int rows, int C, size_t stride, float* out) {
+static void colsum(Run& R, Bwd& B, const float* in, int rows, int C, size_t stride, float* out) {
   const int rpb = 256, nb = cdiv(rows, rpb);
   float* part = nb > 1 ? R.ws.get<float>((size_t)nb * C) : nullptr;
   if (R.plan) return;
   if (nb == 1) {
-    colsum_final(R, in, rows, C, stride, out, nullptr, 0);
+    colsum_final(R, B, in, rows, C, stride, out, nullptr, 0);
   } else {
     colsum_kernel<<<dim3(cdiv(C, 64), nb), 256, 0, R.st>>>(in, rows, C, stride, rpb, part, 0);
     HIPCHK(hipGetLastError());
-    colsum_final(R, part, nb, C, C, out, nullptr, 0);
+    colsum_final(R, B, part, nb, C, C, out, nullptr, 0);
   }
 }
 
 // outa[c] = sum of in[r][c], outb[c] = sum of in[r][C + c] (rows of 2C floats at `stride`): one launch
 // per level instead of two colsum calls
-static void colsum_pair(Run& R, const float* in, int rows, int C, size_t stride, float* outa, float* outb) {
+static void colsum_pair(Run& R, Bwd& B, const float* in, int rows, int C, size_t stride, float* outa, float* outb) {
   const int rpb = 256, nb = cdiv(rows, rpb);
   float* part = nb > 1 ? R.ws.get<float>((size_t)nb * 2 * C) : nullptr;
   if (R.plan) return;
   if (nb == 1) {
-    colsum_final(R, in, rows, 2 * C, stride, outa, outb, C);
+    colsum_final(R, B, in, rows, 2 * C, stride, outa, outb, C);
   } else {
     colsum_kernel<<<dim3(cdiv(2 * C, 64), nb), 256, 0, R.st>>>(in, rows, 2 * C, stride, rpb, part, 0);
     HIPCHK(hipGetLastError());
-    colsum_final(R, part, nb, 2 * C, 2 * C, outa, outb, C);
+    colsum_final(R, B, part, nb, 2 * C, 2 * C, outa, outb, C);
   }
 }
 
 // bias gradient = column sums of dY [M][C]
-static void bias_grad(Run& R, const float* dy, int M, int C, float* out) { colsum(R, dy, M, C, C, out); }
+static void bias_grad(Run& R, Bwd& B, const float* dy, int M, int C, float* out) { colsum(R, B, dy, M, C, C, out); }
 
-// Per-block partial maxima of |dY| for the device-side operand scale of the f16-core data and weight
-// gradients (X3Params::a_amax, WgradParams::dy_amax).  The weight and data gradients of a layer read
-// the same dY back to back (wgrad, then dgrad): the measurement is reused once, by the very next call
-// on the same tensor, and then dropped — a later call on that buffer (its content may have changed)
-// measures again.  Same decisions in the plan and the real pass (arena pointers correspond one to one).
-static const unsigned* dy_amax(Run& R, const float* dy, size_t n, int* parts) {
-  if (R.amax_src == dy && R.amax_n == n && R.amax_uses > 0) {
-    if (--R.amax_uses == 0) R.amax_src = nullptr;
-    *parts = R.amax_parts;
-    return R.amax_slot;
-  }
-  const int np = (int)std::min<size_t>((n + 4095) / 4096, 256);  // (>= 4 float4 per thread)
+// The device-side operand scale of the f16-core weight and data gradients that read the `count` floats at
+// p (wgrad, dgrad), measured where no producer wrote it as a by-product (gn_bwd, gn8_bwd do).  It holds
+// for the buffer's content at this point: whoever rewrites the buffer measures again.
+static AbsMax measure_absmax(Run& R, const float* p, size_t count) {
+  const int np = (int)std::min<size_t>((count + 4095) / 4096, 256);  // (>= 4 float4 per thread)
   unsigned* slot = R.ws.get<unsigned>(256);
   if (!R.plan) {
-    R.begin("absmax_part_kernel", 0.0, 4.0 * (double)n);
-    absmax_part_kernel<<<np, 256, 0, R.st>>>(dy, n, slot);
+    R.begin("absmax_part_kernel", 0.0, 4.0 * (double)count);
+    absmax_part_kernel<<<np, 256, 0, R.st>>>(p, count, slot);
     R.end();
     HIPCHK(hipGetLastError());
   }
-  R.amax_src = dy;
-  R.amax_n = n;
-  R.amax_slot = slot;
-  R.amax_parts = np;
-  R.amax_uses = 1;
-  *parts = np;
-  return slot;
+  return AbsMax{slot, np};
 }
 
 static bool wgrad_fast(int Cin, int Cout) { return Cin % 64 == 0 && Cout % 64 == 0; }
@@ -603,9 +558,11 @@ static bool wgrad_fast(int Cin, int Cout) { return Cin % 64 == 0 && Cout % 64 ==
 // weight gradient of a conv3x3 (taps 9) / Linear (taps 1) over NHWC input x and NHWC dY
 // geo 1 / 2 (taps 16, WgradParams): the VAE's Conv2d / ConvTranspose2d 4x4 s2 p1 — rows on the small
 // H x W map, x on the 2H x 2W map; geo 2 swaps the operands' roles (dy = the layer input, x = dY)
-static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, int Cin, int Cout, int taps,
-                  int cin_real, float* grad, float* bias_grad_out = nullptr, int geo = 0) {
-  if (R.data_only) return;  // (no parameter gradient: neither the launches nor their workspace)
+// dy_scale: the scale of the operand that holds dY (`dy`; the gathered `x` when geo 2 swaps the roles) for
+// the x3 kernels (wgrad_fast); the fp32 kernels take none
+static void wgrad(Run& R, Bwd& B, const float* dy, const float* x, int N, int H, int W, int Cin, int Cout, int taps,
+                  int cin_real, float* grad, float* bias_grad_out, AbsMax dy_scale, int geo = 0) {
+  if (B.data_only) return;  // (no parameter gradient: neither the launches nor their workspace)
   const int M = N * H * W, K = taps * Cin;
   const size_t xel = (size_t)M * Cin * (geo != 0 ? 4 : 1);  // elements of the gathered operand
   if ((geo != 0) != (taps == 16)) throw Error(DMX_E_INTERNAL, "wgrad: 16 taps go with the stride-2 geometries");
@@ -623,13 +580,12 @@ static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, 
   float* part = R.ws.get<float>((size_t)splits * Cout * K);
   // bias gradient: column sums of dY, from the fast kernel's k-tile-0 blocks (per split)
   float* bpart = (bias_grad_out != nullptr && fast) ? R.ws.get<float>((size_t)splits * Cout) : nullptr;
-  int nparts = 0;
-  // (x3 products: the scale of the operand that holds dY — the gathered one with swapped roles)
-  const unsigned* amax = !fast ? nullptr : geo == 2 ? dy_amax(R, x, xel, &nparts) : dy_amax(R, dy, (size_t)M * Cout, &nparts);
+  if (fast && dy_scale.part == nullptr) throw Error(DMX_E_INTERNAL, "wgrad: the x3 kernels need dY's scale");
+  if (!fast) dy_scale = AbsMax{};
   if (!R.plan) {
     check_range(R, dy, (size_t)M * Cout * 4, "wgrad dY");
     check_range(R, x, xel * 4, "wgrad X");
-    WgradParams p{dy, x, N, H, W, Cin, Cout, taps, M, K, rps, part, bpart, amax, nparts};
+    WgradParams p{dy, x, N, H, W, Cin, Cout, taps, M, K, rps, part, bpart, dy_scale.part, dy_scale.n};
     R.begin("wgrad_kernel", 2.0 * M * (double)Cout * K, 4.0 * ((double)M * Cout + (double)xel + (double)splits * Cout * K));
     const dim3 g128(Cout / 128, cdiv(K, 128), splits), g64(Cout / 64, cdiv(K, 128), splits);
     const dim3 gf(cdiv(Cout, 64), cdiv(K, 64), splits);
@@ -653,8 +609,8 @@ static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, 
   }
   // bias gradient = column sums of dY: the fast kernel's per-split sums, else a pass over dY
   if (bias_grad_out != nullptr) {
-    if (fast) colsum(R, bpart, splits, Cout, Cout, bias_grad_out);
-    else bias_grad(R, dy, M, Cout, bias_grad_out);
+    if (fast) colsum(R, B, bpart, splits, Cout, Cout, bias_grad_out);
+    else bias_grad(R, B, dy, M, Cout, bias_grad_out);
   }
 }
 
@@ -663,102 +619,49 @@ static void wgrad(Run& R, const float* dy, const float* x, int N, int H, int W, 
 // max|dY| before the split (gradients sit far below f16's normal range; unscaled, their lo parts went
 // subnormal — 4.6e-4 rel-L2, round 2) and the weights carry a device-side scale refreshed with them
 // (Packer::split_dev), so nothing waits on the host.
-static void dgrad(Run& R, const float* dy, int Cy, int N, int H, int W, const ConvW& dw, float* dx, bool accumulate) {
-  int parts = 0;
-  const unsigned* amax = dy_amax(R, dy, (size_t)N * H * W * Cy, &parts);
-  if (R.data_only) {  // no wgrad shares the measurement: a later call on this buffer measures again
-    R.amax_src = nullptr;
-    R.amax_uses = 0;
-  }
-  R.a_amax = amax;
-  R.a_nparts = parts;
-  try {
-    gemm(R, plain_src(dy, Cy), SRC_PLAIN, N, H, W, dw, accumulate ? EPI_BIAS_RES : EPI_BIAS, dx,
-         accumulate ? dx : nullptr, nullptr, 1);
-  } catch (...) {
-    R.a_amax = nullptr;
-    R.a_nparts = 0;
-    throw;
-  }
-  R.a_amax = nullptr;
-  R.a_nparts = 0;
+static void dgrad(Run& R, const float* dy, int Cy, int N, int H, int W, const ConvW& dw, float* dx, bool accumulate,
+                  AbsMax dy_scale) {
+  if (dy_scale.part == nullptr) throw Error(DMX_E_INTERNAL, "dgrad: the split GEMM needs dY's scale");
+  gemm(R, plain_src(dy, Cy), SRC_PLAIN, N, H, W, dw, accumulate ? EPI_BIAS_RES : EPI_BIAS, dx,
+       accumulate ? dx : nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, dy_scale);
 }
 
-static void gn_bwd_launch(Run& R, const float* r, const float2* rp, int nseg, int rrows, const Vec& g, const Vec& b,
-                          const float* res, int act, const float* dout, int N, int C, int HW, float* dr, float* dres,
-                          int dres_mode, float* chpart, float* demb, int demb_stride, int demb_off,
-                          int ppb, double* bsum, float* bch, unsigned* amax, int achunks);
 static int gn_bwd_achunks(int HW, int C) { return std::max(1, std::min(64, cdiv(HW * C, 4096))); }
 
-static void gn_bwd(Run& R, const float* r, const float2* rp, int nseg, int rrows, const Vec& g, const Vec& b,
-                   const float* res, int act, const float* dout, int N, int C, int HW, float* dr, float* dres,
-                   int dres_mode, float* ggamma, float* gbeta, float* demb, int demb_stride, int demb_off,
-                   int amax_uses = 0) {
+// GroupNorm(1, C) (+ GELU, + residual, + emb sums) adjoint.  p: the tensors and modes (r ... demb_off; the
+// rest zero) — gn_bwd adds pass A's chunking and the scratch.  dgamma / dbeta -> ggamma / gbeta through
+// colsum_pair.  want_absmax: pass B also writes the per-block max |dr|, returned as the scale of the x3
+// gradient GEMMs that read dr next (no separate absmax pass).
+static AbsMax gn_bwd(Run& R, Bwd& B, GnBwdParams p, int N, float* ggamma, float* gbeta, bool want_absmax) {
+  const int C = p.C, HW = p.HW;
   // (the float4 passes: 4 channels per thread, C / 4 threads per pixel row dividing the 256-thread block)
   if (C % 4 != 0 || C / 4 > 256 || 256 % (C / 4) != 0) throw Error(DMX_E_INTERNAL, "gn_bwd: C must be 4 x a divisor of 256");
   // pass A over ~512 blocks in total (>= 16 pixels each)
   const int chunks = std::max(1, std::min(cdiv(512, N), cdiv(HW, 16)));
-  const int ppb = cdiv(HW, chunks);
-  float* chpart = R.ws.get<float>((size_t)N * 2 * C);
-  double* bsum = R.ws.get<double>((size_t)N * chunks * 2);
-  float* bch = R.ws.get<float>((size_t)N * chunks * 3 * C);
-  // amax_uses > 0: pass B also writes the per-block max |dr| — the next amax_uses x3 gradient GEMMs
-  // reading dr take their device-side scale from it (dy_amax) instead of a separate absmax pass
+  p.ppb = cdiv(HW, chunks);
+  p.chunks = cdiv(HW, p.ppb);
+  p.chpart = R.ws.get<float>((size_t)N * 2 * C);
+  p.bsum = R.ws.get<double>((size_t)N * chunks * 2);
+  p.bch = R.ws.get<float>((size_t)N * chunks * 3 * C);
   const int achunks = gn_bwd_achunks(HW, C);
-  unsigned* amax = amax_uses > 0 ? R.ws.get<unsigned>((size_t)N * achunks) : nullptr;
-  if (!R.plan) gn_bwd_launch(R, r, rp, nseg, rrows, g, b, res, act, dout, N, C, HW, dr, dres, dres_mode, chpart,
-                             demb, demb_stride, demb_off, ppb, bsum, bch, amax, achunks);
-  if (amax_uses > 0) {
-    R.amax_src = dr;
-    R.amax_n = (size_t)N * HW * C;
-    R.amax_slot = amax;
-    R.amax_parts = N * achunks;
-    R.amax_uses = amax_uses;
+  unsigned* amax = want_absmax ? R.ws.get<unsigned>((size_t)N * achunks) : nullptr;
+  if (!R.plan) {
+    R.begin("gn_bwd_reduce_kernel", 0.0, 4.0 * (double)N * HW * C * (p.res ? 3 : 2));
+    gn_bwd_reduce_kernel<<<dim3(p.chunks, N), 256, 0, R.st>>>(p);
+    R.end();
+    HIPCHK(hipGetLastError());
+    p.amax_part = amax;
+    R.begin("gn_bwd_apply_kernel", 0.0, 4.0 * (double)N * HW * C * (p.res ? 4 : 3));
+    gn_bwd_apply_kernel<<<dim3(achunks, N), 256, 0, R.st>>>(p);
+    R.end();
+    HIPCHK(hipGetLastError());
   }
-  if (!R.data_only) colsum_pair(R, chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
+  if (!B.data_only) colsum_pair(R, B, p.chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
+  return want_absmax ? AbsMax{amax, N * achunks} : AbsMax{};
 }
 
-static void gn_bwd_launch(Run& R, const float* r, const float2* rp, int nseg, int rrows, const Vec& g, const Vec& b,
-                          const float* res, int act, const float* dout, int N, int C, int HW, float* dr, float* dres,
-                          int dres_mode, float* chpart, float* demb, int demb_stride, int demb_off,
-                          int ppb, double* bsum, float* bch, unsigned* amax, int achunks) {
-  GnBwdParams p;
-  std::memset(&p, 0, sizeof(p));
-  p.r = r;
-  p.rowpart = rp;
-  p.nseg = nseg;
-  p.rrows = rrows;
-  p.gamma = g.p;
-  p.beta = b.p;
-  p.res = res;
-  p.act = act;
-  p.dout = dout;
-  p.C = C;
-  p.HW = HW;
-  p.dr = dr;
-  p.dres = dres;
-  p.dres_mode = dres_mode;
-  p.chpart = chpart;
-  p.demb = demb;
-  p.demb_stride = demb_stride;
-  p.demb_off = demb_off;
-  p.chunks = cdiv(HW, ppb);
-  p.ppb = ppb;
-  p.bsum = bsum;
-  p.bch = bch;
-  R.begin("gn_bwd_reduce_kernel", 0.0, 4.0 * (double)N * HW * C * (res ? 3 : 2));
-  gn_bwd_reduce_kernel<<<dim3(p.chunks, N), 256, 0, R.st>>>(p);
-  R.end();
-  HIPCHK(hipGetLastError());
-  p.amax_part = amax;
-  R.begin("gn_bwd_apply_kernel", 0.0, 4.0 * (double)N * HW * C * (res ? 4 : 3));
-  gn_bwd_apply_kernel<<<dim3(achunks, N), 256, 0, R.st>>>(p);
-  R.end();
-  HIPCHK(hipGetLastError());
-}
-
-static void ln_bwd(Run& R, const float* x, const Vec& w, const float* dy, float* dx, bool accumulate, int M, int C,
-                   float* gw, float* gb) {
+static void ln_bwd(Run& R, Bwd& B, const float* x, const Vec& w, const float* dy, float* dx, bool accumulate, int M,
+                   int C, float* gw, float* gb) {
   const int blocks = std::min(cdiv(M, 4), 512);
   float* part = R.ws.get<float>((size_t)blocks * 2 * C);
   if (!R.plan) {
@@ -772,7 +675,7 @@ static void ln_bwd(Run& R, const float* x, const Vec& w, const float* dy, float*
     R.end();
     HIPCHK(hipGetLastError());
   }
-  if (!R.data_only) colsum_pair(R, part, blocks, C, 2 * (size_t)C, gw, gb);
+  if (!B.data_only) colsum_pair(R, B, part, blocks, C, 2 * (size_t)C, gw, gb);
 }
 
 // the two MFMA attention-backward launches (train.h); st: [N][4][L][3] — with have_stats, slots 0 / 1
@@ -808,72 +711,87 @@ static void attn_core_bwd(Run& R, const float* qkv, const float* o, const float*
 // ResBlock backward: dout -> dx (x's gradient; accumulated when dx_acc), parameter gradients,
 // and the emb slice's per-sample sums into demb (Down / Up second block).
 // dr1_out: where the first conv's output gradient is left for the caller (the input conv's data gradient).
-static void res_bwd(Run& R, const TRes& t, const GradMap& G, const float* dout, float* dx, bool dx_acc, float* demb,
+static void res_bwd(Run& R, Bwd& B, const TRes& t, const float* dout, float* dx, bool dx_acc, float* demb,
                     int demb_stride, float** dr1_out = nullptr) {
   const ResW& w = *t.w;
-  const int N = t.N, H = t.H, W = t.W, M = N * H * W, HW = H * W, seg = 32;
+  const int N = t.N, H = t.H, W = t.W, M = N * H * W, seg = 32;
   const std::string& p = w.prefix;
+  // out = [x +] GN2(conv2(a1)) [+ emb]
   float* dr2 = R.ws.get<float>((size_t)M * w.cout);
-  gn_bwd(R, t.r2, t.rp2, w.cout / seg, t.rr2, w.g2, w.b2, t.residual ? t.x : nullptr, 0, dout, N, w.cout, HW, dr2,
-         t.residual ? dx : nullptr, t.residual ? (dx_acc ? 2 : 1) : 0, gdst(R, G, p + ".double_conv.4.weight"),
-         gdst(R, G, p + ".double_conv.4.bias"), t.emb_off >= 0 ? demb : nullptr, demb_stride, t.emb_off,
-         (!R.data_only && wgrad_fast(w.mid, w.cout) ? 1 : 0) + 1);
-  wgrad(R, dr2, t.a1, N, H, W, w.mid, w.cout, 9, w.mid, gdst(R, G, p + ".double_conv.3.weight"));
+  GnBwdParams g2{};
+  g2.r = t.r2; g2.rowpart = t.rp2; g2.nseg = w.cout / seg; g2.rrows = t.rr2;
+  g2.gamma = w.g2.p; g2.beta = w.b2.p;
+  g2.dout = dout; g2.C = w.cout; g2.HW = H * W; g2.dr = dr2;
+  if (t.residual) { g2.res = t.x; g2.dres = dx; g2.dres_mode = dx_acc ? 2 : 1; }
+  g2.demb = t.emb_off >= 0 ? demb : nullptr; g2.demb_stride = demb_stride; g2.demb_off = t.emb_off;
+  const AbsMax s2 = gn_bwd(R, B, g2, N, B.grad(p + ".double_conv.4.weight"), B.grad(p + ".double_conv.4.bias"), true);
+  wgrad(R, B, dr2, t.a1, N, H, W, w.mid, w.cout, 9, w.mid, B.grad(p + ".double_conv.3.weight"), nullptr, s2);
   float* da1 = R.ws.get<float>((size_t)M * w.mid);
-  dgrad(R, dr2, w.cout, N, H, W, w.d2, da1, false);
+  dgrad(R, dr2, w.cout, N, H, W, w.d2, da1, false, s2);
+  // a1 = GELU(GN1(conv1(x)))
   float* dr1 = R.ws.get<float>((size_t)M * w.mid);
-  gn_bwd(R, t.r1, t.rp1, w.mid / seg, t.rr1, w.g1, w.b1, nullptr, 1, da1, N, w.mid, HW, dr1, nullptr, 0,
-         gdst(R, G, p + ".double_conv.1.weight"), gdst(R, G, p + ".double_conv.1.bias"), nullptr, 0, 0,
-         (!R.data_only && wgrad_fast(w.cin, w.mid) ? 1 : 0) + (dx != nullptr ? 1 : 0));
-  wgrad(R, dr1, t.x, N, H, W, w.cin, w.mid, 9, w.cin_real, gdst(R, G, p + ".double_conv.0.weight"));
-  if (dx != nullptr) dgrad(R, dr1, w.mid, N, H, W, w.d1, dx, t.residual || dx_acc);
+  GnBwdParams g1{};
+  g1.r = t.r1; g1.rowpart = t.rp1; g1.nseg = w.mid / seg; g1.rrows = t.rr1;
+  g1.gamma = w.g1.p; g1.beta = w.b1.p;
+  g1.act = 1; g1.dout = da1; g1.C = w.mid; g1.HW = H * W; g1.dr = dr1;
+  // (dr1's scale has a reader unless this is the input block: no dx, and in the full pass the fp32 wgrad)
+  const bool readers = (!B.data_only && wgrad_fast(w.cin, w.mid)) || dx != nullptr;
+  const AbsMax s1 = gn_bwd(R, B, g1, N, B.grad(p + ".double_conv.1.weight"), B.grad(p + ".double_conv.1.bias"), readers);
+  wgrad(R, B, dr1, t.x, N, H, W, w.cin, w.mid, 9, w.cin_real, B.grad(p + ".double_conv.0.weight"), nullptr, s1);
+  if (dx != nullptr) dgrad(R, dr1, w.mid, N, H, W, w.d1, dx, t.residual || dx_acc, s1);
   if (dr1_out != nullptr) *dr1_out = dr1;
 }
 
-// AttenionBlock backward; dout (the block output's gradient) is consumed (used as scratch).
-static void attn_bwd(Run& R, const TAttn& t, const GradMap& G, float* dout, float* dx) {
+// AttenionBlock backward; dout (the block output's gradient) is consumed (used as scratch).  Buffers are
+// rewritten in place between their uses (GELU' on dh, LN2^T into dout, in_proj^T into dav): every
+// (wgrad, dgrad) pair takes a measurement of its dY as it stands just before the pair.
+static void attn_bwd(Run& R, Bwd& B, const TAttn& t, float* dout, float* dx) {
   const AttnW& a = *t.w;
   const int C = a.c, N = t.N, H = t.H, W = t.W, M = N * H * W, L = H * W;
   const std::string& p = a.prefix;
   // out = ff2(gelu(ff1(al))) + av
-  wgrad(R, dout, t.f, N, H, W, C, C, 1, C, gdst(R, G, p + ".ff_self.3.weight"), gdst(R, G, p + ".ff_self.3.bias"));
+  AbsMax s = measure_absmax(R, dout, (size_t)M * C);
+  wgrad(R, B, dout, t.f, N, H, W, C, C, 1, C, B.grad(p + ".ff_self.3.weight"), B.grad(p + ".ff_self.3.bias"), s);
   float* dh = R.ws.get<float>((size_t)M * C);
-  dgrad(R, dout, C, N, H, W, a.df2, dh, false);
+  dgrad(R, dout, C, N, H, W, a.df2, dh, false, s);
   if (!R.plan) {
     gelu_bwd_kernel<<<ew_blocks((size_t)M * C), 256, 0, R.st>>>(dh, t.h1, dh, (size_t)M * C);
     HIPCHK(hipGetLastError());
   }
-  wgrad(R, dh, t.al, N, H, W, C, C, 1, C, gdst(R, G, p + ".ff_self.1.weight"), gdst(R, G, p + ".ff_self.1.bias"));
+  s = measure_absmax(R, dh, (size_t)M * C);
+  wgrad(R, B, dh, t.al, N, H, W, C, C, 1, C, B.grad(p + ".ff_self.1.weight"), B.grad(p + ".ff_self.1.bias"), s);
   float* dal = R.ws.get<float>((size_t)M * C);
-  dgrad(R, dh, C, N, H, W, a.df1, dal, false);
+  dgrad(R, dh, C, N, H, W, a.df1, dal, false, s);
   // al = LN2(av): dav = dout + LN2^T(dal)
-  ln_bwd(R, t.av, a.l2w, dal, dout, true, M, C, gdst(R, G, p + ".ff_self.0.weight"), gdst(R, G, p + ".ff_self.0.bias"));
+  ln_bwd(R, B, t.av, a.l2w, dal, dout, true, M, C, B.grad(p + ".ff_self.0.weight"), B.grad(p + ".ff_self.0.bias"));
   float* dav = dout;
   // av = out_proj(attn(xl)) + xl
-  wgrad(R, dav, t.ao, N, H, W, C, C, 1, C, gdst(R, G, p + ".mha.out_proj.weight"), gdst(R, G, p + ".mha.out_proj.bias"));
+  s = measure_absmax(R, dav, (size_t)M * C);
+  wgrad(R, B, dav, t.ao, N, H, W, C, C, 1, C, B.grad(p + ".mha.out_proj.weight"), B.grad(p + ".mha.out_proj.bias"), s);
   float* dao = R.ws.get<float>((size_t)M * C);
-  dgrad(R, dav, C, N, H, W, a.dout, dao, false);
+  dgrad(R, dav, C, N, H, W, a.dout, dao, false, s);
   float* dqkv = R.ws.get<float>((size_t)M * 3 * C);
   attn_core_bwd(R, t.qkv, t.ao, dao, dqkv, t.st, N, L, C);
-  wgrad(R, dqkv, t.xl, N, H, W, C, 3 * C, 1, C, gdst(R, G, p + ".mha.in_proj_weight"), gdst(R, G, p + ".mha.in_proj_bias"));
-  dgrad(R, dqkv, 3 * C, N, H, W, a.dqkv, dav, true);  // dxl = dav + in_proj^T(dqkv)
-  ln_bwd(R, t.x, a.l1w, dav, dx, false, M, C, gdst(R, G, p + ".ln.weight"), gdst(R, G, p + ".ln.bias"));
+  s = measure_absmax(R, dqkv, (size_t)M * 3 * C);
+  wgrad(R, B, dqkv, t.xl, N, H, W, C, 3 * C, 1, C, B.grad(p + ".mha.in_proj_weight"), B.grad(p + ".mha.in_proj_bias"), s);
+  dgrad(R, dqkv, 3 * C, N, H, W, a.dqkv, dav, true, s);  // dxl = dav + in_proj^T(dqkv)
+  ln_bwd(R, B, t.x, a.l1w, dav, dx, false, M, C, B.grad(p + ".ln.weight"), B.grad(p + ".ln.bias"));
 }
 
-static void zero_grad(Run& R, const GradMap& G, dmx_model* m, const std::string& name) {
-  if (R.plan || R.data_only) return;
-  for (auto& k : m->keys)
+static void zero_grad(Run& R, Bwd& B, const std::string& name) {
+  if (R.plan || B.data_only) return;
+  for (auto& k : R.m->keys)
     if (k.name == name) {
       size_t n = 1;
       for (auto s : k.shape) n *= (size_t)s;
-      HIPCHK(hipMemsetAsync(G(name), 0, n * sizeof(float), R.st));
+      HIPCHK(hipMemsetAsync(B.grad(name), 0, n * sizeof(float), R.st));
     }
 }
 
 // dW[o][k] = sum_r dY[r][o] x[r][k], db[o] = sum_r dY[r][o]
-static void dense_dw(Run& R, const float* dy, int ldy, const float* x, int ldx, int rows, int O, int K, float* dw,
-                     float* db) {
-  if (R.data_only) return;
+static void dense_dw(Run& R, Bwd& B, const float* dy, int ldy, const float* x, int ldx, int rows, int O, int K,
+                     float* dw, float* db) {
+  if (B.data_only) return;
   small_gemm(R, SmallGemm{dy, x, 1, ldy, ldx, 1, O, K, rows, 0, dw, K, nullptr, 0});
   if (R.plan || db == nullptr) return;
   dense_db_kernel<<<cdiv(O, 256), 256, 0, R.st>>>(dy, ldy, rows, O, db);
@@ -892,8 +810,7 @@ static void dense_dx(Run& R, const float* dy, int ldy, const float* w, int rows,
 static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps, const float* d_geom,
                            float* d_x = nullptr) {
   dmx_model* m = R.m;
-  R.data_only = d_x != nullptr;
-  R.colsum_defer = !R.plan && !R.data_only;  // the final-level column sums run batched at the end (colsum_flush)
+  Bwd B{G, d_x != nullptr, !R.plan && d_x == nullptr};
   const int N = T.n, H = T.h, W = T.w, HW = H * W, M = N * HW, Co = m->in_ch;
   // heads
   R.layer = "train.heads.bwd";
@@ -907,22 +824,22 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     }
     HIPCHK(hipGetLastError());
   }
-  wgrad(R, dyo, T.feat, N, H, W, 64, Co, 1, 64, gdst(R, G, "out.weight"), gdst(R, G, "out.bias"));
+  wgrad(R, B, dyo, T.feat, N, H, W, 64, Co, 1, 64, B.grad("out.weight"), B.grad("out.bias"), AbsMax{});  // (fp32 kernel)
   dense_dx(R, dyo, Co, srcp(m, "out.weight"), M, Co, 64, dfeat, 64, false);
   if (m->kind == DMX_UNET_COND_GEOM) {
     const int gh = m->cfg.ghid, gd = m->cfg.gdim;
     float* dhs = R.ws.get<float>((size_t)N * gh);
     float* dg = R.ws.get<float>((size_t)N * 64);
     if (d_geom != nullptr) {
-      dense_dw(R, d_geom, gd, T.hs, gh, N, gd, gh, gdst(R, G, "geom_head.mlp.2.weight"),
-               gdst(R, G, "geom_head.mlp.2.bias"));
+      dense_dw(R, B, d_geom, gd, T.hs, gh, N, gd, gh, B.grad("geom_head.mlp.2.weight"),
+               B.grad("geom_head.mlp.2.bias"));
       dense_dx(R, d_geom, gd, srcp(m, "geom_head.mlp.2.weight"), N, gd, gh, dhs, gh, false);
       if (!R.plan) {
         silu_bwd_kernel<<<ew_blocks((size_t)N * gh), 256, 0, R.st>>>(dhs, T.hpre, dhs, (size_t)N * gh, 0);
         HIPCHK(hipGetLastError());
       }
-      dense_dw(R, dhs, gh, T.g, 64, N, gh, 64, gdst(R, G, "geom_head.mlp.0.weight"),
-               gdst(R, G, "geom_head.mlp.0.bias"));
+      dense_dw(R, B, dhs, gh, T.g, 64, N, gh, 64, B.grad("geom_head.mlp.0.weight"),
+               B.grad("geom_head.mlp.0.bias"));
       dense_dx(R, dhs, gh, srcp(m, "geom_head.mlp.0.weight"), N, gh, 64, dg, 64, false);
       if (!R.plan) {
         gap_bwd_kernel<<<ew_blocks((size_t)M * 64), 256, 0, R.st>>>(dg, N, HW, dfeat);
@@ -931,11 +848,11 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     } else {
       for (const char* k : {"geom_head.mlp.0.weight", "geom_head.mlp.0.bias", "geom_head.mlp.2.weight",
                             "geom_head.mlp.2.bias"})
-        zero_grad(R, G, m, k);
+        zero_grad(R, B, k);
     }
   }
   // (the data-only backward needs no embedding gradient: the blocks' emb sums are not formed)
-  float* demb = R.data_only ? nullptr : R.ws.get<float>((size_t)N * m->hsum);
+  float* demb = B.data_only ? nullptr : R.ws.get<float>((size_t)N * m->hsum);
   float* dskip[3];
   for (int i = 0; i < 3; ++i) dskip[i] = R.ws.get<float>((size_t)N * T.sh[i] * T.sw[i] * T.sc[i]);
   // up path, last block first
@@ -946,11 +863,11 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     const int Mi = N * u.H * u.W, Cin = u.C0 + u.C1;
     R.layer = "train.up" + std::to_string(i + 1) + ".bwd";
     float* dxs = R.ws.get<float>((size_t)Mi * m->up[i].cout);
-    attn_bwd(R, T.usa[i], G, dcur, dxs);
+    attn_bwd(R, B, T.usa[i], dcur, dxs);
     float* dh0 = R.ws.get<float>((size_t)Mi * Cin);
-    res_bwd(R, T.ur1[i], G, dxs, dh0, false, demb, m->hsum);
+    res_bwd(R, B, T.ur1[i], dxs, dh0, false, demb, m->hsum);
     float* dcat = R.ws.get<float>((size_t)Mi * Cin);
-    res_bwd(R, T.ur0[i], G, dh0, dcat, false, nullptr, 0);
+    res_bwd(R, B, T.ur0[i], dh0, dcat, false, nullptr, 0);
     float* dlow = R.ws.get<float>((size_t)N * u.Hs * u.Ws * u.C1);
     if (!R.plan) {
       const size_t tot = (size_t)Mi * u.C0 + (size_t)N * u.Hs * u.Ws * u.C1;
@@ -964,7 +881,7 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     R.layer = "train.bot" + std::to_string(i + 1) + ".bwd";
     const TRes& b = T.bot[i];
     float* d = R.ws.get<float>((size_t)b.N * b.H * b.W * b.w->cin);
-    res_bwd(R, b, G, dcur, d, false, nullptr, 0);
+    res_bwd(R, B, b, dcur, d, false, nullptr, 0);
     dcur = d;
   }
   for (int i = 2; i >= 0; --i) {
@@ -972,11 +889,11 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
     const TRes& r1 = T.dr1[i];
     const int Mi = N * r1.H * r1.W, Cin = T.sc[i];
     float* dxs = R.ws.get<float>((size_t)Mi * m->down[i].cout);
-    attn_bwd(R, T.dsa[i], G, dcur, dxs);
+    attn_bwd(R, B, T.dsa[i], dcur, dxs);
     float* dh0 = R.ws.get<float>((size_t)Mi * Cin);
-    res_bwd(R, r1, G, dxs, dh0, false, demb, m->hsum);
+    res_bwd(R, B, r1, dxs, dh0, false, demb, m->hsum);
     float* dpool = R.ws.get<float>((size_t)Mi * Cin);
-    res_bwd(R, T.dr0[i], G, dh0, dpool, false, nullptr, 0);
+    res_bwd(R, B, T.dr0[i], dh0, dpool, false, nullptr, 0);
     if (!R.plan) {
       maxpool_bwd_kernel<<<ew_blocks((size_t)N * T.sh[i] * T.sw[i] * Cin), 256, 0, R.st>>>(
           T.skip[i], dpool, dskip[i], N, T.sh[i], T.sw[i], Cin, 1);
@@ -986,15 +903,14 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
   }
   R.layer = "train.inc.bwd";
   float* dr1 = nullptr;
-  res_bwd(R, T.inc, G, dcur, nullptr, false, nullptr, 0, &dr1);
-  if (R.data_only) {
+  res_bwd(R, B, T.inc, dcur, nullptr, false, nullptr, 0, &dr1);
+  if (B.data_only) {
     if (!R.plan) {
       R.begin("conv0_dgrad_kernel", 2.0 * M * 9.0 * 64 * Co, 4.0 * ((double)M * 64 + (double)M * Co));
       launch_conv0_dgrad(dr1, srcp(m, "inc.double_conv.0.weight"), Co, N, H, W, d_x, R.st);
       R.end();
       HIPCHK(hipGetLastError());
     }
-    R.data_only = false;
     return;
   }
   // embedding
@@ -1005,29 +921,28 @@ static void train_bwd_body(Run& R, Tape& T, const GradMap& G, const float* d_eps
   emb_head_slices(m, off, hc);
   for (int i = 0; i < 6; ++i) {
     const std::string p = std::string(kEmbHeads[i]) + ".emb_layer.1";
-    dense_dw(R, demb + off[i], m->hsum, T.s, 256, N, hc[i], 256, G(p + ".weight"), G(p + ".bias"));
+    dense_dw(R, B, demb + off[i], m->hsum, T.s, 256, N, hc[i], 256, B.grad(p + ".weight"), B.grad(p + ".bias"));
     dense_dx(R, demb + off[i], m->hsum, srcp(m, p + ".weight"), N, hc[i], 256, ds, 256, i > 0);
   }
   if (!R.plan) {
     silu_bwd_kernel<<<ew_blocks((size_t)N * 256), 256, 0, R.st>>>(ds, T.v, dv, (size_t)N * 256, 0);
-    class_emb_bwd_kernel<<<m->cfg.ncls, 256, 0, R.st>>>(dv, T.y, N, m->cfg.ncls, G("class_emb.weight"));
+    class_emb_bwd_kernel<<<m->cfg.ncls, 256, 0, R.st>>>(dv, T.y, N, m->cfg.ncls, B.grad("class_emb.weight"));
     HIPCHK(hipGetLastError());
   }
   if (T.cond) {
     float* dch = R.ws.get<float>((size_t)N * 256);
-    dense_dw(R, dv, 256, T.ch, 256, N, 256, 256, G("cond_mlp.2.weight"), G("cond_mlp.2.bias"));
+    dense_dw(R, B, dv, 256, T.ch, 256, N, 256, 256, B.grad("cond_mlp.2.weight"), B.grad("cond_mlp.2.bias"));
     dense_dx(R, dv, 256, srcp(m, "cond_mlp.2.weight"), N, 256, 256, dch, 256, false);
     if (!R.plan) {
       silu_bwd_kernel<<<ew_blocks((size_t)N * 256), 256, 0, R.st>>>(dch, T.ca, dch, (size_t)N * 256, 0);
       HIPCHK(hipGetLastError());
     }
-    dense_dw(R, dch, 256, T.in24, 24, N, 256, 24, G("cond_mlp.0.weight"), G("cond_mlp.0.bias"));
+    dense_dw(R, B, dch, 256, T.in24, 24, N, 256, 24, B.grad("cond_mlp.0.weight"), B.grad("cond_mlp.0.bias"));
   } else {
     for (const char* k : {"cond_mlp.0.weight", "cond_mlp.0.bias", "cond_mlp.2.weight", "cond_mlp.2.bias"})
-      zero_grad(R, G, m, k);
+      zero_grad(R, B, k);
   }
-  if (!R.plan) colsum_flush(R);
-  R.colsum_defer = false;
+  if (!R.plan) colsum_flush(R, B);
 }
 
 static void check_train(dmx_model* m, int n, int h, int w) {

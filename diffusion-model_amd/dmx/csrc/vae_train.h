@@ -234,7 +234,7 @@ static __global__ __launch_bounds__(256) void vae_dec0_dgrad_kernel(const float*
 // sum(gamma dy xhat) per group and of dgamma = sum(dy xhat), dbeta = sum(dy) per channel;
 // pass B (grid (achunks, N)): the partials in chunk order, then
 //   dr = rstd_g (gamma dy - S1_g / cnt - xhat S2_g / cnt),  cnt = HW C / 8,
-// and the per-block max |dr| for the x3 gradient GEMMs that read dr next (dy_amax).
+// and the per-block max |dr| for the x3 gradient GEMMs that read dr next (gn8_bwd's AbsMax).
 // C / 4 divides 256 and C / 8 is a multiple of 4: a thread's float4 lies in one group.
 // ---------------------------------------------------------------------------
 struct Gn8BwdParams {

@@ -10,6 +10,8 @@
 // data gradient (conv3x3: flipped conv; Conv2d s2: the 4-phase ConvT GEMM; ConvT: the conv4x4-s2 GEMM —
 // both read the forward weight tensor as it lies, the channel roles swap by reinterpretation) -> heads /
 // reparameterisation / clamp / KL adjoint -> encoder stages.  No gradient for x.
+// The pass's state is train_engine.h's: one Bwd per pass, and each stage's dY scale as the AbsMax that
+// gn8_bwd returns, handed to the stage's wgrad and dgrad.
 //
 // Included by engine.hip after train_engine.h (same translation unit).
 #pragma once
@@ -131,7 +133,6 @@ static VStage vae_train_stage(Run& R, const ConvW& cw, const Vec& g, const Vec& 
 static void vae_train_fwd_body(Run& R, VaeTape& T, const float* x, const float* eps, float* x_recon, float* z,
                                float* kl, int n, int h, int w) {
   dmx_model* m = R.m;
-  R.fwd_x3 = true;  // the venc_t / vdec_t weights (device-split planes) on the split GEMM
   T.n = n;
   T.h = h;
   T.w = w;
@@ -188,9 +189,10 @@ static void vae_train_fwd_body(Run& R, VaeTape& T, const float* x, const float* 
 // ---------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------
-// GroupNorm(8) + GELU adjoint (vae_train.h): dout -> dr, dgamma / dbeta through colsum_pair; amax_uses as gn_bwd
-static void gn8_bwd(Run& R, const VStage& t, const Vec& g, const Vec& b, const float* dout, int N, float* dr,
-                    float* ggamma, float* gbeta, int amax_uses) {
+// GroupNorm(8) + GELU adjoint (vae_train.h): dout -> dr, dgamma / dbeta through colsum_pair; want_absmax and the
+// returned scale of dr as gn_bwd
+static AbsMax gn8_bwd(Run& R, Bwd& B, const VStage& t, const Vec& g, const Vec& b, const float* dout, int N, float* dr,
+                      float* ggamma, float* gbeta, bool want_absmax) {
   const int C = t.cout, HW = t.Ho * t.Wo;
   if (C % 32 != 0 || C / 4 > 64 || 256 % (C / 4) != 0) throw Error(DMX_E_INTERNAL, "gn8_bwd: C must be 64, 128 or 256");
   const int chunks = std::max(1, std::min(cdiv(512, N), cdiv(HW, 16)));
@@ -199,7 +201,7 @@ static void gn8_bwd(Run& R, const VStage& t, const Vec& g, const Vec& b, const f
   double* bsum = R.ws.get<double>((size_t)N * chunks * 16);
   float* bch = R.ws.get<float>((size_t)N * chunks * 2 * C);
   const int achunks = gn_bwd_achunks(HW, C);
-  unsigned* amax = amax_uses > 0 ? R.ws.get<unsigned>((size_t)N * achunks) : nullptr;
+  unsigned* amax = want_absmax ? R.ws.get<unsigned>((size_t)N * achunks) : nullptr;
   if (!R.plan) {
     Gn8BwdParams p;
     std::memset(&p, 0, sizeof(p));
@@ -226,69 +228,46 @@ static void gn8_bwd(Run& R, const VStage& t, const Vec& g, const Vec& b, const f
     R.end();
     HIPCHK(hipGetLastError());
   }
-  if (amax_uses > 0) {
-    R.amax_src = dr;
-    R.amax_n = (size_t)N * HW * C;
-    R.amax_slot = amax;
-    R.amax_parts = N * achunks;
-    R.amax_uses = amax_uses;
-  }
-  colsum_pair(R, chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
-}
-
-// data gradient through a packed weight whose GEMM rows run over the H x W grid while dY has n_el
-// elements (the conv4x4-s2 GEMM of a ConvT's gradient reads dY on the 2H x 2W map): dgrad() with that count
-static void vae_dgrad(Run& R, const float* dy, int Cy, size_t n_el, int N, int H, int W, const ConvW& dw, float* dx) {
-  int parts = 0;
-  const unsigned* amax = dy_amax(R, dy, n_el, &parts);
-  R.a_amax = amax;
-  R.a_nparts = parts;
-  try {
-    gemm(R, plain_src(dy, Cy), SRC_PLAIN, N, H, W, dw, EPI_BIAS, dx, nullptr, nullptr, 1);
-  } catch (...) {
-    R.a_amax = nullptr;
-    R.a_nparts = 0;
-    throw;
-  }
-  R.a_amax = nullptr;
-  R.a_nparts = 0;
+  colsum_pair(R, B, chpart, N, C, 2 * (size_t)C, ggamma, gbeta);
+  return want_absmax ? AbsMax{amax, N * achunks} : AbsMax{};
 }
 
 // One stage backward: dout (gradient of the stage's activation) -> parameter gradients of the conv
 // (`p`.weight / .bias) and its GroupNorm (`pn`), and the gradient of the stage's input (returned; null
 // when dw == nullptr: the caller computes it, or the input takes none).
 // kind 0 conv3x3, 1 conv4x4 s2, 2 ConvT 4x4 s2; cin_real: channels of the reference's weight tensor.
-static float* vae_stage_bwd(Run& R, const VStage& t, const GradMap& G, const std::string& p, const std::string& pn,
+static float* vae_stage_bwd(Run& R, Bwd& B, const VStage& t, const std::string& p, const std::string& pn,
                             const Vec& g, const Vec& b, const ConvW* dw, int kind, int cin_real, const float* dout,
                             int N, float** dr_out = nullptr) {
   const int C = t.cout, Mo = N * t.Ho * t.Wo;
-  const size_t nel = (size_t)Mo * C;
-  float* dr = R.ws.get<float>(nel);
+  float* dr = R.ws.get<float>((size_t)Mo * C);
   if (dr_out != nullptr) *dr_out = dr;
+  // dr's scale: read by the x3 weight gradient and by the data gradient
   const bool fast = kind == 2 ? wgrad_fast(C, t.cin) : wgrad_fast(t.cin, C);
-  gn8_bwd(R, t, g, b, dout, N, dr, G(pn + ".weight"), G(pn + ".bias"), (fast ? 1 : 0) + (dw != nullptr ? 1 : 0));
+  const AbsMax s = gn8_bwd(R, B, t, g, b, dout, N, dr, B.grad(pn + ".weight"), B.grad(pn + ".bias"), fast || dw != nullptr);
   if (kind == 2) {
     // rows = the input map's pixels, "dY" operand = the layer input, gathered operand = dY (2H x 2W)
-    wgrad(R, t.in, dr, N, t.H, t.W, C, t.cin, 16, C, G(p + ".weight"), nullptr, 2);
+    wgrad(R, B, t.in, dr, N, t.H, t.W, C, t.cin, 16, C, B.grad(p + ".weight"), nullptr, s, 2);
   } else {
-    wgrad(R, dr, t.in, N, t.Ho, t.Wo, t.cin, C, kind == 1 ? 16 : 9, cin_real, G(p + ".weight"), G(p + ".bias"), kind);
+    wgrad(R, B, dr, t.in, N, t.Ho, t.Wo, t.cin, C, kind == 1 ? 16 : 9, cin_real, B.grad(p + ".weight"),
+          B.grad(p + ".bias"), s, kind);
   }
   float* dx = nullptr;
   if (dw != nullptr) {
     dx = R.ws.get<float>((size_t)N * t.H * t.W * t.cin);
     // conv3x3: flipped conv on dY's grid; conv s2: 4-phase ConvT GEMM, rows = dY's pixels; ConvT: conv4x4-s2
-    // GEMM, rows = the input map's pixels
-    if (kind == 2) vae_dgrad(R, dr, C, nel, N, t.H, t.W, *dw, dx);
-    else vae_dgrad(R, dr, C, nel, N, t.Ho, t.Wo, *dw, dx);
+    // GEMM, rows = the input map's pixels (dY on the 2H x 2W map)
+    if (kind == 2) dgrad(R, dr, C, N, t.H, t.W, *dw, dx, false, s);
+    else dgrad(R, dr, C, N, t.Ho, t.Wo, *dw, dx, false, s);
   }
-  if (kind == 2) bias_grad(R, dr, Mo, C, G(p + ".bias"));  // (after the x3 readers: dy_amax's reuse is consecutive)
+  if (kind == 2) bias_grad(R, B, dr, Mo, C, B.grad(p + ".bias"));
   return dx;
 }
 
 static void vae_train_bwd_body(Run& R, VaeTape& T, const GradMap& G, const float* d_recon, const float* d_z,
                                const float* d_kl) {
   dmx_model* m = R.m;
-  R.colsum_defer = !R.plan;  // the final-level column sums run batched at the end (colsum_flush)
+  Bwd B{G, false, !R.plan};
   const int N = T.n, H = T.h, W = T.w, HW = H * W, M = N * HW;
   const int hl = H / 8, wl = W / 8, HWl = hl * wl, Ml = N * HWl;
   // tail: sigmoid adjoint folded into the staging of dec.18's dY, its weight / bias and data gradients
@@ -311,10 +290,10 @@ static void vae_train_bwd_body(Run& R, VaeTape& T, const GradMap& G, const float
       vae_tail_wgrad_kernel<<<nb, 256, 0, R.st>>>(dpre, T.dec[5].a, N, H, W, ppb, part);
       R.end();
       HIPCHK(hipGetLastError());
-      wgrad_finish_kernel<<<cdiv(3 * 576, 64), 256, 0, R.st>>>(part, nb, 3, 64, 64, 9, G("dec.18.weight"));
+      wgrad_finish_kernel<<<cdiv(3 * 576, 64), 256, 0, R.st>>>(part, nb, 3, 64, 64, 9, B.grad("dec.18.weight"));
       HIPCHK(hipGetLastError());
     }
-    bias_grad(R, dpre, M, 3, G("dec.18.bias"));
+    bias_grad(R, B, dpre, M, 3, B.grad("dec.18.bias"));
   }
   if (!R.plan) {
     R.begin("vae_tail_dgrad_kernel", 2.0 * M * 64.0 * 27.0, 4.0 * (double)M * (64 + 3));
@@ -326,7 +305,7 @@ static void vae_train_bwd_body(Run& R, VaeTape& T, const GradMap& G, const float
   for (int s = 5; s >= 0; --s) {
     R.layer = "vae.train.dec" + std::to_string(s) + ".bwd";
     const std::string p = "dec." + std::to_string(3 * s), pn = "dec." + std::to_string(3 * s + 1);
-    dcur = vae_stage_bwd(R, T.dec[s], G, p, pn, m->vg[s], m->vb[s], s > 0 ? &m->vdec_d[s] : nullptr, (s & 1) ? 2 : 0,
+    dcur = vae_stage_bwd(R, B, T.dec[s], p, pn, m->vg[s], m->vb[s], s > 0 ? &m->vdec_d[s] : nullptr, (s & 1) ? 2 : 0,
                          kVaeDecCin[s], dcur, N, &d0);
   }
   // dec.0's data gradient into the decoder input, then the heads / reparameterisation / KL adjoint
@@ -343,20 +322,19 @@ static void vae_train_bwd_body(Run& R, VaeTape& T, const GradMap& G, const float
     HIPCHK(hipGetLastError());
   }
   const float* act = T.enc[5].a;
-  dense_dw(R, dheads, 8, act, 256, Ml, 4, 256, G("to_mu.weight"), nullptr);
-  dense_dw(R, dheads + 4, 8, act, 256, Ml, 4, 256, G("to_logvar.weight"), nullptr);
-  colsum_pair(R, dheads, Ml, 4, 8, G("to_mu.bias"), G("to_logvar.bias"));
+  dense_dw(R, B, dheads, 8, act, 256, Ml, 4, 256, B.grad("to_mu.weight"), nullptr);
+  dense_dw(R, B, dheads + 4, 8, act, 256, Ml, 4, 256, B.grad("to_logvar.weight"), nullptr);
+  colsum_pair(R, B, dheads, Ml, 4, 8, B.grad("to_mu.bias"), B.grad("to_logvar.bias"));
   dense_dx(R, dheads, 8, srcp(m, "to_mu.weight"), Ml, 4, 256, dact, 256, false);
   dense_dx(R, dheads + 4, 8, srcp(m, "to_logvar.weight"), Ml, 4, 256, dact, 256, true);
   dcur = dact;
   for (int i = 5; i >= 0; --i) {
     R.layer = "vae.train.enc" + std::to_string(i) + ".bwd";
     const std::string p = "enc." + std::to_string(3 * i), pn = "enc." + std::to_string(3 * i + 1);
-    dcur = vae_stage_bwd(R, T.enc[i], G, p, pn, m->veg[i], m->veb[i], i > 0 ? &m->venc_d[i] : nullptr, (i & 1) ? 1 : 0,
+    dcur = vae_stage_bwd(R, B, T.enc[i], p, pn, m->veg[i], m->veb[i], i > 0 ? &m->venc_d[i] : nullptr, (i & 1) ? 1 : 0,
                          kVaeEncCin[i], dcur, N);
   }
-  if (!R.plan) colsum_flush(R);
-  R.colsum_defer = false;
+  if (!R.plan) colsum_flush(R, B);
 }
 
 }  // namespace dmx

@@ -223,3 +223,41 @@ def test_refreshed_training_weights_equal_fresh_model(cuda):
     assert torch.equal(eps1, eps2) and torch.equal(g1, g2)
     for n, p in fresh.named_parameters():
         assert torch.equal(grads1[n], p.grad), n
+
+
+def test_backward_bits_do_not_depend_on_what_ran_before(cuda):
+    """A parameter backward, a data-only backward and a geometry-guided step share the backward's code
+    and (the step) the inference arena: (a) forward + backward, (b) forward + input_grad, (c) one eager
+    guided step, (d) = (a) again — every gradient of (d) equals (a)'s bit for bit, and input_grad on
+    (d)'s tape equals (b)'s."""
+    import diff
+    from dmx import synth
+    from models.unet_cond_geom import UnetCondWithGeomHead
+    m = UnetCondWithGeomHead()
+    m.load_state_dict(synth.unet_cond_geom_weights(0))
+    nm = m.to(cuda).eval().native()
+    B, hw = 2, 16
+    g = torch.Generator().manual_seed(33)
+    x = torch.randn((B, 4, hw, hw), generator=g).to(cuda)
+    t = torch.tensor([700, 40], device=cuda)
+    y = torch.tensor([2, 1], device=cuda)
+    vals = torch.rand((B, 12), generator=g).to(cuda)
+    mask = (torch.rand((B, 12), generator=g) > 0.3).float().to(cuda)
+    d_eps = (torch.randn((B, 4, hw, hw), generator=g) * 1e-3).to(cuda)
+    d_geom = (torch.randn((B, 12), generator=g) * 1e-2).to(cuda)
+
+    def full():
+        tape = nm.train_forward(x, t, y, vals, mask)[2]
+        return tape, nm.train_backward(tape, d_eps, d_geom)
+
+    _, ga = full()                                                                   # (a)
+    dx_b = nm.input_grad(nm.train_forward(x, t, y, vals, mask)[2], d_eps, d_geom)    # (b)
+    d = diff.Diffuser(1000, device=cuda)                                             # (c)
+    out = torch.empty_like(x)
+    nm.step(x, out, t, y, 0, vals, mask, 3.0, d.coef_tables(cuda, True), None, seed=5,
+            geom=(torch.full((B,), 1000.0, device=cuda), d.geom_sig(cuda)))
+    assert torch.isfinite(out).all()
+    tape, gd = full()                                                                # (d)
+    for name, _ in nm.keys:
+        assert torch.equal(ga[name], gd[name]), name
+    assert torch.equal(nm.input_grad(tape, d_eps, d_geom), dx_b)
