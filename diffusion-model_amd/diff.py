@@ -130,6 +130,7 @@ class _SamplerPlan:
     known: Optional[tuple] = None          # the known-region blend's operands (engine.known_blend)
     compose: Optional[tuple] = None        # the composed step's branch tables, contiguous on the device
     geom: Optional[tuple] = None           # geometry guidance: (scale row (B,), sig table) on the device
+    perturb: Optional[Tuple[int, int]] = None  # perturbed-attention guidance: (blocks, branches) bit masks of compose
     rows: Optional[Tuple[int, int]] = None  # a shard: the rows [s, e) of the global batch
     x_start: Optional[torch.Tensor] = None  # the latent the loop starts from
 
@@ -170,6 +171,8 @@ class _SamplerPlan:
             kw["rescale"] = self.rescale
         if self.compose is not None:
             kw["compose"] = self.compose
+        if self.perturb is not None:
+            kw["perturb"] = self.perturb
         if guided and self.geom is not None:
             kw["geom"] = self.geom
         return kw
@@ -606,6 +609,82 @@ class Diffuser:
         return (torch.stack(ys).contiguous(), torch.stack(vs).contiguous(), torch.stack(ms).contiguous(),
                 torch.stack(ws).to(device).contiguous())
 
+    # ---- perturbed-attention guidance: one more branch, its self-attention replaced by the identity --
+    PAG_BLOCKS = ("sa1", "sa2", "sa3", "sa4", "sa5", "sa6")  # bit i of dmx_perturb.blocks is PAG_BLOCKS[i]
+
+    def _pag_args(self, pag_scale, pag_blocks, y_list, vals, msk, guidance_scale, compose=None, model=None,
+                  guidance_interval=None, guidance_rescale=0.0, geom_scale=0.0, null_label=0, device="cpu"):
+        """Argument rules of the samplers' (pag_scale, pag_blocks) keywords -> None (pag_scale 0, or B
+        zeros: the call is the one without the keywords) or (branch tables, (blocks, branches)): the
+        tables of _compose_args with one branch appended — the main condition's rows (branch 1) again,
+        which the step runs with identity attention in `pag_blocks` — and the bit masks of
+        include/dmx.h dmx_perturb.  pag_scale = s is a float or B finite floats, all >= 0; the appended
+        branch has the weight row -s and the main branch's becomes fp32(g + s), so the composed mix
+        e_0 + sum_k w_k (e_k - e_0) is e_u + g (e_c - e_u) + s (e_c - e_p).  compose: _compose_args'
+        result for the call; None with guidance_scale > 0 stands for the plain CFG call (base "null"),
+        and with guidance_scale 0 the composition is K = 1 over the main condition as the base:
+        e_c + s (e_c - e_p), at the cost of a CFG step.  pag_blocks is a non-empty collection of names
+        from PAG_BLOCKS, none twice.  A non-zero scale needs a conditional dmx network, at most two
+        `also` specs, and no guidance_interval / guidance_rescale / geom_scale.  Every violation raises
+        ValueError; nothing here touches a GPU unless `device` is one, and nothing is drawn."""
+        B = len(y_list)
+        row = self._weight_row(pag_scale, B, "pag_scale")
+        if bool((row < 0).any()):
+            raise ValueError(f"pag_scale must be >= 0 (got {pag_scale!r})")
+        if not bool((row != 0).any()):
+            return None
+        names = [pag_blocks] if isinstance(pag_blocks, str) else pag_blocks
+        try:
+            names = list(names)
+        except TypeError:
+            raise ValueError(f"pag_blocks must be a collection of names from {self.PAG_BLOCKS} "
+                             f"(got {pag_blocks!r})") from None
+        if not names or any(not isinstance(n, str) or n not in self.PAG_BLOCKS for n in names):
+            raise ValueError(f"pag_blocks must be a non-empty collection of names from {self.PAG_BLOCKS} "
+                             f"(got {pag_blocks!r})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"pag_blocks names a block twice (got {pag_blocks!r})")
+        blocks = sum(1 << self.PAG_BLOCKS.index(n) for n in names)
+        if model is not None and _native_kind(model) not in (1, 2):
+            if _native_kind(model) == 0:
+                raise ValueError("pag_scale needs a dmx network: a foreign model's attention cannot be perturbed")
+            raise ValueError("pag_scale needs a conditional model (UnetCond / UnetCondWithGeomHead)")
+        try:
+            phi = float(guidance_rescale)
+        except (TypeError, ValueError):
+            phi = float("nan")
+        if guidance_interval is not None or phi != 0.0:
+            raise ValueError("pag_scale takes no guidance_interval / guidance_rescale")
+        if bool((self._weight_row(geom_scale, B, "geom_scale") != 0).any()):
+            raise ValueError("pag_scale takes no geom_scale")
+        s_row = row.to(device)
+        if compose is not None:
+            y_rows, v_rows, m_rows, w = compose
+            if y_rows.shape[0] > self.COMPOSE_MAX:
+                raise ValueError(f"pag_scale adds a branch: at most {self.COMPOSE_MAX - 2} specs in `also` with it "
+                                 f"(got {y_rows.shape[0] - 2})")
+            w = torch.cat([w[:1] + s_row, w[1:], -s_row[None]])
+            y_rows, v_rows, m_rows = (torch.cat([r, r[1:2]]) for r in (y_rows, v_rows, m_rows))
+        else:
+            y_call = torch.tensor([int(c) for c in y_list], dtype=torch.long, device=device)
+            v_call, m_call = vals.to(device).float(), msk.to(device).float()
+            try:
+                g = float(guidance_scale) if guidance_scale else 0.0
+            except (TypeError, ValueError):
+                raise ValueError(f"guidance_scale must be a number (got {guidance_scale!r})") from None
+            if not np.isfinite(g):
+                raise ValueError(f"guidance_scale must be finite (got {guidance_scale!r})")
+            if g > 0:  # the plain CFG call as a composition, plus the perturbed branch
+                ys = [torch.full_like(y_call, int(null_label)), y_call, y_call]
+                w = torch.stack([torch.full((B,), g, dtype=torch.float32, device=device) + s_row, -s_row])
+            else:      # no CFG: the main condition is the base
+                ys = [y_call, y_call]
+                w = -s_row[None]
+            y_rows = torch.stack(ys)
+            v_rows, m_rows = torch.stack([v_call] * len(ys)), torch.stack([m_call] * len(ys))
+        K = y_rows.shape[0] - 1
+        return (y_rows.contiguous(), v_rows.contiguous(), m_rows.contiguous(), w.contiguous()), (blocks, 1 << K)
+
     @staticmethod
     def _eps(model, x, t, y, null_label, cond_vals, cond_mask, g, rescale, compose):
         """A foreign model's prediction as the operands (eu, ec, g) of an update.  compose: one call per
@@ -777,6 +856,8 @@ class Diffuser:
                                     cond_vals if use else None, cond_mask if use else None, g, plan.tables, noise,
                                     **plan.kwargs(g > 0, hist, seed=seed))
                 return out
+            if plan.perturb is not None:
+                raise ValueError("pag_scale needs a dmx network on the GPU: only the native step can perturb attention")
             t = pos if rule == "ddpm" else plan.sched[0][pos - 1]
             if not mirror:
                 eu, ec, g = self._eps(model, x, t, y, null_label, cond_vals, cond_mask, g, plan.rescale, compose)
@@ -1063,6 +1144,8 @@ class Diffuser:
         base="null",
         also=None,
         geom_scale=0.0,
+        pag_scale=0.0,
+        pag_blocks=("sa3",),
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -1113,7 +1196,17 @@ class Diffuser:
         step then costs the CFG forward plus a taped forward and a data-only backward of B rows.  It
         needs a scalar guidance_scale > 0 and `cond`, and takes no guidance_interval, guidance_rescale,
         base or also; a row whose mask is all zero is not guided.  0 (the default) is the call without
-        the keyword; the draw order is unchanged."""
+        the keyword; the draw order is unchanged.
+
+        pag_scale = s (a float or B finite floats, >= 0; a conditional dmx network), with any sampler,
+        init_latent, mask, base and also: perturbed-attention guidance (Ahn et al. 2024).  Every step runs one
+        more branch — the call's own condition again, with the self-attention of the blocks in pag_blocks
+        (names from "sa1".."sa6"; "sa1".."sa3" the down path, "sa4".."sa6" the up path) replaced by the
+        identity — and pushes the prediction away from it: eps = e_u + g (e_c - e_u) + s (e_c - e_p).
+        It acts where CFG has nothing to act on: with guidance_scale 0 the step is e_c + s (e_c - e_p),
+        at the cost of a CFG step.  At most two specs in `also` with it; no guidance_interval,
+        guidance_rescale or geom_scale.  0 (the default) is the call without the keywords; the draw
+        order is unchanged."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         composed = (not (isinstance(base, str) and base == "null")) or bool(also) or self._per_sample(guidance_scale)
         interval, phi = self._guidance_args(None if composed else guidance_scale,
@@ -1131,6 +1224,10 @@ class Diffuser:
         vals, msk = self._build_cond(y_list, cond, cond_mask, key_order, class_keys, device)
         compose = self._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval,
                                      guidance_rescale, null_label, key_order, class_keys, device)
+        pag = self._pag_args(pag_scale, pag_blocks, y_list, vals, msk, guidance_scale, compose, model,
+                             guidance_interval, guidance_rescale, geom_scale, null_label, device)
+        if pag is not None:
+            compose = pag[0]
 
         known = self._known_inputs(init_latent, mask, strength, B, z_shape)
         if known is not None:
@@ -1145,7 +1242,8 @@ class Diffuser:
         x = self._randn((B, C, Hlat, Wlat), device)
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
                                 known=known[:3] if known is not None else None, interval=interval, rescale=phi,
-                                compose=compose, **({} if geom is None else dict(geom=geom)))
+                                compose=compose, **({} if geom is None else dict(geom=geom)),
+                                **({} if pag is None else dict(perturb=pag[1])))
         if vae is None:
             return x
         if torch.cuda.is_available():
@@ -1153,7 +1251,7 @@ class Diffuser:
         return self._decode(vae, x, to_pil)
 
     def _plan(self, x, mode, guidance_scale, known=None, interval=None, rescale=0.0, compose=None,
-              rows=None, geom=None) -> _SamplerPlan:
+              rows=None, geom=None, perturb=None) -> _SamplerPlan:
         """The plan of a sampling call whose x_T draw is x, on x's device.
         mode: _sampler_mode's result.  interval, rescale: _guidance_args' (t_lo, t_hi) or None and phi.
         compose: _compose_args' tables or None; a composed plan has no scale, interval or rescale.
@@ -1164,13 +1262,19 @@ class Diffuser:
         rows = (s, e): a shard — x holds the rows [s, e) of the global draw, and the plan takes those
         rows of z0 and the mask and the columns [:, s:e] of the compose tables.
         geom: _geom_args' scale row or None; the plan carries its rows and the sig table of the rule
-        (geom_sig for ddpm, the schedule's k_e otherwise), converted once: a loop's graphs hold their pointers."""
+        (geom_sig for ddpm, the schedule's k_e otherwise), converted once: a loop's graphs hold their pointers.
+        perturb: _pag_args' (blocks, branches) or None, for the compose tables that came with it; the
+        pair does not depend on the shard."""
         dev = x.device
         rule = "ddpm" if mode is None else mode[0]
         tau = self._mode_timesteps(mode)
         cut = slice(None) if rows is None else slice(*rows)
         plan = _SamplerPlan(rule, start=len(tau), draws=rule == "ddpm" or (rule == "ddim" and mode[2] > 0),
                             rows=rows, x_start=x)
+        if perturb is not None:
+            if compose is None:
+                raise ValueError("perturb belongs to the compose tables of _pag_args")
+            plan.perturb = (int(perturb[0]), int(perturb[1]))
         if compose is not None:  # converted once: a loop's graphs hold their pointers
             plan.compose = tuple(c[:, cut].to(dev).contiguous() for c in compose)
         else:
@@ -1220,13 +1324,13 @@ class Diffuser:
         return run
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
-                       interval=None, rescale=0.0, compose=None, geom=None):
+                       interval=None, rescale=0.0, compose=None, geom=None, perturb=None):
         """The T loop (diff.py:328-344) over the call's plan (_plan), range-guarded in chunks
         (_guarded_loop): the counter walks timesteps, or the positions of a strided schedule, down
         from plan.start, and a replayed chunk restarts from the x and the solver history it started
         with.  A dmx network with guidance (or a composed call) in device-noise mode runs whole chunks
         on the device (_device_chunks); every other case steps on the host (_step)."""
-        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom)
+        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom, perturb=perturb)
         x = plan.x_start
         hist = plan.new_hist(x)
         guard = self._guard_target(model, x)

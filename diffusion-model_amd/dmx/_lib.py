@@ -80,6 +80,12 @@ class Compose(ctypes.Structure):
                 ("weight", ctypes.c_void_p)]
 
 
+class Perturb(ctypes.Structure):
+    """dmx_perturb (include/dmx.h): the perturbed blocks (bit i: sa(i+1)) and branches (bit k: branch k) of a
+    composed step with perturbed-attention guidance."""
+    _fields_ = [("blocks", ctypes.c_uint32), ("branches", ctypes.c_uint32)]
+
+
 class GeomGuide(ctypes.Structure):
     """dmx_geom_guide (include/dmx.h): per-sample scales and the per-position sqrt(1 - ab) table of geometry guidance."""
     _fields_ = [("scale", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("S", ctypes.c_int)]
@@ -159,6 +165,14 @@ SIGNATURES = [
                                       ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
                                       ctypes.POINTER(Compose), _I, _I, _P]),
     ("dmx_compose_eps", _I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("dmx_step_perturbed", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                                ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance), ctypes.POINTER(Compose),
+                                ctypes.POINTER(Perturb), _P]),
+    ("dmx_sample_loop_perturbed", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched),
+                                       ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
+                                       ctypes.POINTER(Compose), ctypes.POINTER(Perturb), _I, _I, _P]),
+    ("dmx_unet_forward_perturbed", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_uint32, _I, _I, _P]),
+    ("dmx_attn_identity", _I, [_P, _P, _I, _I, _I, _P]),
     ("dmx_step_geom", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
                            ctypes.POINTER(KnownSched), ctypes.POINTER(GeomGuide), _P]),
     ("dmx_sample_loop_geom", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),

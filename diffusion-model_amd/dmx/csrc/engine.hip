@@ -1561,6 +1561,33 @@ static void attention_core(Run& R, const float* qkv, float* out, int N, int L, i
   HIPCHK(hipGetLastError());
 }
 
+// Perturbed-attention guidance (include/dmx.h dmx_perturb; perturb.h): in the blocks of `blocks` (bit i
+// stands for sa(i+1)) the samples [row0, row1) of the forward take the identity core — their attention
+// output is their own V — instead of the attention core.  blocks == 0: nothing is perturbed.
+struct Perturb {
+  uint32_t blocks = 0;
+  int row0 = 0, row1 = 0;
+};
+
+// The core of one attention block over N samples; pt non-null: a perturbed block.  attention_core
+// picks its kernel from L, C and the precision alone and each of its blocks works on one sample, so
+// the samples outside [row0, row1) get from a launch over their sub-range the bits a launch over all
+// N gives them.  The profiling records of the sub-range launches carry the sub-range's FLOPs.
+static void attention_rows(Run& R, const float* qkv, float* ao, int N, int L, int C, const Perturb* pt) {
+  if (pt == nullptr) return attention_core(R, qkv, ao, N, L, C);
+  if (R.plan) return;
+  const int r0 = pt->row0, r1 = pt->row1;
+  if (r0 < 0 || r0 >= r1 || r1 > N) throw Error(DMX_E_INTERNAL, "perturbed rows outside the batch");
+  if (C != 64 && C != 128 && C != 256) throw Error(DMX_E_INTERNAL, "identity attention: unsupported C");
+  const size_t tok = (size_t)L * C;
+  if (r0 > 0) attention_core(R, qkv, ao, r0, L, C);
+  R.begin("attn_identity_kernel", 0.0, 8.0 * (double)(r1 - r0) * (double)tok);
+  launch_attn_identity(qkv + (size_t)r0 * tok * 3, ao + (size_t)r0 * tok, (int64_t)(r1 - r0) * L, C, R.st);
+  R.end();
+  HIPCHK(hipGetLastError());
+  if (r1 < N) attention_core(R, qkv + (size_t)r1 * tok * 3, ao + (size_t)r1 * tok, N - r1, L, C);
+}
+
 // Whether the C = 256 QKV runs tok_ln_qkv_w_kernel (8-wave blocks, 384 columns, the LayerNorm of a
 // token tile twice instead of twelve times) instead of the 4-wave 64-column tok_ln_qkv_kernel: where
 // its grid (two column halves per 64-token tile) still fills the chip — sa2 (8192 tokens: 35 vs 41 us
@@ -1572,7 +1599,7 @@ static bool tok_qkv_wide(const Run& R, int N, int L) { return cdiv(dec_n(R, N) *
 static TokW tokw(const ConvW& c) { return TokW{c.Bh, c.Bl, c.bias, c.inv_scale, c.kpad, c.Fh, c.Fl}; }
 
 // Fused token kernels (tokmlp.h) for the split-precision modes: TA -> attention core -> TB.
-static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, int H, int W) {
+static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt) {
   const int C = a.c, M = N * H * W, L = H * W;
   float* qkv = R.ws.get<float>((size_t)M * 3 * C);
   float* ao = R.ws.get<float>((size_t)M * C);
@@ -1614,7 +1641,7 @@ static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, in
     R.end();
     HIPCHK(hipGetLastError());
   }
-  attention_core(R, qkv, ao, N, L, C);
+  attention_rows(R, qkv, ao, N, L, C, pt);
   if (!R.plan) {
     TokParams tp{};
     tp.x = x;
@@ -1648,12 +1675,13 @@ static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, in
   return out;
 }
 
-// AttenionBlock (models/unet_cond.py:32-52) on NHWC == (N, L, C) tokens.
-static float* attn_block(Run& R, const AttnW& a, const float* x, int N, int H, int W) {
+// AttenionBlock (models/unet_cond.py:32-52) on NHWC == (N, L, C) tokens.  pt: the block is perturbed
+// (attention_rows); the QKV and the out / FF launches run over all N rows either way.
+static float* attn_block(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt = nullptr) {
   const int C = a.c, M = N * H * W, L = H * W;
   if (R.m->prec >= 1 && (C == 64 || C == 128 || C == 256) && a.qkv.kpad == C &&
       a.o.kpad == C && a.f1.kpad == C && a.f2.kpad == C)
-    return attn_block_fused(R, a, x, N, H, W);
+    return attn_block_fused(R, a, x, N, H, W, pt);
   float* xl = R.ws.get<float>((size_t)M * C);
   float* qkv = R.ws.get<float>((size_t)M * 3 * C);
   float* ao = R.ws.get<float>((size_t)M * C);
@@ -1663,7 +1691,7 @@ static float* attn_block(Run& R, const AttnW& a, const float* x, int N, int H, i
   float* out = R.ws.get<float>((size_t)M * C);
   layernorm(R, x, xl, a.l1w, a.l1b, M, C);
   gemm(R, plain_src(xl, C), SRC_PLAIN, N, H, W, a.qkv, EPI_BIAS, qkv, nullptr, nullptr, 1);
-  attention_core(R, qkv, ao, N, L, C);
+  attention_rows(R, qkv, ao, N, L, C, pt);
   gemm(R, plain_src(ao, C), SRC_PLAIN, N, H, W, a.o, EPI_BIAS_RES, av, xl, nullptr, 1);
   layernorm(R, av, al, a.l2w, a.l2b, M, C);
   gemm(R, plain_src(al, C), SRC_PLAIN, N, H, W, a.f1, EPI_BIAS_GELU, f, nullptr, nullptr, 1);
@@ -1687,11 +1715,13 @@ struct FwdIn {
                               // already in the workspace (t-independent, same address every step)
   const int64_t* t_map = nullptr;  // strided sampling: t holds positions in [1, n_pos] and the
   int n_pos = 0;                   // timestep is t_map[position - 1] (null: t holds timesteps)
+  Perturb perturb;                 // perturbed-attention guidance: blocks and rows (default: none)
 };
 
 // UnetCond trunk (models/unet_cond_geom.py:52-76): returns the (N,H,W,64) feature
 static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
   dmx_model* m = R.m;
+  auto perturbed = [&](int i) { return (in.perturb.blocks >> i & 1u) != 0 ? &in.perturb : nullptr; };
   // embedding
   float* emb = R.ws.get<float>((size_t)N * m->hsum);
   const bool has_cond = m->kind != DMX_UNET && in.vals != nullptr;
@@ -1792,7 +1822,7 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     ch = nh;
     cw = nw;
     R.layer = "sa" + std::to_string(i + 1);
-    cur = attn_block(R, m->sa[i], h1, N, ch, cw);
+    cur = attn_block(R, m->sa[i], h1, N, ch, cw, perturbed(i));
   }
   // bottleneck
   const _Float16 *cur_h = nullptr, *cur_l = nullptr;  // planes of `cur` (between bottleneck blocks)
@@ -1849,7 +1879,7 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     cw = sw[si];
     cc = m->up[i].cout;
     R.layer = "sa" + std::to_string(4 + i);
-    cur = attn_block(R, m->sa[3 + i], h1, N, ch, cw);
+    cur = attn_block(R, m->sa[3 + i], h1, N, ch, cw, perturbed(3 + i));
   }
   return const_cast<float*>(cur);
 }
@@ -2421,8 +2451,10 @@ int dmx_debug_tap(dmx_model* m, int i, char* name_out, int cap, int64_t* count_o
   });
 }
 
-int dmx_unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
-                     const float* mask, float* eps, float* geom, int n, int h, int w, void* stream) {
+// dmx_unet_forward, with the rows and blocks of `pt` perturbed (none by default)
+static int unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
+                        const float* mask, float* eps, float* geom, int n, int h, int w, const Perturb& pt,
+                        void* stream) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
     check_shapes(m, n, h, w);
@@ -2435,6 +2467,7 @@ int dmx_unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64
     m->taps.clear();
     run_planned(m, st, [&](Run& R) {
       FwdIn in{x, n, t, 1, y, 0, 0, vals, mask, n};
+      in.perturb = pt;
       float* feat = unet_trunk(R, in, n, h, w);
       if (R.plan) return;
       dim3 grid(cdiv(h * w, 256), n);
@@ -2447,6 +2480,21 @@ int dmx_unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64
       }
     });
   });
+}
+
+int dmx_unet_forward(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
+                     const float* mask, float* eps, float* geom, int n, int h, int w, void* stream) {
+  return unet_forward(m, x, t, y, vals, mask, eps, geom, n, h, w, Perturb{}, stream);
+}
+
+int dmx_unet_forward_perturbed(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
+                               const float* mask, float* eps, float* geom, int n, int h, int w, uint32_t blocks,
+                               int row0, int row1, void* stream) {
+  if (!(blocks >= 1u && blocks < 64u))
+    return guarded([&] { REQUIRE(false, "perturb blocks must lie in [1, 63] (bit i: sa(i+1))"); });
+  if (!(0 <= row0 && row0 < row1 && row1 <= n))
+    return guarded([&] { REQUIRE(false, "perturbed rows must satisfy 0 <= row0 < row1 <= n"); });
+  return unet_forward(m, x, t, y, vals, mask, eps, geom, n, h, w, Perturb{blocks, row0, row1}, stream);
 }
 
 // The step and loop entries: each fills a StepMode (step_mode.h) for sample_step / sample_loop
@@ -2483,11 +2531,19 @@ int dmx_step_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* 
   return dmx_step_composed(m, a, ddim, dpm, known, guidance, nullptr, stream);
 }
 
-// The general entries: every part optional.
 int dmx_step_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
                       const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_compose* compose,
                       void* stream) {
-  return guarded([&] { sample_step(m, a, StepMode{ddim, dpm, known, guidance, compose}, (hipStream_t)stream); });
+  return dmx_step_perturbed(m, a, ddim, dpm, known, guidance, compose, nullptr, stream);
+}
+
+// The general entries: every part optional.
+int dmx_step_perturbed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                       const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_compose* compose,
+                       const dmx_perturb* perturb, void* stream) {
+  return guarded([&] {
+    sample_step(m, a, StepMode{ddim, dpm, known, guidance, compose, nullptr, perturb}, (hipStream_t)stream);
+  });
 }
 
 int dmx_sample_loop(dmx_model* m, const dmx_step_args* a, int steps, int use_graph, void* stream) {
@@ -2529,8 +2585,26 @@ int dmx_sample_loop_guided(dmx_model* m, const dmx_step_args* a, const dmx_ddim_
 int dmx_sample_loop_composed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
                              const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
                              const dmx_compose* compose, int steps, int use_graph, void* stream) {
+  return dmx_sample_loop_perturbed(m, a, ddim, dpm, known, guidance, compose, nullptr, steps, use_graph, stream);
+}
+
+int dmx_sample_loop_perturbed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                              const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                              const dmx_compose* compose, const dmx_perturb* perturb, int steps, int use_graph,
+                              void* stream) {
   return guarded([&] {
-    sample_loop(m, a, StepMode{ddim, dpm, known, guidance, compose}, steps, use_graph, (hipStream_t)stream);
+    sample_loop(m, a, StepMode{ddim, dpm, known, guidance, compose, nullptr, perturb}, steps, use_graph,
+                (hipStream_t)stream);
+  });
+}
+
+int dmx_attn_identity(const float* qkv, float* out, int n, int L, int C, void* stream) {
+  return guarded([&] {
+    REQUIRE(qkv && out, "null tensor");
+    REQUIRE(n >= 1 && L >= 1 && (C == 64 || C == 128 || C == 256), "identity attention: n, L >= 1, C in {64, 128, 256}");
+    REQUIRE((double)n * (double)L * (double)C < 2199023255552.0, "too many elements");
+    launch_attn_identity(qkv, out, (int64_t)n * L, C, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
   });
 }
 

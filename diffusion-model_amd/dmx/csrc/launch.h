@@ -86,6 +86,9 @@ void launch_compose_tail4(const StepTailParams& p, const ComposeParams& q, bool 
                           hipStream_t st);
 // the mix alone: e [(K+1)][n][chw], weight [K][n] -> eps [n][chw]; n * chw < 2^39
 void launch_compose_eps(const float* e, const float* weight, int K, int n, int64_t chw, float* eps, hipStream_t st);
+// Perturbed-attention guidance (perturb.h), k_perturb.hip.  The identity-attention core:
+// out [M][C] = the V third of qkv [M][3C], an exact fp32 copy; C in {64, 128, 256}; M * C / 1024 < 2^31
+void launch_attn_identity(const float* qkv, float* out, int64_t M, int C, hipStream_t st);
 // Geometry guidance (geom.h), k_geom.hip.
 // loss [n] (or null) and seed [n][gd] = dL_n / dgeom of the masked regression loss on geom against vals / mask [n][gd]
 void launch_geom_seed(const float* geom, const float* vals, const float* mask, int n, int gd, float* loss, float* seed,

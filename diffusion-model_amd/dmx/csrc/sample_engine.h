@@ -85,7 +85,9 @@ struct GraphStep {
 // known-region blend follows the tail as a launch of its own, on a.x_out in place, at the position
 // the tail read.  A composed step (mode.comp) runs K + 1 branch-major rows through the trunk and the
 // composed tail; with Co < 4 the head, the mix and the update are three launches whose predictions
-// come from the arena.  A geometry-guided step (mode.geom; geom.h) runs, after the trunk, the taped
+// come from the arena.  With mode.perturb the trailing branches of the composition run the identity
+// core in the chosen attention blocks (engine.hip attention_rows); the arena and the tail are the
+// composed step's.  A geometry-guided step (mode.geom; geom.h) runs, after the trunk, the taped
 // training forward of the B conditional rows, the loss seed and the data-only backward
 // (train_engine.h) in the same arena — nothing is allocated outside the plan, so the step captures
 // like any other — then materialises the CFG eps as the rescaled step does, mixes the input
@@ -105,6 +107,10 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
     in.vals = comp->vals;
     in.mask = comp->mask;
     in.cond_rows = N;
+  }
+  if (mode.perturb != nullptr) {  // the trailing branches k0..K: the rows [k0 n, (K + 1) n) of the forward
+    const int k0 = __builtin_ctz(mode.perturb->branches);
+    in.perturb = Perturb{mode.perturb->blocks, k0 * a.n, N};
   }
   in.t_next = gs.t_next;
   in.cond_cached = gs.cond_cached;
@@ -302,6 +308,17 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
     REQUIRE(a->n <= 65535, "geometry-guided steps take at most 65535 samples");
     const void* xo = a->x_out;
     REQUIRE(g.scale != xo && g.sig != xo, "geometry guidance tables must not alias x_out");
+  }
+  if (mode.perturb != nullptr) {
+    const dmx_perturb& p = *mode.perturb;
+    REQUIRE(mode.comp != nullptr, "perturbed-attention guidance needs a composition");
+    REQUIRE(p.blocks >= 1u && p.blocks < 64u, "perturb blocks must lie in [1, 63] (bit i: sa(i+1))");
+    // a non-empty run of set bits that ends at bit K: branches + its lowest set bit == 2^(K+1)
+    REQUIRE(p.branches != 0u && (p.branches >> mode.comp->K) == 1u &&
+                ((p.branches + (p.branches & (0u - p.branches))) == (1u << (mode.comp->K + 1))),
+            "perturb branches must be a non-empty trailing run of the branches 0..K");
+    REQUIRE(mode.geom == nullptr, "perturbed-attention guidance takes no geometry guidance");
+    REQUIRE(mode.rescale() == 0.f, "perturbed-attention guidance takes no guidance rescale");
   }
   REQUIRE(mode.ddim == nullptr || mode.dpm == nullptr, "at most one of the DDIM and DPM schedules");
   if (mode.ddim != nullptr) check_sched(mode.ddim);

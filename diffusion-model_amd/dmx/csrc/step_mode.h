@@ -19,6 +19,8 @@ struct StepMode {
   const dmx_compose* comp = nullptr;       // composed guidance: K + 1 branches; a.y / vals / mask / guidance /
                                            // null_label are not read
   const dmx_geom_guide* geom = nullptr;    // geometry guidance: the GeomHead's input gradient joins the CFG eps
+  const dmx_perturb* perturb = nullptr;    // perturbed-attention guidance: identity attention in the trailing
+                                           // branches of comp
 
   Rule rule() const { return dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM; }
   // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
@@ -38,6 +40,7 @@ struct GraphKey {
   dmx_guidance gd;       // rescaled loops: phi (all zero otherwise, rescale == 0 included)
   dmx_compose comp;      // composed loops: K and the four tables (all zero otherwise)
   dmx_geom_guide geom;   // geometry-guided loops: the two tables and S (all zero otherwise)
+  dmx_perturb perturb;   // perturbed loops: the block and branch bits (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
@@ -46,7 +49,8 @@ struct GraphKey {
 // optional structs enter member by member, so their padding stays zero.  A validated schedule has
 // S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart;
 // a validated composition has K >= 1, which keeps composed keys from plain ones; validated geometry
-// guidance has non-null tables and S >= 1, which keeps its keys from plain ones.
+// guidance has non-null tables and S >= 1, which keeps its keys from plain ones; a validated
+// perturbation has blocks >= 1, which keeps perturbed keys from composed ones.
 inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen) {
   GraphKey key;
   std::memset(&key, 0, sizeof(key));
@@ -98,6 +102,10 @@ inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int
     key.geom.scale = mode.geom->scale;
     key.geom.sig = mode.geom->sig;
     key.geom.S = mode.geom->S;
+  }
+  if (mode.perturb != nullptr) {  // the identity launches and the sub-range cores are in the graphs too
+    key.perturb.blocks = mode.perturb->blocks;
+    key.perturb.branches = mode.perturb->branches;
   }
   key.table_gen = table_gen;
   return key;

@@ -172,7 +172,8 @@ class ShardedCondSampler:
                steps: Optional[int] = None, eta: float = 0.0, spacing: Optional[str] = None,
                init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                strength: Optional[float] = None, guidance_interval=None,
-               guidance_rescale: float = 0.0, base="null", also=None, geom_scale=0.0) -> Optional[torch.Tensor]:
+               guidance_rescale: float = 0.0, base="null", also=None, geom_scale=0.0, pag_scale=0.0,
+               pag_blocks=("sa3",)) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -212,7 +213,12 @@ class ShardedCondSampler:
 
         geom_scale as in Diffuser.sample_latent_cond (geometry guidance), a float or B floats for the
         global batch: every rank takes its rows of the scale table; the loss and its gradient are per
-        sample, hence shard-local (no collective)."""
+        sample, hence shard-local (no collective).
+
+        pag_scale / pag_blocks as in Diffuser.sample_latent_cond (perturbed-attention guidance), the scale
+        a float or B floats for the global batch: the perturbed branch is one more row of the branch
+        tables, sharded by columns with them; which blocks and branches are perturbed does not depend
+        on the shard."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
@@ -231,6 +237,10 @@ class ShardedCondSampler:
         vals, msk = d._build_cond(y_list, cond, cond_mask, None, None, dev)
         compose = d._compose_args(y_list, vals, msk, guidance_scale, base, also, guidance_interval, guidance_rescale,
                                   null_label, None, None, dev)
+        pag = d._pag_args(pag_scale, pag_blocks, y_list, vals, msk, guidance_scale, compose, self.model,
+                          guidance_interval, guidance_rescale, geom_scale, null_label, dev)
+        if pag is not None:
+            compose = pag[0]
         s, e = shard_range(B, ws, rank)
         y = torch.tensor(y_list[s:e], device=dev, dtype=torch.long)
         v, m = vals[s:e].float().contiguous(), msk[s:e].float().contiguous()
@@ -247,7 +257,8 @@ class ShardedCondSampler:
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
         # the single-process sampler's plan for this shard's rows; x is its rows of e0
         plan = d._plan(x, mode, guidance_scale, known[:3] if known is not None else None, interval, phi, compose,
-                       rows=(s, e), **({} if geom is None else dict(geom=geom)))
+                       rows=(s, e), **({} if geom is None else dict(geom=geom)),
+                       **({} if pag is None else dict(perturb=pag[1])))
         x = plan.x_start
         hist = plan.new_hist(x)  # shard-local
         if d.noise_source == "device":

@@ -240,7 +240,10 @@ class NativeModel:
         return int(self.lib.dmx_model_graph_captures(self.handle))
 
     # ---- U-Net ---------------------------------------------------------------------------
-    def forward(self, x, t, y=None, vals=None, mask=None, want_geom=False):
+    def forward(self, x, t, y=None, vals=None, mask=None, want_geom=False, perturb=None):
+        """The network's forward -> (eps, geom or None).  perturb = (blocks, row0, row1): the samples
+        [row0, row1) run with identity attention in the blocks of `blocks` (bit i: sa(i+1); include/dmx.h
+        dmx_unet_forward_perturbed); the other samples keep the bits of the plain forward."""
         n, c, h, w = x.shape
         self.ctx.ensure_time_table(int(t.max().item()) if t.numel() else 1)
         x = x.contiguous().float()
@@ -253,8 +256,17 @@ class NativeModel:
         eps = torch.empty_like(x)
         geom = torch.empty((n, self.geom_dim), device=x.device, dtype=torch.float32) if want_geom else None
         with torch.cuda.device(x.device):
-            check(self.lib.dmx_unet_forward(self.handle, _ptr(x), _ptr(t), _ptr(y), _ptr(vals), _ptr(mask),
-                                            _ptr(eps), _ptr(geom), n, h, w, ctypes.c_void_p(_stream(x.device))))
+            if perturb is not None:
+                blocks, row0, row1 = (int(v) for v in perturb)
+                if not 1 <= blocks < 64 or not 0 <= row0 < row1 <= n:
+                    raise ValueError(f"perturb must be (blocks in [1, 63], row0, row1) with 0 <= row0 < row1 <= {n} "
+                                     f"(got {tuple(perturb)!r})")
+                check(self.lib.dmx_unet_forward_perturbed(self.handle, _ptr(x), _ptr(t), _ptr(y), _ptr(vals),
+                                                          _ptr(mask), _ptr(eps), _ptr(geom), n, h, w, blocks, row0,
+                                                          row1, ctypes.c_void_p(_stream(x.device))))
+            else:
+                check(self.lib.dmx_unet_forward(self.handle, _ptr(x), _ptr(t), _ptr(y), _ptr(vals), _ptr(mask),
+                                                _ptr(eps), _ptr(geom), n, h, w, ctypes.c_void_p(_stream(x.device))))
         return eps, geom
 
     def forward_taps(self, x, t, y=None, vals=None, mask=None):
@@ -399,8 +411,26 @@ class NativeModel:
                 raise ValueError(f"geom {nm} must be a contiguous 1-D fp32 tensor of {cnt} entries on {x.device}")
         return _lib.GeomGuide(scale.data_ptr(), sig.data_ptr(), S)
 
+    @staticmethod
+    def _perturb(perturb, compose, geom):
+        """The C view of perturb = (blocks, branches) (include/dmx.h dmx_perturb): bit i of blocks is sa(i+1),
+        bit k of branches is branch k of `compose`.  The library checks that the branches are the
+        composition's trailing ones."""
+        if compose is None:
+            raise ValueError("perturb needs compose (the perturbed branches are branches of a composition)")
+        if geom is not None:
+            raise ValueError("a perturbed step takes no geometry guidance")
+        if not isinstance(perturb, (tuple, list)) or len(perturb) != 2:
+            raise ValueError("perturb must be the pair (blocks, branches)")
+        blocks, branches = int(perturb[0]), int(perturb[1])
+        if not 1 <= blocks < 64 or not 1 <= branches < 2 ** (_lib.DMX_COMPOSE_MAX + 1):
+            raise ValueError(f"perturb blocks must lie in [1, 63] and branches in [1, {2 ** (_lib.DMX_COMPOSE_MAX + 1) - 1}] "
+                             f"(got {tuple(perturb)!r})")
+        return _lib.Perturb(blocks, branches)
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
-             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None):
+             sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
+             perturb=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -418,9 +448,13 @@ class NativeModel:
         geom = (scale (n,), sig (S,)) (include/dmx.h dmx_geom_guide; _geom): geometry guidance — a CFG step
         whose prediction gains (scale[n] sig[p-1]) dL_n/dx, L_n the GeomHead's masked regression loss
         against the step's own vals / mask.  UnetCondWithGeomHead only; no rescale, no compose.  The
-        step replaces the training tape.  None is the plain step, launched exactly as without the keyword."""
+        step replaces the training tape.  None is the plain step, launched exactly as without the keyword.
+        perturb = (blocks, branches) (include/dmx.h dmx_perturb; with compose only): perturbed-attention
+        guidance — the branches of bit mask `branches` (the composition's trailing ones) run with identity
+        attention in the blocks of bit mask `blocks` (bit i: sa(i+1)).  None is the composed step."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        pt = self._perturb(perturb, compose, geom) if perturb is not None else None
         gg = None
         if geom is not None:
             gg = self._geom(x_in, geom, sched, tables, rescale, compose, guidance, y, vals, mask)
@@ -437,6 +471,9 @@ class NativeModel:
             if gg is not None:
                 check(self.lib.dmx_step_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
                                              ctypes.c_void_p(_stream(x_in.device))))
+            elif pt is not None:
+                check(self.lib.dmx_step_perturbed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
+                                                  ctypes.byref(pt), ctypes.c_void_p(_stream(x_in.device))))
             elif compose is not None:
                 check(self.lib.dmx_step_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                  ctypes.c_void_p(_stream(x_in.device))))
@@ -464,7 +501,8 @@ class NativeModel:
         return self._side_stream
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
-                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None):
+                    use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
+                    perturb=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -481,8 +519,10 @@ class NativeModel:
         compose as in step(): every step of the loop is a composed step.  The captured graphs hold the
         pointers of the converted tables: pass contiguous int64 / fp32 device tensors to replay them.
         geom as in step(): every step of the loop is a geometry-guided step; the graphs hold the pointers
-        of its two tables."""
+        of its two tables.
+        perturb as in step(): every step of the loop is a perturbed composed step, with graphs of its own."""
         _check_state(x, "x")
+        pt = self._perturb(perturb, compose, geom) if perturb is not None else None
         gg = None
         if geom is not None:
             gg = self._geom(x, geom, sched, tables, rescale, compose, guidance, y, vals, mask)
@@ -511,6 +551,10 @@ class NativeModel:
             if gg is not None:
                 check(self.lib.dmx_sample_loop_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
                                                     int(steps), int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            elif pt is not None:
+                check(self.lib.dmx_sample_loop_perturbed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
+                                                         ctypes.byref(pt), int(steps), int(use_graph),
+                                                         ctypes.c_void_p(side.cuda_stream)))
             elif compose is not None:
                 check(self.lib.dmx_sample_loop_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                         int(steps), int(use_graph),
@@ -660,6 +704,22 @@ def compose_eps(e_list, weights):
     with torch.cuda.device(dev):
         check(lib.dmx_compose_eps(_ptr(e_c), _ptr(w_c), K, n, c, h, w, _ptr(eps), ctypes.c_void_p(_stream(dev))))
     return eps
+
+
+def attn_identity(qkv, C):
+    """The identity attention core alone (include/dmx.h dmx_attn_identity): qkv (n, L, 3C) = q | k | v on
+    the GPU -> (n, L, C) = v, an exact fp32 copy — what a perturbed block's core yields.  C in {64, 128, 256}."""
+    lib = _lib.load()
+    require_cuda(qkv, "qkv")
+    C = int(C)
+    q_c = qkv.to(dtype=torch.float32).contiguous()
+    if C not in (64, 128, 256) or q_c.dim() != 3 or q_c.shape[2] != 3 * C or min(q_c.shape) < 1:
+        raise ValueError(f"qkv must be (n, L, 3C) with C in (64, 128, 256) (got {tuple(qkv.shape)}, C={C})")
+    n, L, _ = q_c.shape
+    out = torch.empty((n, L, C), device=q_c.device, dtype=torch.float32)
+    with torch.cuda.device(q_c.device):
+        check(lib.dmx_attn_identity(_ptr(q_c), _ptr(out), n, L, C, ctypes.c_void_p(_stream(q_c.device))))
+    return out
 
 
 def geom_mix(eps, grad, scale, sig, pos):

@@ -377,8 +377,47 @@ int dmx_geom_mix(const float* eps, const float* grad, const float* scale, const 
 int dmx_geom_seed(const float* geom, const float* vals, const float* mask, int n, int gd, float* loss_out,
                   float* seed_out, void* stream);
 
+/* ---- Perturbed-attention guidance: an identity-attention branch in a composed step (Ahn et al. 2024,
+ * "Self-rectifying diffusion sampling with perturbed-attention guidance"; no reference counterpart).
+ * In a perturbed branch the self-attention of the chosen blocks is replaced by the identity: the
+ * softmax matrix is I, so a token's attention output is its own value vector (the V third of the
+ * in_proj output, bias included); out_proj, the residual and the feed-forward run as always.  Bit i
+ * of `blocks` stands for the block sa(i+1), i = 0..5 (sa1..sa3 the down path, sa4..sa6 the up path);
+ * it must be non-zero and below 64.  Bit k of `branches` marks branch k of the composition (0 = the
+ * base) as perturbed; the set bits must form a non-empty run k0..K, the trailing branches, so that
+ * the perturbed rows [k0*n, (K+1)*n) of the branch-major forward are one range.  The mix is the
+ * composition's, unchanged: with branch K the main condition's rows again, perturbed, weight -s on
+ * it and g + s on the main branch, eps = e_u + g (e_c - e_u) + s (e_c - e_p).  Rows of unperturbed
+ * branches keep the bits they have without the struct; a perturbed row skips the attention core of
+ * the chosen blocks (an exact fp32 copy in every precision mode). */
+typedef struct dmx_perturb {
+  uint32_t blocks;   /* bit i: sa(i+1); 1 .. 63 */
+  uint32_t branches; /* bit k: branch k; a trailing run of 0 .. K */
+} dmx_perturb;
+
+/* The general step and loop entries: every part of dmx_step_composed / dmx_sample_loop_composed
+ * (which forward here with perturb == NULL) plus perturb, which may be NULL.  With perturb given
+ * compose must be given, and there is no rescale (as in every composed step) and no geometry
+ * guidance.  A perturbed loop's graphs belong to its dmx_perturb as they belong to its
+ * composition: composed loops never replay them, nor the reverse. */
+int dmx_step_perturbed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                       const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_compose* compose,
+                       const dmx_perturb* perturb, void* stream);
+int dmx_sample_loop_perturbed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                              const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                              const dmx_compose* compose, const dmx_perturb* perturb, int steps, int use_graph,
+                              void* stream);
+/* dmx_unet_forward with the samples [row0, row1) perturbed in the blocks of `blocks` (0 <= row0 <
+ * row1 <= n, blocks in 1..63): the other samples' outputs have the bits dmx_unet_forward gives them. */
+int dmx_unet_forward_perturbed(dmx_model* m, const float* x, const int64_t* t, const int64_t* y, const float* vals,
+                               const float* mask, float* eps, float* geom, int n, int h, int w, uint32_t blocks,
+                               int row0, int row1, void* stream);
+/* The identity core alone: qkv (n,L,3C) = q | k | v -> out (n,L,C) = v, an exact fp32 copy.
+ * C in {64, 128, 256}; n, L >= 1; n*L*C < 2^41. */
+int dmx_attn_identity(const float* qkv, float* out, int n, int L, int C, void* stream);
+
 /* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
- * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / geometry guidance / time-table
+ * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / perturbation / geometry guidance / time-table
  * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
  * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
  * after another, inside the model's one workspace; whatever reallocates or invalidates it (a

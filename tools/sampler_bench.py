@@ -2,7 +2,7 @@
 one JSON line.
 
   python tools/sampler_bench.py [--rounds 5]
-      [--groups loops,known_loops,guidance_loops,composed_loops,end_to_end]
+      [--groups loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end]
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -25,6 +25,9 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    base, each as a ratio to the plain step, and what a user would run without the batched step — three
    B-sample forwards, compose_eps and the standalone update per step, eager — with the model's workspace
    after the K = 2 and the K = 4 loops.
+   Perturbed-attention guidance likewise (legs dpmpp_2m_a, composed_k2, pag_sa3, pag_all6, dpmpp_2m_b): three
+   ordinary branches against the same three with the last one's attention replaced by the identity in sa3
+   or in all six blocks, each PAG leg as a ratio to composed_k2 and to the plain step, with the workspace.
 2. Wall-clock images/s of Diffuser.sample_latent_cond with the VAE decode to uint8 images, for
    (ddpm, T = 1000), (ddim, S = 50, eta = 0) and (dpmpp_2m, S = 20, log-SNR spacing): the first call (it captures the graphs) and the best of
    the calls after it, separately.  The decode is warmed before either, so the first-call figures differ
@@ -286,6 +289,64 @@ def composed_legs(nm, d, dev, rounds):
     return out
 
 
+def pag_legs(nm, d, dev, rounds):
+    """The DPM-Solver++(2M) loop plain (CFG), composed with three ordinary branches (K = 2) and with
+    perturbed-attention guidance — the same three branches, the last one the main condition's rows with
+    identity attention in sa3 alone or in all six blocks: same schedule, buffers and method as loop_legs.
+    The plain leg runs first and last in every round: the spread of one loop measured twice."""
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
+    ys = torch.stack([torch.zeros_like(y), y, y]).contiguous()
+    comp = (ys, torch.stack([vals] * 3).contiguous(), torch.stack([mask] * 3).contiguous(),
+            torch.stack([torch.full((B,), 2 * GUIDANCE, device=dev), torch.full((B,), -GUIDANCE, device=dev)]))
+    modes = {"dpmpp_2m": None, "composed_k2": {}, "pag_sa3": dict(perturb=(0b000100, 0b100)),
+             "pag_all6": dict(perturb=(0b111111, 0b100))}
+
+    def leg(kind):
+        extra = modes[kind]
+        kw = dict(sched=sched, hist=hist, **(dict(compose=comp, **extra) if extra is not None else {}))
+        a = (None, 0, None, None, 0.0) if extra is not None else (y, 0, vals, mask, GUIDANCE)
+        x.copy_(x0)
+        t_dev.fill_(S)
+        nm.sample_loop(x, t_dev, *a, None, WARM, **kw)  # captures this loop's graphs once
+        x.copy_(x0)
+        t_dev.fill_(S)
+        torch.cuda.synchronize()
+        e_0, e_1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e_0.record()
+        nm.sample_loop(x, t_dev, *a, None, TIMED, **kw)
+        e_1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == S - TIMED and bool(torch.isfinite(x).all())
+        return e_0.elapsed_time(e_1) / TIMED
+
+    for kind in ("pag_all6", "pag_sa3", "composed_k2", "dpmpp_2m"):  # (the arena reaches its size first)
+        leg(kind)
+    ws = nm.workspace_bytes()
+    c0 = nm.graph_captures()
+    ms = {"dpmpp_2m_a": [], "composed_k2": [], "pag_sa3": [], "pag_all6": [], "dpmpp_2m_b": []}
+    for _ in range(rounds):
+        ms["dpmpp_2m_a"].append(leg("dpmpp_2m"))
+        ms["composed_k2"].append(leg("composed_k2"))
+        ms["pag_sa3"].append(leg("pag_sa3"))
+        ms["pag_all6"].append(leg("pag_all6"))
+        ms["dpmpp_2m_b"].append(leg("dpmpp_2m"))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    plain_mean = 0.5 * (med["dpmpp_2m_a"] + med["dpmpp_2m_b"])
+    out = {"ms_per_step_" + k: round(v, 4) for k, v in med.items()}
+    out.update({"dpmpp_2m_spread_ms": round(abs(med["dpmpp_2m_a"] - med["dpmpp_2m_b"]), 4),
+                "composed_k2_over_dpmpp_2m_mean": round(med["composed_k2"] / plain_mean, 4),
+                "pag_sa3_over_composed_k2": round(med["pag_sa3"] / med["composed_k2"], 4),
+                "pag_all6_over_composed_k2": round(med["pag_all6"] / med["composed_k2"], 4),
+                "pag_sa3_over_dpmpp_2m_mean": round(med["pag_sa3"] / plain_mean, 4),
+                "pag_all6_over_dpmpp_2m_mean": round(med["pag_all6"] / plain_mean, 4),
+                "workspace_bytes": ws, "graph_captures_in_rounds": nm.graph_captures() - c0,
+                "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}})
+    return out
+
+
 def end_to_end(model, dev):
     import diff
     from dmx import synth
@@ -327,7 +388,7 @@ def end_to_end(model, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--groups", default="loops,known_loops,guidance_loops,composed_loops,end_to_end")
+    ap.add_argument("--groups", default="loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end")
     args = ap.parse_args()
     groups = args.groups.split(",")
     if not torch.cuda.is_available():
@@ -343,7 +404,7 @@ def main():
     res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
            "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
     for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs),
-                     ("composed_loops", composed_legs)):
+                     ("composed_loops", composed_legs), ("pag_loops", pag_legs)):
         if name in groups:
             res[name] = fn(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
     if "end_to_end" in groups:

@@ -31,6 +31,7 @@ struct Inputs {
   dmx_guidance gd;
   dmx_compose comp;
   dmx_geom_guide geom;
+  dmx_perturb perturb;
   explicit Inputs(int fill = 0) {
     std::memset(&a, 0, sizeof(a));  // (the step args enter the key as the caller's bytes)
     a.x_in = a.x_out = mem;
@@ -84,12 +85,16 @@ struct Inputs {
     geom.scale = mem + 20;
     geom.sig = mem + 21;
     geom.S = 3;
+    std::memset(&perturb, fill, sizeof(perturb));
+    perturb.blocks = 4;    // sa3
+    perturb.branches = 4;  // branch 2 of K = 2
   }
   GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1,
-               bool use_comp = false, bool use_geom = false) const {
+               bool use_comp = false, bool use_geom = false, bool use_perturb = false) const {
     return make_graph_key(a, StepMode{use_ddim ? &ddim : nullptr, use_dpm ? &dpm : nullptr,
                                       use_known ? &known : nullptr, use_gd ? &gd : nullptr,
-                                      use_comp ? &comp : nullptr, use_geom ? &geom : nullptr}, table_gen);
+                                      use_comp ? &comp : nullptr, use_geom ? &geom : nullptr,
+                                      use_perturb ? &perturb : nullptr}, table_gen);
   }
 };
 
@@ -240,6 +245,37 @@ int main() {
     CHECK(Inputs(0xAA).key(ddim, dpm, true, false, 1, false, true) == Inputs(0).key(ddim, dpm, true, false, 1, false, true));
   }
   CHECK(StepMode{}.geom == nullptr);
+  // 11. perturbed-attention guidance: a perturbed key is not the composed key; both members count;
+  // all zero when absent
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    const GraphKey composed = Inputs().key(ddim, dpm, false, false, 1, true);
+    const GraphKey perturbed = Inputs().key(ddim, dpm, false, false, 1, true, false, true);
+    CHECK(!(perturbed == composed));
+    CHECK(!(perturbed == Inputs().key(ddim, dpm)));
+    auto moved_p = [&](auto&& edit) {
+      Inputs in;
+      edit(in);
+      return !(in.key(ddim, dpm, false, false, 1, true, false, true) == perturbed);
+    };
+    CHECK(moved_p([](Inputs& in) { in.perturb.blocks = 63; }));
+    CHECK(moved_p([](Inputs& in) { in.perturb.branches = 6; }));
+    CHECK(moved_p([](Inputs& in) { in.comp.weight = mem + 40; }));  // (the composition stays in)
+    CHECK(!moved_p([](Inputs& in) { in.a.guidance = 0.f; }));
+    // with a known region it is still its own key
+    CHECK(!(Inputs().key(ddim, dpm, true, false, 1, true, false, true) == Inputs().key(ddim, dpm, true, false, 1, true)));
+    // a key without it holds zeros there, whatever the other paths
+    const dmx_perturb zero{};
+    for (int kn = 0; kn < 2; ++kn)
+      for (int cp = 0; cp < 2; ++cp)
+        for (int gg = 0; gg < 2; ++gg) {
+          const GraphKey k = Inputs(0xAA).key(ddim, dpm, kn != 0, true, 1, cp != 0, gg != 0);
+          CHECK(std::memcmp(&k.perturb, &zero, sizeof(zero)) == 0);
+        }
+    CHECK(Inputs(0xAA).key(ddim, dpm, true, true, 1, true, false, true) ==
+          Inputs(0).key(ddim, dpm, true, true, 1, true, false, true));
+  }
+  CHECK(StepMode{}.perturb == nullptr);
   if (fails == 0) std::puts("step_mode_check: ok");
   return fails == 0 ? 0 : 1;
 }
