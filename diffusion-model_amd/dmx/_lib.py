@@ -91,6 +91,25 @@ class GeomGuide(ctypes.Structure):
     _fields_ = [("scale", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("S", ctypes.c_int)]
 
 
+DMX_OPTIM_CHUNK = 4096
+DMX_OPTIM_ALIGNED = 1
+DMX_OPTIM_DECOUPLED = 2
+
+
+class OptimChunk(ctypes.Structure):
+    """dmx_optim_chunk (include/dmx.h): one block's share of the optimizer's tensor list."""
+    _fields_ = [("offset", ctypes.c_int64), ("tensor", ctypes.c_int32), ("len", ctypes.c_int32)]
+
+
+class OptimTensor(ctypes.Structure):
+    """dmx_optim_tensor (include/dmx.h): one tensor's pointers and coefficients of one optimizer step."""
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("ema", ctypes.c_void_p),
+                ("step_size", ctypes.c_float), ("inv_sqrt_bc2", ctypes.c_float), ("lr_wd", ctypes.c_float),
+                ("eps", ctypes.c_float), ("wd", ctypes.c_float), ("omb1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("omb2", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -193,6 +212,11 @@ SIGNATURES = [
     ("dmx_step_profile", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(KernelRecord), _I, ctypes.POINTER(_I), _P]),
     ("dmx_attn_core_backward", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_diag_wino_stamps", _I, [_P, _I]),
+    ("dmx_optim_chunks", _I64, [_I, ctypes.POINTER(_I64), ctypes.POINTER(OptimChunk), _I64]),
+    ("dmx_optim_create", _I, [_I, _I, ctypes.POINTER(_I64), ctypes.POINTER(_P)]),
+    ("dmx_optim_destroy", _I, [_P]),
+    ("dmx_optim_set_step", _I, [_P, _P, _I, _P]),
+    ("dmx_optim_step", _I, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
 ]
 
 _lib = None

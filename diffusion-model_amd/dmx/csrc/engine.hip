@@ -2104,6 +2104,7 @@ static void vae_enc_body(Run& R, const float* x, const float* eps, float* z, flo
 #include "train_engine.h"  // (before the sampler: a geometry-guided step runs the taped forward and backward)
 #include "sample_engine.h"
 #include "vae_train_engine.h"
+#include "optim_engine.h"
 
 // ===========================================================================
 // C ABI
@@ -2821,6 +2822,68 @@ int dmx_vae_encode(dmx_model* m, const float* x, const float* eps, float* z, flo
                      kl + s, b, h, w);
       });
     }
+  });
+}
+
+int64_t dmx_optim_chunks(int n, const int64_t* numel, dmx_optim_chunk* out, int64_t cap) {
+  int64_t count = -1;
+  guarded([&] {
+    REQUIRE(n >= 0 && (numel != nullptr || n == 0), "bad tensor list");
+    for (int i = 0; i < n; ++i) REQUIRE(numel[i] >= 0, "negative element count");
+    const std::vector<dmx_optim_chunk> c = optim_chunks(n, numel);
+    for (int64_t i = 0; out != nullptr && i < (int64_t)c.size() && i < cap; ++i) out[i] = c[i];
+    count = (int64_t)c.size();
+  });
+  return count;
+}
+
+int dmx_optim_create(int device, int n, const int64_t* numel, dmx_optim** out) {
+  return guarded([&] {
+    REQUIRE(out != nullptr, "null out");
+    REQUIRE(n >= 0 && (numel != nullptr || n == 0), "bad tensor list");
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) {
+      REQUIRE(numel[i] >= 0, "negative element count");
+      total += (double)numel[i] / DMX_OPTIM_CHUNK + 1.0;
+    }
+    REQUIRE(total < 2147483647.0, "too many chunks for one launch");
+    auto* o = new dmx_optim();
+    try {
+      o->device = device;
+      o->numel.assign(numel, numel + n);
+      const std::vector<dmx_optim_chunk> c = optim_chunks(n, numel);
+      o->n_chunks = (int64_t)c.size();
+      HIPCHK(hipSetDevice(device));
+      HIPCHK(hipMalloc((void**)&o->chunks, std::max<size_t>(c.size(), 1) * sizeof(dmx_optim_chunk)));
+      HIPCHK(hipMalloc((void**)&o->partials, std::max<size_t>(c.size(), 1) * sizeof(double)));
+      if (!c.empty())
+        HIPCHK(hipMemcpy(o->chunks, c.data(), c.size() * sizeof(dmx_optim_chunk), hipMemcpyHostToDevice));
+      for (int k = 0; k < 2; ++k) o->ring.push_back(optim_new_slot((size_t)n));
+    } catch (...) {
+      optim_free(o);
+      throw;
+    }
+    *out = o;
+  });
+}
+
+int dmx_optim_destroy(dmx_optim* o) {
+  return guarded([&] {
+    if (o) optim_free(o);
+  });
+}
+
+int dmx_optim_set_step(dmx_optim* o, const dmx_optim_tensor* rows, int n, void* stream) {
+  return guarded([&] {
+    REQUIRE(o != nullptr, "null optimizer");
+    optim_set_step(o, rows, n, (hipStream_t)stream);
+  });
+}
+
+int dmx_optim_step(dmx_optim* o, float max_norm, float ema_d, float ema_omd, float* norm_out, void* stream) {
+  return guarded([&] {
+    REQUIRE(o != nullptr, "null optimizer");
+    optim_step(o, max_norm, ema_d, ema_omd, norm_out, (hipStream_t)stream);
   });
 }
 

@@ -98,5 +98,17 @@ void launch_geom_mix(const float* eps, const float* grad, const dmx_geom_guide& 
                      int n, int64_t chw, float* eps_out, int* range_flag, hipStream_t st);
 // dx (NCHW [n][Ci][H][W]) = the data gradient of the first 3x3 conv (weight [64][Ci][3][3]) from dr (NHWC, 64 channels)
 void launch_conv0_dgrad(const float* dr, const float* w, int Ci, int n, int H, int W, float* dx, hipStream_t st);
+// The optimizer step (optim.h), k_optim.hip: with max_norm > 0 and norm_out, the gradient's sum of squares per
+// chunk into partials [n_chunks] and norm / coef into norm_out [2]; then the Adam update, one block per chunk.
+// n_chunks < 2^31 (checked by dmx_optim_create); chunks, rows, partials and norm_out are device memory.
+struct OptimLaunch {
+  const dmx_optim_chunk* chunks;
+  int64_t n_chunks;
+  const dmx_optim_tensor* rows;
+  double* partials;
+  float max_norm, ema_d, ema_omd;
+  float* norm_out;
+};
+void launch_optim_step(const OptimLaunch& o, hipStream_t st);
 
 }  // namespace dmx

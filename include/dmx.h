@@ -531,6 +531,64 @@ int dmx_diag_wino_stamps(unsigned long long* host, int cap);
  * once a training step ran, the tape and the backward workspace. */
 int64_t dmx_model_workspace_bytes(const dmx_model* m);
 
+/* ---- optimizer step (replaces torch.optim.Adam's step of train_latent_cond.py:99,163 and train_vae.py):
+ * fused multi-tensor Adam / AdamW with global-norm gradient clipping and an exponential moving average
+ * of the weights, over any list of contiguous fp32 device tensors.  Independent of dmx_model.
+ *
+ * The tensor list is cut once into chunks of at most DMX_OPTIM_CHUNK elements (one kernel block per
+ * chunk).  Every step the caller passes one row per tensor: the pointers (gradient pointers change every
+ * step) and that tensor's own coefficients, all computed on the host in double and rounded once:
+ *   step_size = lr / (1 - beta1^step), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^step), lr_wd = lr * weight_decay,
+ *   wd = weight_decay (coupled decay; 0 in a decoupled row), omb1 = 1 - beta1, omb2 = 1 - beta2.
+ * A row with g == NULL is skipped (torch: .grad is None).  Per element, in fp32, torch/optim/adam.py's
+ * single-tensor rule:
+ *   g' = coef g (+ wd p);  decoupled: p -= lr_wd p;  m += (g' - m) omb1;  v = beta2 v + omb2 g' g';
+ *   p -= step_size m / (sqrt(v) inv_sqrt_bc2 + eps);  ema != NULL: ema = d ema + (1 - d) p.
+ * The gradient buffers are only read. */
+#define DMX_OPTIM_CHUNK 4096
+#define DMX_OPTIM_ALIGNED 1u   /* set by dmx_optim_set_step: p, g, m, v, ema all 16-byte aligned */
+#define DMX_OPTIM_DECOUPLED 2u /* AdamW: the decay multiplies p and does not enter the gradient */
+
+typedef struct dmx_optim dmx_optim;
+
+typedef struct dmx_optim_chunk {
+  int64_t offset; /* first element, a multiple of DMX_OPTIM_CHUNK */
+  int32_t tensor;
+  int32_t len;    /* 1 .. DMX_OPTIM_CHUNK */
+} dmx_optim_chunk;
+
+typedef struct dmx_optim_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  float* ema;
+  float step_size, inv_sqrt_bc2, lr_wd, eps;
+  float wd, omb1, beta2, omb2;
+  uint32_t flags;
+  uint32_t reserved;
+} dmx_optim_tensor;
+
+/* The chunk table of n tensors with numel[i] elements (host only, no device needed): writes up to cap
+ * chunks to out (NULL: count only) and returns the number of chunks, or -1. */
+int64_t dmx_optim_chunks(int n, const int64_t* numel, dmx_optim_chunk* out, int64_t cap);
+
+int dmx_optim_create(int device, int n, const int64_t* numel, dmx_optim** out);
+int dmx_optim_destroy(dmx_optim* o);
+
+/* The rows of the next step: copied into pinned host memory and uploaded with one asynchronous copy on
+ * `stream`.  The staging buffers form a ring; one is rewritten only after the step that read it has
+ * finished on the device (an event recorded behind that step), so the host waits only when it runs a
+ * whole ring of steps ahead of the device. */
+int dmx_optim_set_step(dmx_optim* o, const dmx_optim_tensor* rows, int n, void* stream);
+
+/* One step over the rows last set, enqueued on `stream`; no host synchronisation.  max_norm > 0 with
+ * norm_out (device, 2 floats) clips by the global gradient norm: norm_out[0] = the norm before clipping,
+ * norm_out[1] = coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_'s rule); sums in
+ * a fixed order, no atomics.  ema_d / ema_omd = d and 1 - d of the weight average (read where a row's ema
+ * is set).  A set of rows is consumed by one step. */
+int dmx_optim_step(dmx_optim* o, float max_norm, float ema_d, float ema_omd, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
