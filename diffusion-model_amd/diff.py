@@ -119,10 +119,11 @@ class _SamplerPlan:
     """What a sampling call's steps have in common, derived once (Diffuser._plan; the public one-step
     entries fill in the fields they need): the loops of the single-process and the sharded sampler
     walk the same plan, a shard's being the plan of its rows."""
-    rule: str                              # "ddpm", "ddim" or "dpm"
-    start: int = 0                         # the loop counter's first value: T, S, or p0 of a known-region loop
+    rule: str                              # "ddpm", "ddim", "dpm" or "invert"
+    start: int = 0                         # the loop counter's first value: T, S, p0 of a known-region or
+                                           # start-latent loop, or the row count N of an inversion
     tables: Optional[tuple] = None         # coef_tables (ddpm)
-    sched: Optional[tuple] = None          # ddim_tables / dpm_tables (the strided rules)
+    sched: Optional[tuple] = None          # ddim_tables / dpm_tables (the strided rules) / invert_tables
     draws: bool = True                     # do the steps draw noise (ddpm, or ddim with eta > 0)
     scale: float = 0.0                     # guidance scale of the guided steps (0 in a composed plan)
     rescale: float = 0.0                   # CFG rescale phi of the guided steps
@@ -147,7 +148,10 @@ class _SamplerPlan:
         return self.scale if guided else 0.0
 
     def new_hist(self, x):
-        """The DPM solver's history buffer for x (the loop's first position does not read it)."""
+        """The DPM solver's history buffer for x (the loop's first position does not read it), or an
+        inversion's source latent: x's values, the loop starting with x == src."""
+        if self.rule == "invert":
+            return x.detach().to(torch.float32).contiguous().clone()
         return torch.empty_like(x, dtype=torch.float32) if self.rule == "dpm" else None
 
     def kwargs(self, guided: bool, hist=None, seed=None, use_graph=None) -> dict:
@@ -161,6 +165,9 @@ class _SamplerPlan:
             kw["use_graph"] = use_graph
             if self.rows is not None:
                 kw["sample_offset"] = self.rows[0]
+        if self.rule == "invert":  # (its seed is not read, and it takes none of the parts below)
+            kw["invert"] = (self.sched, hist)
+            return kw
         if self.sched is not None:
             kw["sched"] = self.sched
         if hist is not None:
@@ -321,6 +328,38 @@ class Diffuser:
                                              + tuple(v.float().contiguous().to(device) for v in tabs))
         return cache[key]
 
+    # ---- DDIM inversion: R + 1 rows per position p = 1..p0, stored in countdown order -------------
+    def invert_tables(self, steps: int, strength=None, refine: int = 0, device="cpu"):
+        """(t_eval, i_x, i_e, adv) of the DDIM inversion over the first p0 = _known_start(strength, steps)
+        positions of ddim_timesteps(steps), R = `refine` fixed-point refinements per position.  Position p
+        goes from s = tau_{p-1} (tau_0 = 0, alpha_bar 1) up to t = tau_p in the rows k = 0..R:
+        i_x = sqrt(ab[t]/ab[s]), i_e = sqrt(1-ab[t]) - i_x sqrt(1-ab[s]), so that y = i_x src + i_e eps;
+        t_eval = s for k = 0 (tau_1 at p = 1: there is no timestep 0) and t for k >= 1; adv = 1 on row R,
+        where y becomes the next position's src.  The N = p0 (R + 1) rows are laid out in countdown
+        order: the loop counter c runs N..1 and reads row c - 1, the forward index being j = N - c,
+        p = j // (R + 1) + 1, k = j % (R + 1).  int64 / fp32 / fp32 / int32; computed in float64 from the
+        fp32 alpha_bars and rounded to fp32 once; cached per (steps, p0, refine, device)."""
+        if isinstance(refine, bool) or not isinstance(refine, int) or refine < 0:
+            raise ValueError(f"refine must be an int >= 0 (got {refine!r})")
+        if isinstance(steps, bool) or not isinstance(steps, int):
+            raise ValueError(f"steps must be an int (got {steps!r})")
+        tau = self.ddim_timesteps(steps)
+        p0, R = self._known_start(strength, len(tau)), refine
+        key = (steps, p0, R, str(device))
+        cache = self.__dict__.setdefault("_invert_tables", {})
+        if key not in cache:
+            ab = torch.cat([torch.ones(1, dtype=torch.float64), self._host[1].double()])  # ab[0] := 1
+            p = torch.arange(p0 * (R + 1), dtype=torch.long) // (R + 1) + 1
+            k = torch.arange(p0 * (R + 1), dtype=torch.long) % (R + 1)
+            tau_t = torch.tensor([0] + tau, dtype=torch.long)
+            s, t = tau_t[p - 1], tau_t[p]
+            i_x = torch.sqrt(ab[t] / ab[s])
+            i_e = torch.sqrt(1 - ab[t]) - i_x * torch.sqrt(1 - ab[s])
+            t_eval = torch.where(k == 0, torch.clamp(s, min=tau[0]), t)
+            rows = (t_eval, i_x.float(), i_e.float(), (k == R).to(torch.int32))
+            cache[key] = tuple(v.flip(0).contiguous().to(device) for v in rows)
+        return cache[key]
+
     # ---- known-region sampling (img2img start, masked inpainting): one row per position, as above --
     def known_tables(self, tau, device="cpu"):
         """(q_a, q_e) of the known-region blend for the ascending timesteps `tau` of a loop (tau_p at
@@ -344,6 +383,8 @@ class Diffuser:
         """tau of a _sampler_mode result: the timesteps its loop's positions 1..S stand for."""
         if mode is None:
             return list(range(1, int(self.num_timesteps) + 1))
+        if mode[0] == "invert":  # (its rows walk the first p0 of these upwards)
+            return self.ddim_timesteps(mode[1])
         return self.ddim_timesteps(mode[1]) if mode[0] == "ddim" else self.dpm_timesteps(mode[1], mode[2])
 
     @staticmethod
@@ -823,7 +864,8 @@ class Diffuser:
         return self._step(model, x, t, plan, True, y, null_label, cond_vals, cond_mask)
 
     def _step(self, model, x, pos, plan, guided, y=None, null_label=0, cond_vals=None, cond_mask=None, hist=None):
-        """One step of plan.rule at `pos` ((B,): timesteps for ddpm, positions of plan.sched otherwise)
+        """One step of plan.rule at `pos` ((B,): timesteps for ddpm, positions of plan.sched otherwise —
+        countdown rows of an inversion, whose `hist` is its source latent)
         after the public entries' range checks — the samplers' loops build pos from a host-known
         counter and call this directly, so the host never waits on the device per step.
         guided: CFG (plan.scale > 0 and y given; rescaled for plan.rescale > 0), else one conditional
@@ -874,6 +916,8 @@ class Diffuser:
             out = _engine.ddpm_update(x, eu, ec, g, pos, plan.tables, noise, seed=seed or 0)
         elif rule == "ddim":
             out = _engine.ddim_update(x, eu, ec, g, pos, plan.sched, noise, seed=seed or 0)
+        elif rule == "invert":
+            out = _engine.invert_update(x, eu, ec, g, pos, plan.sched, hist)
         else:
             out = _engine.dpm_update(x, eu, ec, g, pos, plan.sched, hist)
         return self._blend(out, pos, plan.known)
@@ -1146,6 +1190,7 @@ class Diffuser:
         geom_scale=0.0,
         pag_scale=0.0,
         pag_blocks=("sa3",),
+        start_latent: Optional[torch.Tensor] = None,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -1206,7 +1251,16 @@ class Diffuser:
         It acts where CFG has nothing to act on: with guidance_scale 0 the step is e_c + s (e_c - e_p),
         at the cost of a CFG step.  At most two specs in `also` with it; no guidance_interval,
         guidance_rescale or geom_scale.  0 (the default) is the call without the keywords; the draw
-        order is unchanged."""
+        order is unchanged.
+
+        start_latent = x ((B,C,h,w), (1,C,h,w) or (C,h,w), broadcast to the batch), with sampler="ddim" or
+        "dpmpp_2m": the loop starts from x as it is — no noise is added to it — at position
+        p0 = min(S, max(1, floor(strength S + 0.5))) (S for strength None) and runs p0 steps.  With
+        x = invert_latent_cond(..., steps=S, strength=strength) and eta = 0 this is the way back from an
+        inverted latent, under the same or an edited condition.  It excludes init_latent and mask;
+        z_shape defaults to x's shape.  Draw order: no x_T draw is made and, with z_shape None, no encode
+        draw either; ddim with eta > 0 still draws once per step, everything else draws nothing.
+        Without the keyword the call is what it is today, `strength` without init_latent an error."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         composed = (not (isinstance(base, str) and base == "null")) or bool(also) or self._per_sample(guidance_scale)
         interval, phi = self._guidance_args(None if composed else guidance_scale,
@@ -1229,29 +1283,79 @@ class Diffuser:
         if pag is not None:
             compose = pag[0]
 
-        known = self._known_inputs(init_latent, mask, strength, B, z_shape)
-        if known is not None:
-            C, Hlat, Wlat = known[3]
-        elif z_shape is None:
-            if vae is None:
-                raise ValueError("z_shape 省略時は vae が必要です。")
-            C, Hlat, Wlat = self._latent_shape(vae, dummy_input_hw, device)
+        known, entry = None, {}
+        if start_latent is not None:
+            if init_latent is not None or mask is not None:
+                raise ValueError("`start_latent` excludes `init_latent` and `mask`")
+            if mode is None:
+                raise ValueError('`start_latent` needs sampler="ddim" or "dpmpp_2m"')
+            x, _, _, (C, Hlat, Wlat) = self._known_inputs(start_latent, None, strength, B, z_shape)
+            x = x.to(device)  # (the latent as it is: nothing is drawn for x_T)
+            entry = dict(start=self._known_start(strength, mode[1]))
         else:
-            C, Hlat, Wlat = z_shape
-
-        x = self._randn((B, C, Hlat, Wlat), device)
+            known = self._known_inputs(init_latent, mask, strength, B, z_shape)
+            if known is not None:
+                C, Hlat, Wlat = known[3]
+            elif z_shape is None:
+                if vae is None:
+                    raise ValueError("z_shape 省略時は vae が必要です。")
+                C, Hlat, Wlat = self._latent_shape(vae, dummy_input_hw, device)
+            else:
+                C, Hlat, Wlat = z_shape
+            x = self._randn((B, C, Hlat, Wlat), device)
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
                                 known=known[:3] if known is not None else None, interval=interval, rescale=phi,
                                 compose=compose, **({} if geom is None else dict(geom=geom)),
-                                **({} if pag is None else dict(perturb=pag[1])))
+                                **({} if pag is None else dict(perturb=pag[1])), **entry)
         if vae is None:
             return x
         if torch.cuda.is_available():
             torch.cuda.empty_cache()
         return self._decode(vae, x, to_pil)
 
+    def invert_latent_cond(self, model, init_latent, class_counts, steps, strength=None, refine=0,
+                           guidance_scale: float = 3.0, null_label: int = 0, cond=None, cond_mask=None,
+                           key_order: Optional[List[str]] = None, class_keys: Optional[Dict[int, List[str]]] = None,
+                           progress: bool = False):
+        """DDIM inversion: the probability-flow ODE walked upwards from the latent z0 = init_latent
+        ((B,C,h,w), (1,C,h,w) or (C,h,w), broadcast to the batch of class_counts) under the condition that
+        sample_latent_cond's class_counts / cond / cond_mask / key_order / class_keys describe.  Returns
+        the latent at position p0 = min(S, max(1, floor(strength S + 0.5))) (S for strength None) of
+        ddim_timesteps(steps) — fp32, z0's shape — which sample_latent_cond(..., start_latent=it,
+        strength=strength, sampler="ddim", steps=steps) walks back down, under the same condition to
+        reconstruct z0 or under another one to edit it.  refine = R >= 0: R fixed-point refinements per
+        position (invert_tables), R + 1 network evaluations each; R = 0 is the plain inversion, which
+        reconstructs poorly under CFG, and every refinement closes the gap by a roughly constant factor.
+        A dmx network on the GPU with guidance_scale > 0 runs whole chunks on the device; guidance 0 and
+        foreign models step on the host.  Nothing is drawn: the global RNG state is untouched.  Every
+        argument violation raises ValueError."""
+        T = int(self.num_timesteps)
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= T:
+            raise ValueError(f"steps must be an int in [1, {T}] (got {steps!r})")
+        if isinstance(refine, bool) or not isinstance(refine, int) or refine < 0:
+            raise ValueError(f"refine must be an int >= 0 (got {refine!r})")
+        self._known_start(strength, steps)
+        try:
+            g = float(guidance_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"guidance_scale must be one finite float >= 0 (got {guidance_scale!r})") from None
+        if not (math.isfinite(g) and g >= 0):
+            raise ValueError(f"guidance_scale must be one finite float >= 0 (got {guidance_scale!r})")
+        if init_latent is None:
+            raise ValueError("init_latent (the latent to invert) is required")
+        device = self.device
+        y_list: List[int] = []
+        for cls, num in self._norm_counts(class_counts):
+            y_list += [cls] * num
+        z0 = self._known_inputs(init_latent, None, None, len(y_list), None)[0]
+        y = torch.tensor(y_list, device=device, dtype=torch.long)
+        vals, msk = self._build_cond(y_list, cond, cond_mask, key_order, class_keys, device)
+        x = self._run_cond_loop(model, z0.to(device), y, vals, msk, g, null_label, progress,
+                                ("invert", steps, strength, refine))
+        return x.to(torch.float32)
+
     def _plan(self, x, mode, guidance_scale, known=None, interval=None, rescale=0.0, compose=None,
-              rows=None, geom=None, perturb=None) -> _SamplerPlan:
+              rows=None, geom=None, perturb=None, start=None) -> _SamplerPlan:
         """The plan of a sampling call whose x_T draw is x, on x's device.
         mode: _sampler_mode's result.  interval, rescale: _guidance_args' (t_lo, t_hi) or None and phi.
         compose: _compose_args' tables or None; a composed plan has no scale, interval or rescale.
@@ -1264,7 +1368,11 @@ class Diffuser:
         geom: _geom_args' scale row or None; the plan carries its rows and the sig table of the rule
         (geom_sig for ddpm, the schedule's k_e otherwise), converted once: a loop's graphs hold their pointers.
         perturb: _pag_args' (blocks, branches) or None, for the compose tables that came with it; the
-        pair does not depend on the shard."""
+        pair does not depend on the shard.
+        start = p0 (a strided rule, no `known`): x is no draw but the latent the loop starts from, as it
+        is, at position p0 (sample_latent_cond's start_latent).
+        mode ("invert", S, strength, R): the plan of invert_latent_cond — x is z0, the schedule is
+        invert_tables' and the counter walks its N rows down; it takes none of the other parts."""
         dev = x.device
         rule = "ddpm" if mode is None else mode[0]
         tau = self._mode_timesteps(mode)
@@ -1295,12 +1403,22 @@ class Diffuser:
                     plan.x_start = e0.clone()
                 if kmask is not None:
                     plan.known = (z0, e0, kmask[cut].to(dev), q_a, q_e)
+        if start is not None:
+            if known is not None or rule not in ("ddim", "dpm"):
+                raise ValueError("a start position belongs to a strided loop without a known region")
+            plan.start = int(start)
         if rule == "ddpm":
             plan.tables = self.coef_tables(dev, clamp_prev=True)
         elif rule == "ddim":
             plan.sched = self.ddim_tables(mode[1], mode[2], dev)
+        elif rule == "invert":
+            if not (known is None and interval is None and compose is None and geom is None and not rescale > 0):
+                raise ValueError("inversion takes no known region, interval, rescale, composition or geometry guidance")
+            plan.sched = self.invert_tables(mode[1], mode[2], mode[3], dev)
+            plan.start = int(plan.sched[0].numel())
         else:  # (a loop entering at p0 < S: that row is first-order)
-            plan.sched = self.dpm_tables(mode[1], mode[2], dev, plan.start if known is not None else None)
+            entered = known is not None or start is not None
+            plan.sched = self.dpm_tables(mode[1], mode[2], dev, plan.start if entered else None)
         if geom is not None:
             sig = self.geom_sig(dev) if rule == "ddpm" else plan.sched[1]
             plan.geom = (geom[cut].to(device=dev, dtype=torch.float32).contiguous(), sig)
@@ -1324,22 +1442,25 @@ class Diffuser:
         return run
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
-                       interval=None, rescale=0.0, compose=None, geom=None, perturb=None):
+                       interval=None, rescale=0.0, compose=None, geom=None, perturb=None, start=None):
         """The T loop (diff.py:328-344) over the call's plan (_plan), range-guarded in chunks
         (_guarded_loop): the counter walks timesteps, or the positions of a strided schedule, down
         from plan.start, and a replayed chunk restarts from the x and the solver history it started
         with.  A dmx network with guidance (or a composed call) in device-noise mode runs whole chunks
-        on the device (_device_chunks); every other case steps on the host (_step)."""
-        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom, perturb=perturb)
+        on the device (_device_chunks); every other case steps on the host (_step).  An inversion
+        (mode "invert") draws nothing and takes the device loop in either noise mode; its source latent
+        travels in the history slot, so a replayed chunk restarts from its x and its src."""
+        plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom, perturb=perturb,
+                          **({} if start is None else dict(start=start)))
         x = plan.x_start
         hist = plan.new_hist(x)
         guard = self._guard_target(model, x)
         native = _native_kind(model) in (1, 2) and x.is_cuda and (plan.compose is not None or plan.scale > 0)
-        device_loop = native and self.noise_source == "device"
+        device_loop = native and (self.noise_source == "device" or plan.rule == "invert")
         bar = tqdm(total=plan.start, desc="Sampling (cond+numeric)") if progress else None
         if device_loop:
             x = x.contiguous().clone()
-            seed = 0 if plan.rule == "dpm" else self._seed()  # the DPM solver draws nothing
+            seed = 0 if plan.rule in ("dpm", "invert") else self._seed()  # (these draw nothing)
             run = self._device_chunks(model.native(), plan, x, y, null_label, vals.float().contiguous(),
                                       msk.float().contiguous(), hist, seed, bar)
         else:

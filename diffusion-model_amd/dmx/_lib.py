@@ -60,6 +60,12 @@ class DpmSched(ctypes.Structure):
                 ("hist", ctypes.c_void_p), ("S", ctypes.c_int)]
 
 
+class InvertSched(ctypes.Structure):
+    """dmx_invert_sched (include/dmx.h): per-row tables of a DDIM inversion (countdown order) and its source buffer."""
+    _fields_ = [("t_map", ctypes.c_void_p), ("i_x", ctypes.c_void_p), ("i_e", ctypes.c_void_p),
+                ("adv", ctypes.c_void_p), ("src", ctypes.c_void_p), ("S", ctypes.c_int)]
+
+
 class KnownSched(ctypes.Structure):
     """dmx_known_sched (include/dmx.h): known latent, fixed draw, mask and per-position tables of a known-region loop."""
     _fields_ = [("z0", ctypes.c_void_p), ("e0", ctypes.c_void_p), ("mask", ctypes.c_void_p),
@@ -167,6 +173,10 @@ SIGNATURES = [
     ("dmx_step_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _P]),
     ("dmx_sample_loop_dpm", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DpmSched), _I, _I, _P]),
     ("dmx_dpm_update", _I, [_P, _P, _P, _P, ctypes.c_float, _P, _I, ctypes.POINTER(DpmSched), _I, _I, _I, _I, _P]),
+    ("dmx_step_invert", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(InvertSched), _P]),
+    ("dmx_sample_loop_invert", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(InvertSched), _I, _I, _P]),
+    ("dmx_invert_update", _I, [_P, _P, _P, _P, ctypes.c_float, _P, _I, ctypes.POINTER(InvertSched), _I, _I, _I, _I,
+                               _P]),
     ("dmx_known_blend", _I, [_P, _P, _P, _I, ctypes.POINTER(KnownSched), _I, _I, _I, _I, _P]),
     ("dmx_step_known", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
                             ctypes.POINTER(KnownSched), _P]),

@@ -2518,6 +2518,19 @@ int dmx_step_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sched* sche
   });
 }
 
+static StepMode invert_mode(const dmx_invert_sched* sched) {
+  StepMode mode;
+  mode.invert = sched;
+  return mode;
+}
+
+int dmx_step_invert(dmx_model* m, const dmx_step_args* a, const dmx_invert_sched* sched, void* stream) {
+  return guarded([&] {
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_step(m, a, invert_mode(sched), (hipStream_t)stream);
+  });
+}
+
 int dmx_step_known(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
                    const dmx_known_sched* known, void* stream) {
   return guarded([&] {
@@ -2564,6 +2577,14 @@ int dmx_sample_loop_dpm(dmx_model* m, const dmx_step_args* a, const dmx_dpm_sche
   return guarded([&] {
     REQUIRE(sched != nullptr, "null schedule");
     sample_loop(m, a, StepMode{nullptr, sched}, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop_invert(dmx_model* m, const dmx_step_args* a, const dmx_invert_sched* sched, int steps,
+                           int use_graph, void* stream) {
+  return guarded([&] {
+    REQUIRE(sched != nullptr, "null schedule");
+    sample_loop(m, a, invert_mode(sched), steps, use_graph, (hipStream_t)stream);
   });
 }
 
@@ -2747,6 +2768,22 @@ int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* e
     StepTailParams p = update_params(x, x_out, eu, ec, guidance, pos, pos_stride, n, c, h, w);
     set_sched(p, *sched);
     launch_update(p, Rule::DPM, (hipStream_t)stream);
+  });
+}
+
+// The update is elementwise with one table row per sample, so the (n,c,h,w) operands go through the
+// one-pixel-per-thread tail as n rows of one channel and c*h*w pixels: any c >= 1.
+int dmx_invert_update(const float* x_src, float* x_out, const float* eu, const float* ec, float guidance,
+                      const int64_t* pos, int pos_stride, const dmx_invert_sched* sched, int n, int c, int h, int w,
+                      void* stream) {
+  return guarded([&] {
+    check_sched(sched);
+    REQUIRE(x_out != x_src && x_out != sched->src, "x_out must not alias the source latent");
+    REQUIRE(n >= 1 && n <= 65535 && c >= 1 && h >= 1 && w >= 1, "bad shape");
+    REQUIRE((double)c * (double)h * (double)w < 2147483648.0, "too many elements per sample");
+    StepTailParams p = update_params(x_src, x_out, eu, ec, guidance, pos, pos_stride, n, 1, 1, c * h * w);
+    set_sched(p, *sched);
+    launch_update(p, Rule::INVERT, (hipStream_t)stream);
   });
 }
 

@@ -712,9 +712,10 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* qkv, float*
   }
 }
 
-// (Philox noise, StepTailParams and the ddpm / ddim / dpm element updates: tail_math.h, shared with
-// the composed tail of compose.h.)
-template <bool DDIM, bool DPM = false>
+// (Philox noise, StepTailParams and the ddpm / ddim / dpm / invert element updates: tail_math.h, shared
+// with the composed tail of compose.h.)  INV: the DDIM-inversion instance — no noise; p.x is the
+// position's source latent (the engine passes the schedule's src), p.src receives y on adv rows.
+template <bool DDIM, bool DPM = false, bool INV = false>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int n = blockIdx.y;
@@ -753,7 +754,7 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
   // where sigma is 0 (eta = 0, and position 1 always); DDPM: no noise at t = 1
   float kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
-  const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // the DPM solver takes no noise
+  const bool noisy = (DPM || INV) ? false : DDIM ? kn != 0.f : t != 1;  // DPM and inversion take no noise
   float nz[4] = {0.f, 0.f, 0.f, 0.f};
   if (noisy) {
     if (p.noise != nullptr) {
@@ -765,7 +766,10 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
     }
   }
   float c1 = 0.f, c2 = 0.f, sd = 0.f, ke = 0.f, ka = 0.f, ks = 0.f, kd = 0.f;
-  if (DPM) {  // (ks / kd / kn carry k_x / k_c / k_p)
+  int adv = 0;
+  if (INV) {  // (ks / kd carry i_x / i_e)
+    ks = p.i_x[t - 1], kd = p.i_e[t - 1], adv = p.adv[t - 1];
+  } else if (DPM) {  // (ks / kd / kn carry k_x / k_c / k_p)
     ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_x[t - 1], kd = p.k_c[t - 1], kn = p.k_p[t - 1];
   } else if (DDIM) {
     ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_s[t - 1], kd = p.k_d[t - 1];
@@ -776,7 +780,11 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
     const float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
     flag_nonfinite(p.range_flag, eps);
     const size_t idx = ((size_t)n * Co + c) * p.HW + pix;
-    if (DPM)
+    if (INV) {
+      const float y = invert_elem(p.x[idx], eps, ks, kd);
+      p.x_out[idx] = y;
+      if (adv != 0) p.src[idx] = y;
+    } else if (DPM)
       p.x_out[idx] = dpm_elem(p.x[idx], eps, ke, ka, ks, kd, kn, p.hist + idx);
     else
       p.x_out[idx] = DDIM ? ddim_elem(p.x[idx], eps, ke, ka, ks, kd, kn, nz[c])
@@ -789,7 +797,7 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
 // coalesced, instead of 64 rows at a 256-byte lane stride); the 1x1-conv dot products are
 // reduced over the 16 lanes with DPP (fixed order), then lanes 0..3 of the group finish
 // channel c = lane (CFG mix, posterior mean, Philox noise, store).
-template <bool DDIM, bool DPM = false>
+template <bool DDIM, bool DPM = false, bool INV = false>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -818,7 +826,7 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
   const float v = sub == 0 ? ec[0] : sub == 1 ? ec[1] : sub == 2 ? ec[2] : ec[3];
   float nz = 0.f, kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
-  const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
+  const bool noisy = (DPM || INV) ? false : DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
   const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
   if (noisy) {
     if (p.noise != nullptr) {
@@ -831,7 +839,11 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
   }
   const float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
   flag_nonfinite(p.range_flag, eps);
-  if (DPM)
+  if (INV) {
+    const float y = invert_elem(p.x[idx], eps, p.i_x[t - 1], p.i_e[t - 1]);
+    p.x_out[idx] = y;
+    if (p.adv[t - 1] != 0) p.src[idx] = y;
+  } else if (DPM)
     p.x_out[idx] = dpm_elem(p.x[idx], eps, p.k_e[t - 1], p.k_a[t - 1], p.k_x[t - 1], p.k_c[t - 1], p.k_p[t - 1],
                             p.hist + idx);
   else if (DDIM)

@@ -54,19 +54,33 @@ static void set_sched(StepTailParams& p, const dmx_dpm_sched& dp) {
   p.hist = dp.hist;
 }
 
+// The inversion form: countdown positions over the S rows; the tail reads the position's source latent
+// where the other rules read x (kernels.h), and stores into the same buffer on adv rows.
+static void set_sched(StepTailParams& p, const dmx_invert_sched& iv) {
+  p.tmax = iv.S;
+  p.t_map = iv.t_map;
+  p.i_x = iv.i_x;
+  p.i_e = iv.i_e;
+  p.adv = iv.adv;
+  p.src = iv.src;
+}
+
 // The tail's launch: the instance of the update rule; head4 = the network head path with Co = 4
 // (16 pixels per block), else one pixel per thread; comp: the composed head4 tail (launch.h).
 static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st,
                              const ComposeParams* comp = nullptr) {
   if (comp != nullptr) {
     if (!head4) throw Error(DMX_E_INTERNAL, "the composed tail is the Co = 4 head tail");
+    if (rule == Rule::INVERT) throw Error(DMX_E_INTERNAL, "there is no composed inversion tail");
     launch_compose_tail4(p, *comp, rule == Rule::DDIM, rule == Rule::DPM, grid, st);
   } else if (!head4) {
-    if (rule == Rule::DPM) step_tail_kernel<false, true><<<grid, 256, 0, st>>>(p);
+    if (rule == Rule::INVERT) step_tail_kernel<false, false, true><<<grid, 256, 0, st>>>(p);
+    else if (rule == Rule::DPM) step_tail_kernel<false, true><<<grid, 256, 0, st>>>(p);
     else if (rule == Rule::DDIM) step_tail_kernel<true><<<grid, 256, 0, st>>>(p);
     else step_tail_kernel<false><<<grid, 256, 0, st>>>(p);
   } else {
-    if (rule == Rule::DPM) step_tail4_kernel<false, true><<<grid, 256, 0, st>>>(p);
+    if (rule == Rule::INVERT) step_tail4_kernel<false, false, true><<<grid, 256, 0, st>>>(p);
+    else if (rule == Rule::DPM) step_tail4_kernel<false, true><<<grid, 256, 0, st>>>(p);
     else if (rule == Rule::DDIM) step_tail4_kernel<true><<<grid, 256, 0, st>>>(p);
     else step_tail4_kernel<false><<<grid, 256, 0, st>>>(p);
   }
@@ -175,7 +189,10 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   p.seed = a.seed;
   p.sample_offset = a.sample_offset;
   p.range_flag = m->range_flag;
-  if (rule == Rule::DPM) {
+  if (rule == Rule::INVERT) {
+    set_sched(p, *mode.invert);
+    p.x = mode.invert->src;  // (the latent the network saw, a.x_in, is not an operand of the update)
+  } else if (rule == Rule::DPM) {
     set_sched(p, *mode.dpm);
   } else if (rule == Rule::DDIM) {
     set_sched(p, *mode.ddim);
@@ -185,7 +202,10 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
     p.c2 = a.c2;
     p.sd = a.sd;
   }
-  R.layer = rule == Rule::DPM ? "out+cfg+dpm" : rule == Rule::DDIM ? "out+cfg+ddim" : "out+cfg+ddpm";
+  R.layer = rule == Rule::INVERT ? "out+cfg+invert"
+            : rule == Rule::DPM  ? "out+cfg+dpm"
+            : rule == Rule::DDIM ? "out+cfg+ddim"
+                                 : "out+cfg+ddpm";
   const double el = (double)a.n * p.Co * p.HW;
   const double head_flops = 2.0 * N * p.HW * 64.0 * p.Co, head_bytes = 4.0 * ((double)N * p.HW * 64 + 3.0 * el);
   if (comp != nullptr) {
@@ -265,6 +285,13 @@ static void check_sched(const dmx_dpm_sched* dp) {
   REQUIRE(dp->hist != nullptr, "DPM schedule needs a history buffer");
 }
 
+static void check_sched(const dmx_invert_sched* iv) {
+  REQUIRE(iv != nullptr, "null schedule");
+  REQUIRE(iv->S >= 1, "schedule needs S >= 1 rows");
+  REQUIRE(iv->t_map && iv->i_x && iv->i_e && iv->adv, "null table in schedule");
+  REQUIRE(iv->src != nullptr, "inversion schedule needs a source buffer");
+}
+
 static void check_known(const dmx_known_sched* kn, const float* x_out) {
   REQUIRE(kn != nullptr, "null known-region schedule");
   REQUIRE(kn->S >= 1, "known-region schedule needs S >= 1 positions");
@@ -278,6 +305,7 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   REQUIRE(m != nullptr, "null model");
   REQUIRE(a != nullptr, "null step args");
   const bool cfg = m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr;
+  if (const char* why = mode.invert_conflict()) throw Error(DMX_E_ARG, why);
   if (mode.comp != nullptr) {
     const dmx_compose& c = *mode.comp;
     REQUIRE(c.K >= 1 && c.K <= DMX_COMPOSE_MAX, "compose K must lie in [1, DMX_COMPOSE_MAX]");
@@ -323,6 +351,7 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   REQUIRE(mode.ddim == nullptr || mode.dpm == nullptr, "at most one of the DDIM and DPM schedules");
   if (mode.ddim != nullptr) check_sched(mode.ddim);
   if (mode.dpm != nullptr) check_sched(mode.dpm);
+  if (mode.invert != nullptr) check_sched(mode.invert);
   if (mode.known != nullptr) {  // its tables must cover the positions of the step's schedule
     check_known(mode.known, a->x_out);
     REQUIRE(mode.known->mask != nullptr, "a known-region step needs a mask");
@@ -331,7 +360,10 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   }
   check_shapes(m, a->n, a->h, a->w);
   REQUIRE(a->x_in && a->x_out && a->t, "null tensor in step args");
-  if (mode.rule() == Rule::DPM) {
+  if (mode.rule() == Rule::INVERT) {
+    REQUIRE(a->noise == nullptr, "inversion takes no noise (noise must be NULL)");
+    REQUIRE(mode.invert->src != a->x_in && mode.invert->src != a->x_out, "src must not alias x");
+  } else if (mode.rule() == Rule::DPM) {
     REQUIRE(a->noise == nullptr, "the DPM solver takes no noise (noise must be NULL)");
     REQUIRE(mode.dpm->hist != a->x_in && mode.dpm->hist != a->x_out, "hist must not alias x");
   } else if (mode.rule() == Rule::DDPM) {  // (the strided steps ignore these)
@@ -386,7 +418,8 @@ static constexpr int kGraphSteps = 8;
 // `steps` in-place steps.  The scalar a->t counts down by one per step in every mode — timesteps in
 // the DDPM loop, positions of the schedule in the strided ones.  The DPM history buffer is updated
 // in place by every step and the known-region blend reads the position scalar its tail read, so
-// neither needs more than t's ping-pong inside the multi-step graph.
+// neither needs more than t's ping-pong inside the multi-step graph.  An inversion counts its rows
+// down the same way and updates its source buffer in place, as the DPM loop its history.
 static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mode, int steps, int use_graph,
                         hipStream_t st) {
   validate(m, a, mode, true);
@@ -443,7 +476,8 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
 }
 
 // ---------------------------------------------------------------------------
-// Standalone updates (dmx_ddpm_update / dmx_ddim_update / dmx_dpm_update): the tail on given eps
+// Standalone updates (dmx_ddpm_update / dmx_ddim_update / dmx_dpm_update / dmx_invert_update): the
+// tail on given eps
 // ---------------------------------------------------------------------------
 // What the three have in common; the caller adds its tables (and noise, where its rule draws).
 static StepTailParams update_params(const float* x, float* x_out, const float* eu, const float* ec, float guidance,

@@ -8,7 +8,7 @@
 
 namespace dmx {
 
-enum class Rule { DDPM, DDIM, DPM };  // the tail's update
+enum class Rule { DDPM, DDIM, DPM, INVERT };  // the tail's update
 
 // The optional parts of a step (include/dmx.h); all null: the plain DDPM step.
 struct StepMode {
@@ -21,14 +21,35 @@ struct StepMode {
   const dmx_geom_guide* geom = nullptr;    // geometry guidance: the GeomHead's input gradient joins the CFG eps
   const dmx_perturb* perturb = nullptr;    // perturbed-attention guidance: identity attention in the trailing
                                            // branches of comp
+  const dmx_invert_sched* invert = nullptr;  // DDIM inversion: a.t holds countdown positions over the rows; no
+                                             // other part may be given (invert_conflict)
 
-  Rule rule() const { return dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM; }
+  Rule rule() const {
+    return invert != nullptr ? Rule::INVERT : dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM;
+  }
+  // The part an inversion step cannot be combined with, as the message of its DMX_E_ARG; null: none.
+  // (A guidance struct with rescale == 0 is no part, as everywhere.)
+  const char* invert_conflict() const {
+    if (invert == nullptr) return nullptr;
+    if (ddim != nullptr) return "an inversion step takes no DDIM schedule (its rows are its schedule)";
+    if (dpm != nullptr) return "an inversion step takes no DPM schedule";
+    if (known != nullptr) return "an inversion step takes no known region";
+    if (rescale() > 0.f) return "an inversion step takes no guidance rescale";
+    if (comp != nullptr) return "an inversion step takes no composition";
+    if (geom != nullptr) return "an inversion step takes no geometry guidance";
+    if (perturb != nullptr) return "an inversion step takes no perturbed-attention guidance";
+    return nullptr;
+  }
   // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
   // rescale == 0 is no guidance struct at all: launches and graph key are those of the plain call.
   float rescale() const { return gd != nullptr && gd->rescale > 0.f ? gd->rescale : 0.f; }
   // positions of the step's schedule, and their timesteps (null: the position is the timestep)
-  int positions(const dmx_step_args& a) const { return dpm != nullptr ? dpm->S : ddim != nullptr ? ddim->S : a.T; }
-  const int64_t* t_map() const { return dpm != nullptr ? dpm->t_map : ddim != nullptr ? ddim->t_map : nullptr; }
+  int positions(const dmx_step_args& a) const {
+    return invert != nullptr ? invert->S : dpm != nullptr ? dpm->S : ddim != nullptr ? ddim->S : a.T;
+  }
+  const int64_t* t_map() const {
+    return invert != nullptr ? invert->t_map : dpm != nullptr ? dpm->t_map : ddim != nullptr ? ddim->t_map : nullptr;
+  }
 };
 
 // Compared bytewise, so every byte is zero unless make_graph_key sets it.
@@ -41,13 +62,14 @@ struct GraphKey {
   dmx_compose comp;      // composed loops: K and the four tables (all zero otherwise)
   dmx_geom_guide geom;   // geometry-guided loops: the two tables and S (all zero otherwise)
   dmx_perturb perturb;   // perturbed loops: the block and branch bits (all zero otherwise)
+  dmx_invert_sched inv;  // inversion loops: tables, source buffer and S = rows (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
 
 // The key of a loop: everything its graphs hold.  The step args enter as the caller's bytes; the
 // optional structs enter member by member, so their padding stays zero.  A validated schedule has
-// S >= 1, which keeps the keys of the three rules, and known-region keys from plain ones, apart;
+// S >= 1, which keeps the keys of the four rules, and known-region keys from plain ones, apart;
 // a validated composition has K >= 1, which keeps composed keys from plain ones; validated geometry
 // guidance has non-null tables and S >= 1, which keeps its keys from plain ones; a validated
 // perturbation has blocks >= 1, which keeps perturbed keys from composed ones.
@@ -77,6 +99,14 @@ inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int
     key.dpm.k_p = mode.dpm->k_p;
     key.dpm.hist = mode.dpm->hist;  // read and written by every step
     key.dpm.S = mode.dpm->S;
+  } else if (mode.rule() == Rule::INVERT) {
+    key.a.seed = 0;  // (not read: inversion draws nothing)
+    key.inv.t_map = mode.invert->t_map;
+    key.inv.i_x = mode.invert->i_x;
+    key.inv.i_e = mode.invert->i_e;
+    key.inv.adv = mode.invert->adv;
+    key.inv.src = mode.invert->src;  // read by every row, written by the last row of a position
+    key.inv.S = mode.invert->S;
   }
   if (mode.known != nullptr) {  // the blend's launches are in the graphs too
     key.known.z0 = mode.known->z0;

@@ -1,6 +1,6 @@
 // dmx — the small device helpers the step tails share with the CFG-rescale kernels (guidance.h) and
 // the composed tail (compose.h): the range-guard flag, the one-rounding barrier, the 16-lane DPP
-// sum, the Philox noise, the tails' parameter block and the element updates of the three rules.
+// sum, the Philox noise, the tails' parameter block and the element updates of the four rules.
 #pragma once
 #include <type_traits>
 
@@ -93,6 +93,12 @@ struct StepTailParams {
   // the DDIM form, k_x / k_c / k_p per position, hist (x's shape) read where k_p != 0 and written
   const float* k_x; const float* k_c; const float* k_p;
   float* hist;
+  // DDIM-inversion form, the <false, false, true> instantiations: t holds countdown positions in
+  // [1, tmax] over the rows of the schedule, t_map[c - 1] is the row's evaluation timestep, i_x / i_e /
+  // adv per row; x points at the source latent of the position (the schedule's src in a step: the
+  // latent the network saw is not read), src (x's shape) is written where adv != 0
+  const float* i_x; const float* i_e; const int* adv;
+  float* src;
 };
 
 DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float nz) {
@@ -121,5 +127,13 @@ DMX_DEV float dpm_elem(float x, float eps, float ke, float ka, float kx, float k
   *hist = x0;
   return out;
 }
+// DDIM inversion (Song et al. 2021, eq. 12 with sigma = 0, solved for the noisier latent) from timestep
+// s up to t > s, src being the latent at s and eps the prediction at the row's evaluation point:
+//   y = i_x*src + i_e*eps
+// with i_x = sqrt(ab[t]/ab[s]), i_e = sqrt(1-ab[t]) - i_x*sqrt(1-ab[s]) tabulated per row on the host;
+// one rounding per op in torch's evaluation order.  The rows of one position share src: the first
+// predicts at (src, s), the refinement rows at (y, t), iterating y <- F(src, eps(y, t)) towards the
+// exact preimage of the DDIM step t -> s; the position's last row stores its y as the next src.
+DMX_DEV float invert_elem(float src, float eps, float ix, float ie) { return rnd(ix * src) + rnd(ie * eps); }
 
 }  // namespace dmx

@@ -14,7 +14,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DdimSched, DpmSched, Guidance, KnownSched, StepArgs, check
+from ._lib import DdimSched, DpmSched, Guidance, InvertSched, KnownSched, StepArgs, check
 
 TIME_DIM = 256
 
@@ -428,9 +428,28 @@ class NativeModel:
                              f"(got {tuple(perturb)!r})")
         return _lib.Perturb(blocks, branches)
 
+    def _invert(self, x, invert, sched, hist, known, rescale, compose, geom, perturb, noise=None):
+        """The C view of invert = (tables, src) for a step or loop on x, which takes no other optional part;
+        makes sure the time table reaches the rows' largest timestep (read back once per table tuple,
+        which is kept alive with the value)."""
+        others = (("sched", sched), ("hist", hist), ("known", known), ("compose", compose), ("geom", geom),
+                  ("perturb", perturb), ("noise", noise))
+        given = [nm for nm, v in others if v is not None] + (["rescale"] if float(rescale) > 0 else [])
+        if given:
+            raise ValueError(f"an inversion step takes no {' / '.join(given)}")
+        if not isinstance(invert, (tuple, list)) or len(invert) != 2:
+            raise ValueError("invert must be the pair (tables, src)")
+        tables, src = invert
+        iv = _invert_struct(tables, x.device, src, x)
+        last = getattr(self, "_invert_last", None)
+        if last is None or last[0] is not tables[0]:
+            last = self._invert_last = (tables[0], int(tables[0].max().item()))
+        self.ctx.ensure_time_table(last[1])
+        return iv
+
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
              sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
-             perturb=None):
+             perturb=None, invert=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -451,9 +470,16 @@ class NativeModel:
         step replaces the training tape.  None is the plain step, launched exactly as without the keyword.
         perturb = (blocks, branches) (include/dmx.h dmx_perturb; with compose only): perturbed-attention
         guidance — the branches of bit mask `branches` (the composition's trailing ones) run with identity
-        attention in the blocks of bit mask `blocks` (bit i: sa(i+1)).  None is the composed step."""
+        attention in the blocks of bit mask `blocks` (bit i: sa(i+1)).  None is the composed step.
+        invert = (tables, src) (include/dmx.h dmx_invert_sched; tables: Diffuser.invert_tables, src: fp32,
+        x's shape, not x): one row of a DDIM inversion instead — `t` holds countdown positions in [1, N],
+        x_out = i_x src + i_e eps and src takes it on the last row of a position.  `tables`, `noise` and
+        `seed` are not read, and no other optional part may be given."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        iv = None
+        if invert is not None:
+            iv = self._invert(x_in, invert, sched, hist, known, rescale, compose, geom, perturb, noise)
         pt = self._perturb(perturb, compose, geom) if perturb is not None else None
         gg = None
         if geom is not None:
@@ -463,12 +489,18 @@ class NativeModel:
             comp, self._live_comp = self._compose(x_in, compose, rescale)
             y = vals = mask = None
             null_label, guidance, rescale = 0, 0.0, 0.0
-        mode, tables = self._mode(x_in, sched, hist, known, rescale, guidance, y, tables)
+        if iv is None:
+            mode, tables = self._mode(x_in, sched, hist, known, rescale, guidance, y, tables)
+        else:
+            tables = None
         t, y, vals, mask, noise = self._norm_inputs(x_in, t, y, vals, mask, noise)
         a = self._args(x_in, x_out, t, t_stride, y, null_label, vals, mask, guidance, tables, noise, seed,
                        sample_offset)
         with torch.cuda.device(x_in.device):
-            if gg is not None:
+            if iv is not None:
+                check(self.lib.dmx_step_invert(self.handle, ctypes.byref(a), ctypes.byref(iv),
+                                               ctypes.c_void_p(_stream(x_in.device))))
+            elif gg is not None:
                 check(self.lib.dmx_step_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
                                              ctypes.c_void_p(_stream(x_in.device))))
             elif pt is not None:
@@ -502,7 +534,7 @@ class NativeModel:
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
                     use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
-                    perturb=None):
+                    perturb=None, invert=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -520,8 +552,14 @@ class NativeModel:
         pointers of the converted tables: pass contiguous int64 / fp32 device tensors to replay them.
         geom as in step(): every step of the loop is a geometry-guided step; the graphs hold the pointers
         of its two tables.
-        perturb as in step(): every step of the loop is a perturbed composed step, with graphs of its own."""
+        perturb as in step(): every step of the loop is a perturbed composed step, with graphs of its own.
+        invert = (tables, src) as in step(): `steps` rows of a DDIM inversion, t_dev counting the rows
+        down from N; nothing is drawn (`seed` is not read) and the graphs hold the pointers of the four
+        tables and of src."""
         _check_state(x, "x")
+        iv = None
+        if invert is not None:
+            iv = self._invert(x, invert, sched, hist, known, rescale, compose, geom, perturb)
         pt = self._perturb(perturb, compose, geom) if perturb is not None else None
         gg = None
         if geom is not None:
@@ -533,22 +571,30 @@ class NativeModel:
             self._live_comp = comp_live
             y = vals = mask = None
             null_label, guidance, rescale = 0, 0.0, 0.0
-        mode, tables = self._mode(x, sched, hist, known, rescale, guidance, y, tables)
+        if iv is None:
+            mode, tables = self._mode(x, sched, hist, known, rescale, guidance, y, tables)
+        else:
+            tables = invert[0]  # (kept alive below; the step args carry no tables)
         if t_dev.dtype != torch.long or not t_dev.is_contiguous() or t_dev.device != x.device:
             raise ValueError("sample_loop: t_dev must be a contiguous int64 device scalar on x's device "
                              "(it is decremented in place)")
         _, y, vals, mask, _ = self._norm_inputs(x, t_dev, y, vals, mask, None)
-        a = self._args(x, x, t_dev, 0, y, null_label, vals, mask, guidance, tables, None, seed, sample_offset)
+        a = self._args(x, x, t_dev, 0, y, null_label, vals, mask, guidance, None if iv is not None else tables, None,
+                       seed, sample_offset)
         cur = torch.cuda.current_stream(x.device)
         side = self.side_stream()
         side.wait_stream(cur)
-        live = (x, t_dev, y, vals, mask, hist) + tuple(sched if sched is not None else tables) + tuple(known or ())
+        live = (x, t_dev, y, vals, mask, hist if iv is None else invert[1])
+        live += tuple(sched if sched is not None else tables) + tuple(known or ())
         live += tuple(comp_live) + (tuple(geom) if geom is not None else ())
         for keep in live:
             if keep is not None:
                 keep.record_stream(side)
         with torch.cuda.device(x.device):
-            if gg is not None:
+            if iv is not None:
+                check(self.lib.dmx_sample_loop_invert(self.handle, ctypes.byref(a), ctypes.byref(iv), int(steps),
+                                                      int(use_graph), ctypes.c_void_p(side.cuda_stream)))
+            elif gg is not None:
                 check(self.lib.dmx_sample_loop_geom(self.handle, ctypes.byref(a), *mode[:3], ctypes.byref(gg),
                                                     int(steps), int(use_graph), ctypes.c_void_p(side.cuda_stream)))
             elif pt is not None:
@@ -873,6 +919,50 @@ def dpm_update(x, eu, ec, guidance, pos, sched, hist, out=None):
     with torch.cuda.device(dev):
         check(lib.dmx_dpm_update(_ptr(x_c), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
                                  ctypes.byref(sc), n, c, h, w, ctypes.c_void_p(_stream(dev))))
+    return out
+
+
+def _invert_struct(tables, device, src, x) -> InvertSched:
+    """The C view of the (t_eval, i_x, i_e, adv) tables of Diffuser.invert_tables and the source buffer:
+    int64 / fp32 / fp32 / int32 contiguous 1-D tensors of one length N on `device`, src a contiguous fp32
+    tensor of x's shape on `device` that does not share x's storage.  Nothing is converted: the kernels
+    read the caller's tensors."""
+    if not isinstance(tables, (tuple, list)) or len(tables) != 4:
+        raise ValueError("invert tables must be the 4-tuple (t_eval, i_x, i_e, adv) of Diffuser.invert_tables")
+    N = int(tables[0].numel())
+    for i, (v, want) in enumerate(zip(tables, (torch.long, torch.float32, torch.float32, torch.int32))):
+        if v.dtype != want or v.dim() != 1 or v.numel() != N or not v.is_contiguous() or v.device != device:
+            raise ValueError(f"invert tables[{i}] must be a contiguous 1-D {want} tensor of {N} entries on {device}")
+    if N < 1:
+        raise ValueError("invert tables are empty")
+    if (not isinstance(src, torch.Tensor) or src.dtype != torch.float32 or not src.is_contiguous()
+            or src.device != device or tuple(src.shape) != tuple(x.shape)):
+        raise ValueError(f"src must be a contiguous fp32 tensor of shape {tuple(x.shape)} on {device}")
+    if src.data_ptr() == x.data_ptr():
+        raise ValueError("src must not alias x")
+    return InvertSched(*[v.data_ptr() for v in tables], src.data_ptr(), N)
+
+
+def invert_update(x, eu, ec, guidance, pos, tables, src, out=None):
+    """Standalone DDIM-inversion update (include/dmx.h dmx_invert_update) for duck-typed models: returns
+    y = i_x src + i_e eps and stores it in src where the row's adv is set.  x: the latent the prediction
+    was made on (it gives the shape, any C >= 1; its values are not read); pos: (n,) countdown positions in
+    [1, N]; tables: Diffuser.invert_tables on x's device; src: fp32, contiguous, x's shape.
+    out: where y goes (fp32, contiguous, x's shape; may be x itself, never src), a new tensor by default.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    x_c, eu_c, ec_c, _, p_c = _update_operands(x, eu, ec, None, pos, "pos")
+    dev = x.device
+    if out is None:
+        out = torch.empty_like(x_c)
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev
+          or tuple(out.shape) != tuple(x_c.shape)):
+        raise ValueError(f"out must be a contiguous fp32 tensor of shape {tuple(x_c.shape)} on {dev}")
+    iv = _invert_struct(tables, dev, src, out)  # (src must not be where y goes)
+    n, c, h, w = x_c.shape
+    with torch.cuda.device(dev):
+        check(lib.dmx_invert_update(_ptr(src), _ptr(out), _ptr(eu_c), _ptr(ec_c), float(guidance), _ptr(p_c), 1,
+                                    ctypes.byref(iv), n, c, h, w, ctypes.c_void_p(_stream(dev))))
     return out
 
 

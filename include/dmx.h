@@ -217,6 +217,49 @@ int dmx_dpm_update(const float* x, float* x_out, const float* eu, const float* e
                    const int64_t* pos, int pos_stride, const dmx_dpm_sched* sched, int n, int c, int h, int w,
                    void* stream);
 
+/* ---- DDIM inversion: the probability-flow ODE walked upwards, from a latent z0 to the noisy latent
+ * that the DDIM sampler (eta = 0) maps back to z0 (Song et al. 2021, eq. 12 with sigma = 0 solved for
+ * the noisier latent; fixed-point refinement as in Pan et al. 2023, "Effective real image editing with
+ * accelerated iterative diffusion inversion"; no reference counterpart).  With tau the ascending
+ * timesteps of a DDIM schedule, position p = 1..p0 goes from s = tau_{p-1} (tau_0 = 0, alpha_bar 1) up
+ * to t = tau_p in R + 1 rows k = 0..R, each computing
+ *   eps = eu + g*(ec-eu) at (x, t_eval);   y = i_x*src + i_e*eps;   x <- y;   adv != 0: src <- y
+ * one IEEE rounding per operation in that order, with
+ *   i_x = sqrt(ab[t]/ab[s]),  i_e = sqrt(1-ab[t]) - i_x*sqrt(1-ab[s]),
+ *   t_eval = s for k = 0 (tau_1 at p = 1: there is no timestep 0), t for k >= 1,  adv = (k == R).
+ * src is the latent at the start of the position: row 0 is the plain DDIM inversion step, rows k >= 1
+ * iterate y <- F(src, eps(y, t)), whose fixed point is the exact preimage of the DDIM step t -> s.  The
+ * S = p0*(R+1) rows are stored in COUNTDOWN order — the counter c runs S..1 and reads row c - 1; the
+ * row of (p, k) is c = S - ((p-1)*(R+1) + k) — so a->t counts down as in every other loop and t_map is
+ * the t_eval column.  A caller starts with x == src == z0 (two buffers).  src has x's shape (n,C,h,w),
+ * must not alias x, and each of its elements is read and written by the same lane.  No noise is read or
+ * drawn.  All members are device pointers / counts owned by the caller. */
+typedef struct dmx_invert_sched {
+  const int64_t* t_map; /* [S] int64: t_eval per row */
+  const float* i_x;     /* [S] each */
+  const float* i_e;
+  const int* adv;       /* [S] int32 */
+  float* src;           /* (n,C,h,w), read + written */
+  int S;                /* rows */
+} dmx_invert_sched;
+
+/* dmx_step / dmx_sample_loop with the inversion update: a->t holds COUNTDOWN positions in [1, S],
+ * a->noise must be NULL and a->c1, c2, sd, T and seed are not read.  CFG, the one-forward step for
+ * guidance 0, t_stride and ragged batches are those of the DDIM step.  There is no known region,
+ * rescale, composition, geometry or perturbed-attention guidance.  A captured graph belongs to one
+ * schedule (table pointers, src and S): another schedule or src buffer, or a DDIM, DPM or DDPM loop
+ * on the same model captures anew. */
+int dmx_step_invert(dmx_model* m, const dmx_step_args* a, const dmx_invert_sched* sched, void* stream);
+int dmx_sample_loop_invert(dmx_model* m, const dmx_step_args* a, const dmx_invert_sched* sched, int steps,
+                           int use_graph, void* stream);
+/* Standalone update for duck-typed foreign models (ec NULL => eps = eu), any c >= 1; pos: device int64
+ * countdown positions, pos_stride 0 => one value for every sample.  x_src is the source latent the update
+ * reads (sched->src in a loop), sched->src receives y where adv != 0; x_out may alias
+ * the x the prediction was made on, never x_src or sched->src. */
+int dmx_invert_update(const float* x_src, float* x_out, const float* eu, const float* ec, float guidance,
+                      const int64_t* pos, int pos_stride, const dmx_invert_sched* sched, int n, int c, int h, int w,
+                      void* stream);
+
 /* ---- Known-region sampling: img2img starts and masked inpainting (no reference counterpart).
  * z0 is a known latent and e0 one fixed Gaussian draw, both (n,C,h,w); mask is (n,h,w) in [0,1],
  * broadcast over channels, 1 = regenerate, 0 = keep.  Positions p in [1, S] and tau are those of
@@ -417,7 +460,7 @@ int dmx_unet_forward_perturbed(dmx_model* m, const float* x, const int64_t* t, c
 int dmx_attn_identity(const float* qkv, float* out, int n, int L, int C, void* stream);
 
 /* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
- * distinct loops (distinct dmx_step_args / schedule / known region / guidance / composition / perturbation / geometry guidance / time-table
+ * distinct loops (distinct dmx_step_args / schedule / inversion / known region / guidance / composition / perturbation / geometry guidance / time-table
  * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
  * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
  * after another, inside the model's one workspace; whatever reallocates or invalidates it (a

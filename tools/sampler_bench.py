@@ -10,7 +10,9 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    noise as the DDPM step does), the DPM-Solver++(2M) loop (S = 50, log-SNR spacing; it draws nothing and
    reads and writes its history buffer) and the DDPM loop alternate in one process, the DDPM leg twice per
    round (legs ddpm_a, ddim, dpmpp_2m, ddpm_b), so the spread between two measurements of the SAME loop is
-   known and the few-step legs are judged against it, not against a preset figure.  A model
+   known and the few-step legs are judged against it, not against a preset figure.  A DDIM-inversion
+   leg (S = 50, R = 1: 100 rows; a row is one forward, the inverting tail reads and on the last row of
+   a position writes its source latent) runs between dpmpp_2m and ddpm_b: ms per row.  A model
    keeps the graphs of its last four loops: every leg first runs 8 steps untimed (a capture, or a
    replay where its graphs are still held), then 48 steps (six launches of the 8-step graph)
    between two device events.  Reported: the median over the rounds.
@@ -34,7 +36,8 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    from the steady ones by the sampler's own start-up only.  (dpmpp_2m, S = 20) is also run with a guidance
    interval that covers half of its positions (the middle ten), to be compared with the plain leg of
    the same run: its loop alternates unguided / guided / unguided segments, so it shows whether their
-   graphs are reused.
+   graphs are reused.  Last, invert_latent_cond(S = 20, strength 0.3, R = 2) followed by
+   sample_latent_cond(start_latent=..., ddim) and the decode: the edit round trip, in images/s.
 
 There is no fallback: without a GPU this fails."""
 import argparse
@@ -76,16 +79,21 @@ def loop_legs(nm, d, dev, rounds):
     tables = d.coef_tables(dev, True)
     sched = d.ddim_tables(S, 1.0, dev)
     dpm_sched, hist = d.dpm_tables(S, "logsnr", dev), torch.empty_like(x0)
+    inv_tab, src = d.invert_tables(S, None, 1, dev), torch.empty_like(x0)
+    inv_rows = int(inv_tab[0].numel())
 
     def leg(kind):
-        start = T if kind == "ddpm" else S  # (the few-step legs start at position S: no history needed)
+        # (the few-step legs start at position S: no history needed; the inversion at its first row)
+        start = T if kind == "ddpm" else inv_rows if kind == "invert" else S
         kw = {"ddpm": dict(seed=1234), "ddim": dict(seed=1234, sched=sched),
-              "dpm": dict(sched=dpm_sched, hist=hist)}[kind]
+              "dpm": dict(sched=dpm_sched, hist=hist), "invert": dict(invert=(inv_tab, src))}[kind]
         tab = tables if kind == "ddpm" else None
         x.copy_(x0)
+        src.copy_(x0)
         t_dev.fill_(start)
         nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tab, WARM, **kw)  # captures this loop's graphs
         x.copy_(x0)
+        src.copy_(x0)
         t_dev.fill_(start)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -96,17 +104,20 @@ def loop_legs(nm, d, dev, rounds):
         assert int(t_dev.item()) == start - TIMED and bool(torch.isfinite(x).all())
         return e0.elapsed_time(e1) / TIMED
 
-    ms = {"ddpm_a": [], "ddim": [], "dpmpp_2m": [], "ddpm_b": []}
+    ms = {"ddpm_a": [], "ddim": [], "dpmpp_2m": [], "invert": [], "ddpm_b": []}
     leg("ddpm")  # workspace, split planes, time table
     for _ in range(rounds):
         ms["ddpm_a"].append(leg("ddpm"))
         ms["ddim"].append(leg("ddim"))
         ms["dpmpp_2m"].append(leg("dpm"))
+        ms["invert"].append(leg("invert"))
         ms["ddpm_b"].append(leg("ddpm"))
     med = {k: statistics.median(v) for k, v in ms.items()}
     ddpm_mean = 0.5 * (med["ddpm_a"] + med["ddpm_b"])
     return {"ms_per_step_ddpm_a": round(med["ddpm_a"], 4), "ms_per_step_ddpm_b": round(med["ddpm_b"], 4),
             "ms_per_step_ddim": round(med["ddim"], 4), "ms_per_step_dpmpp_2m": round(med["dpmpp_2m"], 4),
+            "ms_per_row_invert": round(med["invert"], 4),
+            "invert_minus_ddim_ms": round(med["invert"] - med["ddim"], 4),
             "ddpm_spread_ms": round(abs(med["ddpm_a"] - med["ddpm_b"]), 4),
             "ddim_minus_ddpm_mean_ms": round(med["ddim"] - ddpm_mean, 4),
             "dpmpp_2m_minus_ddpm_mean_ms": round(med["dpmpp_2m"] - ddpm_mean, 4),
@@ -381,6 +392,25 @@ def end_to_end(model, dev):
                      "steady_s": round(min(secs[1:]), 4), "steady_images_per_s": round(B / min(secs[1:]), 2),
                      "calls_s": [round(v, 4) for v in secs],
                      "graph_captures": model.native().graph_captures() - c0}
+    # the edit round trip: invert 6 of 20 positions with two refinements (18 rows), sample back, decode
+    g = torch.Generator().manual_seed(12)
+    z0 = (0.8 * torch.randn((B, 4, HW, HW), generator=g)).to(dev)
+    kw_inv = dict(guidance_scale=GUIDANCE, cond=vals, cond_mask=mask)
+    kw_back = dict(kw, start_latent=None, strength=0.3, sampler="ddim", steps=20)
+    del kw_back["z_shape"]
+    secs = []
+    c0 = model.native().graph_captures()
+    for _ in range(4):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lat = d.invert_latent_cond(model, z0, counts, steps=20, strength=0.3, refine=2, **kw_inv)
+        imgs = d.sample_latent_cond(model, counts, **dict(kw_back, start_latent=lat))
+        secs.append(time.perf_counter() - t0)
+        assert len(imgs) == B and imgs[0].size == (8 * HW, 8 * HW)
+    out["invert_S20_s0.3_R2_plus_resample"] = {
+        "first_call_s": round(secs[0], 4), "first_call_images_per_s": round(B / secs[0], 2),
+        "steady_s": round(min(secs[1:]), 4), "steady_images_per_s": round(B / min(secs[1:]), 2),
+        "calls_s": [round(v, 4) for v in secs], "graph_captures": model.native().graph_captures() - c0}
     out["range_fallbacks"] = d.range_fallbacks
     return out
 

@@ -21,6 +21,7 @@ static int fails = 0;
 
 static float mem[64];
 static int64_t imem[8];
+static int amem[4];
 
 // Every struct is filled over `fill` bytes first: what its padding then holds.
 struct Inputs {
@@ -32,6 +33,7 @@ struct Inputs {
   dmx_compose comp;
   dmx_geom_guide geom;
   dmx_perturb perturb;
+  dmx_invert_sched inv;
   explicit Inputs(int fill = 0) {
     std::memset(&a, 0, sizeof(a));  // (the step args enter the key as the caller's bytes)
     a.x_in = a.x_out = mem;
@@ -88,7 +90,28 @@ struct Inputs {
     std::memset(&perturb, fill, sizeof(perturb));
     perturb.blocks = 4;    // sa3
     perturb.branches = 4;  // branch 2 of K = 2
+    std::memset(&inv, fill, sizeof(inv));
+    inv.t_map = imem + 4;
+    inv.i_x = mem + 22;
+    inv.i_e = mem + 23;
+    inv.adv = amem;
+    inv.src = mem + 24;
+    inv.S = 3;
   }
+  // an inversion: alone, or (for the rules that refuse it) beside one other part
+  StepMode inv_mode(int with = 0) const {
+    StepMode m;
+    m.invert = &inv;
+    if (with == 1) m.ddim = &ddim;
+    if (with == 2) m.dpm = &dpm;
+    if (with == 3) m.known = &known;
+    if (with == 4) m.gd = &gd;
+    if (with == 5) m.comp = &comp;
+    if (with == 6) m.geom = &geom;
+    if (with == 7) m.perturb = &perturb;
+    return m;
+  }
+  GraphKey inv_key(int table_gen = 1) const { return make_graph_key(a, inv_mode(), table_gen); }
   GraphKey key(bool use_ddim, bool use_dpm, bool use_known = false, bool use_gd = false, int table_gen = 1,
                bool use_comp = false, bool use_geom = false, bool use_perturb = false) const {
     return make_graph_key(a, StepMode{use_ddim ? &ddim : nullptr, use_dpm ? &dpm : nullptr,
@@ -276,6 +299,73 @@ int main() {
           Inputs(0).key(ddim, dpm, true, true, 1, true, false, true));
   }
   CHECK(StepMode{}.perturb == nullptr);
+  // 12. DDIM inversion: a rule of its own with a key of its own, member by member, src included; neither the
+  // DDPM tables, T nor the seed are in it; it combines with no other part
+  {
+    const GraphKey inverted = Inputs().inv_key();
+    CHECK(Inputs().inv_mode().rule() == Rule::INVERT);
+    CHECK(StepMode{}.invert == nullptr && StepMode{}.invert_conflict() == nullptr);
+    CHECK(!(inverted == Inputs().key(false, false)) && !(inverted == Inputs().key(true, false)) &&
+          !(inverted == Inputs().key(false, true)));
+    auto moved_i = [&](auto&& edit) {
+      Inputs in;
+      edit(in);
+      return !(in.inv_key() == inverted);
+    };
+    CHECK(moved_i([](Inputs& in) { in.inv.t_map = imem + 5; }));
+    CHECK(moved_i([](Inputs& in) { in.inv.i_x = mem + 40; }));
+    CHECK(moved_i([](Inputs& in) { in.inv.i_e = mem + 40; }));
+    CHECK(moved_i([](Inputs& in) { in.inv.adv = amem + 1; }));
+    CHECK(moved_i([](Inputs& in) { in.inv.src = mem + 40; }));
+    CHECK(moved_i([](Inputs& in) { in.inv.S = 4; }));
+    CHECK(!moved_i([](Inputs& in) { in.a.c1 = mem + 40; }));
+    CHECK(!moved_i([](Inputs& in) { in.a.c2 = nullptr; }));
+    CHECK(!moved_i([](Inputs& in) { in.a.sd = mem + 40; }));
+    CHECK(!moved_i([](Inputs& in) { in.a.T = 0; }));
+    CHECK(!moved_i([](Inputs& in) { in.a.seed = 8; }));
+    CHECK(moved_i([](Inputs& in) { in.a.x_in = in.a.x_out = mem + 40; }));  // (what it still reads stays in)
+    CHECK(moved_i([](Inputs& in) { in.a.guidance = 0.f; }));
+    CHECK(moved_i([](Inputs& in) { in.a.y = imem + 5; }));
+    CHECK(!(Inputs().inv_key(2) == inverted));
+    // the tables of a DDIM schedule at the same addresses are still another key: the member differs
+    {
+      Inputs in;
+      in.ddim.t_map = in.inv.t_map;
+      in.ddim.k_e = in.inv.i_x;
+      in.ddim.k_a = in.inv.i_e;
+      CHECK(!(in.key(true, false) == inverted));
+    }
+    // every other key holds zeros there, and the inversion key holds zeros in every other member
+    const dmx_invert_sched zero{};
+    for (int mode = 0; mode < 3; ++mode)
+      for (int kn = 0; kn < 2; ++kn)
+        for (int cp = 0; cp < 2; ++cp) {
+          const GraphKey k = Inputs(0xAA).key(mode == 1, mode == 2, kn != 0, true, 1, cp != 0, false, cp != 0);
+          CHECK(std::memcmp(&k.inv, &zero, sizeof(zero)) == 0);
+        }
+    const dmx_ddim_sched zd{};
+    const dmx_dpm_sched zp{};
+    const dmx_known_sched zk{};
+    CHECK(std::memcmp(&inverted.sched, &zd, sizeof(zd)) == 0 && std::memcmp(&inverted.dpm, &zp, sizeof(zp)) == 0 &&
+          std::memcmp(&inverted.known, &zk, sizeof(zk)) == 0);
+    // its padding stays out of the key
+    CHECK(Inputs(0xAA).inv_key() == Inputs(0).inv_key());
+    // alone, or beside a guidance struct with rescale 0, it is legal; beside anything else it is refused with a message
+    CHECK(Inputs().inv_mode().invert_conflict() == nullptr);
+    CHECK(Inputs().inv_mode(4).invert_conflict() == nullptr);
+    CHECK(make_graph_key(Inputs().a, Inputs().inv_mode(4), 1) == inverted);
+    const int others[6] = {1, 2, 3, 5, 6, 7};
+    for (int with : others) {
+      const Inputs in;
+      const char* why = in.inv_mode(with).invert_conflict();
+      CHECK(why != nullptr && std::strlen(why) > 0);
+    }
+    {
+      Inputs in;
+      in.gd.rescale = 0.5f;
+      CHECK(in.inv_mode(4).invert_conflict() != nullptr);
+    }
+  }
   if (fails == 0) std::puts("step_mode_check: ok");
   return fails == 0 ? 0 : 1;
 }
