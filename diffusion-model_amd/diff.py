@@ -134,6 +134,8 @@ class _SamplerPlan:
     perturb: Optional[Tuple[int, int]] = None  # perturbed-attention guidance: (blocks, branches) bit masks of compose
     rows: Optional[Tuple[int, int]] = None  # a shard: the rows [s, e) of the global batch
     x_start: Optional[torch.Tensor] = None  # the latent the loop starts from
+    cache: int = 1                         # feature caching: a refresh step every cache-th position of a guard
+                                           # chunk, reuse steps between (1: every step is the plain step)
 
     def guided(self, i: int) -> bool:
         return self.run_g is True or (self.run_g is not None and self.run_g[0] <= i <= self.run_g[1])
@@ -154,11 +156,14 @@ class _SamplerPlan:
             return x.detach().to(torch.float32).contiguous().clone()
         return torch.empty_like(x, dtype=torch.float32) if self.rule == "dpm" else None
 
-    def kwargs(self, guided: bool, hist=None, seed=None, use_graph=None) -> dict:
+    def kwargs(self, guided: bool, hist=None, seed=None, use_graph=None, phase: int = 0) -> dict:
         """The keywords of NativeModel.step (seed: a drawn Philox seed, else none) and, with
         use_graph given, NativeModel.sample_loop for a guided or unguided step: a feature that
-        is off passes no keyword."""
+        is off passes no keyword.  phase: how far into its guard chunk the step (the loop's first
+        step) stands — read by a cached plan alone."""
         kw = {}
+        if self.cache > 1:
+            kw["cache"] = (self.cache, int(phase))
         if seed is not None:
             kw["seed"] = seed
         if use_graph is not None:
@@ -726,6 +731,38 @@ class Diffuser:
         K = y_rows.shape[0] - 1
         return (y_rows.contiguous(), v_rows.contiguous(), m_rows.contiguous(), w.contiguous()), (blocks, 1 << K)
 
+    # ---- feature caching: the deep U-Net feature is refreshed every N-th step and reused between ----
+    @staticmethod
+    def _cache_args(cache_interval, model=None, composed=False, pag=False, geom=False, guidance_interval=None,
+                    unguided_ddpm=False):
+        """Argument rules of the samplers' cache_interval keyword -> N (1: the call without the keyword,
+        which None and 1 both are).  N > 1 needs a dmx network and takes none of: composed guidance
+        (`composed`: base / also / a per-sample guidance_scale), pag_scale (`pag`), geom_scale (`geom`), a
+        guidance_interval (the rows of a step change between its segments), the ddpm sampler with
+        guidance_scale 0 (`unguided_ddpm`: that loop mirrors the reference's unguided branch through the
+        module's forward, which cannot be cut short).  Every violation raises
+        ValueError naming both parties; nothing here touches the model or a GPU, and nothing is drawn."""
+        if cache_interval is None:
+            return 1
+        if isinstance(cache_interval, bool) or not isinstance(cache_interval, int) or cache_interval < 1:
+            raise ValueError(f"cache_interval must be None or an int >= 1 (got {cache_interval!r})")
+        if cache_interval == 1:
+            return 1
+        if composed:
+            raise ValueError("cache_interval takes no composed guidance (base / also / per-sample guidance_scale)")
+        if pag:
+            raise ValueError("cache_interval takes no pag_scale")
+        if geom:
+            raise ValueError("cache_interval takes no geom_scale")
+        if guidance_interval is not None:
+            raise ValueError("cache_interval takes no guidance_interval (the rows of a step change between segments)")
+        if unguided_ddpm:
+            raise ValueError('cache_interval with sampler="ddpm" needs guidance_scale > 0 (its unguided loop calls '
+                             'the module\'s forward as the reference does); use a strided sampler for guidance_scale 0')
+        if model is not None and _native_kind(model) == 0:
+            raise ValueError("cache_interval needs a dmx network: a foreign model's forward cannot be cut short")
+        return int(cache_interval)
+
     @staticmethod
     def _eps(model, x, t, y, null_label, cond_vals, cond_mask, g, rescale, compose):
         """A foreign model's prediction as the operands (eu, ec, g) of an update.  compose: one call per
@@ -863,7 +900,8 @@ class Diffuser:
                             scale=float(guidance_scale) if guidance_scale else 0.0)
         return self._step(model, x, t, plan, True, y, null_label, cond_vals, cond_mask)
 
-    def _step(self, model, x, pos, plan, guided, y=None, null_label=0, cond_vals=None, cond_mask=None, hist=None):
+    def _step(self, model, x, pos, plan, guided, y=None, null_label=0, cond_vals=None, cond_mask=None, hist=None,
+              phase=0):
         """One step of plan.rule at `pos` ((B,): timesteps for ddpm, positions of plan.sched otherwise —
         countdown rows of an inversion, whose `hist` is its source latent)
         after the public entries' range checks — the samplers' loops build pos from a host-known
@@ -875,7 +913,9 @@ class Diffuser:
         A dmx network on the GPU runs it as one native step, known-region blend included; any other
         model is called like the reference and the update and the blend run natively after it.
         The native step draws its noise (host mode) or seed (device mode) before the step, the
-        foreign one after the model's forwards; a rule that draws nothing consumes neither."""
+        foreign one after the model's forwards; a rule that draws nothing consumes neither.
+        phase: the step's offset in its guard chunk, which decides whether a cached plan's step refreshes
+        the feature or reuses it; only the native step can do either."""
         rule, compose = plan.rule, plan.compose
         g = plan.scale if guided and compose is None and y is not None and plan.scale > 0 else 0.0
         mirror = rule == "ddpm" and guided and compose is None and g == 0.0
@@ -896,8 +936,11 @@ class Diffuser:
                 use = cond_vals is not None and cond_mask is not None
                 model.native().step(x_in, out, pos.to(x.device), None if y is None else y.to(x.device), null_label,
                                     cond_vals if use else None, cond_mask if use else None, g, plan.tables, noise,
-                                    **plan.kwargs(g > 0, hist, seed=seed))
+                                    **plan.kwargs(g > 0, hist, seed=seed, phase=phase))
                 return out
+            if plan.cache > 1:
+                raise ValueError("cache_interval needs a dmx network on the GPU: only the native step can reuse "
+                                 "the cached feature")
             if plan.perturb is not None:
                 raise ValueError("pag_scale needs a dmx network on the GPU: only the native step can perturb attention")
             t = pos if rule == "ddpm" else plan.sched[0][pos - 1]
@@ -1191,6 +1234,7 @@ class Diffuser:
         pag_scale=0.0,
         pag_blocks=("sa3",),
         start_latent: Optional[torch.Tensor] = None,
+        cache_interval: Optional[int] = None,
     ):
         """Class + numeric-condition latent sampler (diff.py:174-369).
 
@@ -1260,7 +1304,15 @@ class Diffuser:
         inverted latent, under the same or an edited condition.  It excludes init_latent and mask;
         z_shape defaults to x's shape.  Draw order: no x_T draw is made and, with z_shape None, no encode
         draw either; ddim with eta > 0 still draws once per step, everything else draws nothing.
-        Without the keyword the call is what it is today, `strength` without init_latent an error."""
+        Without the keyword the call is what it is today, `strength` without init_latent an error.
+
+        cache_interval = N (an int >= 1; a dmx network), with any sampler, guidance_rescale, init_latent / mask /
+        strength and start_latent: feature caching (DeepCache, Ma et al. 2024).  Every N-th step runs the whole
+        network and keeps its deepest up-path feature (sa5's output); the N - 1 steps between run only inc,
+        up3, sa6 and the head on the kept feature.  The count restarts with every guard chunk (GUARD_CHUNK
+        positions), so each chunk begins with a full step.  An approximation, off by default: None and 1 are the
+        call without the keyword.  It takes no composed guidance, pag_scale, geom_scale or guidance_interval,
+        and the draw order is unchanged."""
         mode = self._sampler_mode(sampler, steps, eta, spacing, self.num_timesteps)
         composed = (not (isinstance(base, str) and base == "null")) or bool(also) or self._per_sample(guidance_scale)
         interval, phi = self._guidance_args(None if composed else guidance_scale,
@@ -1282,6 +1334,8 @@ class Diffuser:
                              guidance_interval, guidance_rescale, geom_scale, null_label, device)
         if pag is not None:
             compose = pag[0]
+        cache = self._cache_args(cache_interval, model, composed, pag is not None, geom is not None, guidance_interval,
+                                 mode is None and not composed and not float(guidance_scale or 0) > 0)
 
         known, entry = None, {}
         if start_latent is not None:
@@ -1306,7 +1360,8 @@ class Diffuser:
         x = self._run_cond_loop(model, x, y, vals, msk, guidance_scale, null_label, progress, mode,
                                 known=known[:3] if known is not None else None, interval=interval, rescale=phi,
                                 compose=compose, **({} if geom is None else dict(geom=geom)),
-                                **({} if pag is None else dict(perturb=pag[1])), **entry)
+                                **({} if pag is None else dict(perturb=pag[1])), **entry,
+                                **({} if cache == 1 else dict(cache=cache)))
         if vae is None:
             return x
         if torch.cuda.is_available():
@@ -1355,7 +1410,7 @@ class Diffuser:
         return x.to(torch.float32)
 
     def _plan(self, x, mode, guidance_scale, known=None, interval=None, rescale=0.0, compose=None,
-              rows=None, geom=None, perturb=None, start=None) -> _SamplerPlan:
+              rows=None, geom=None, perturb=None, start=None, cache=1) -> _SamplerPlan:
         """The plan of a sampling call whose x_T draw is x, on x's device.
         mode: _sampler_mode's result.  interval, rescale: _guidance_args' (t_lo, t_hi) or None and phi.
         compose: _compose_args' tables or None; a composed plan has no scale, interval or rescale.
@@ -1372,13 +1427,24 @@ class Diffuser:
         start = p0 (a strided rule, no `known`): x is no draw but the latent the loop starts from, as it
         is, at position p0 (sample_latent_cond's start_latent).
         mode ("invert", S, strength, R): the plan of invert_latent_cond — x is z0, the schedule is
-        invert_tables' and the counter walks its N rows down; it takes none of the other parts."""
+        invert_tables' and the counter walks its N rows down; it takes none of the other parts.
+        cache = N (_cache_args): feature caching with a refresh every N-th position of a guard chunk; it
+        takes no composition, geometry or perturbed-attention guidance, guidance interval or inversion."""
         dev = x.device
         rule = "ddpm" if mode is None else mode[0]
         tau = self._mode_timesteps(mode)
         cut = slice(None) if rows is None else slice(*rows)
         plan = _SamplerPlan(rule, start=len(tau), draws=rule == "ddpm" or (rule == "ddim" and mode[2] > 0),
                             rows=rows, x_start=x)
+        if isinstance(cache, bool) or cache != 1:
+            if isinstance(cache, bool) or not isinstance(cache, int) or cache < 1:
+                raise ValueError(f"cache must be an int >= 1 (got {cache!r})")
+            for nm, v in (("composition", compose), ("geometry guidance", geom),
+                          ("perturbed-attention guidance", perturb), ("guidance interval", interval),
+                          ("inversion", True if rule == "invert" else None)):
+                if v is not None:
+                    raise ValueError(f"a cached plan (cache_interval > 1) takes no {nm}")
+            plan.cache = cache
         if perturb is not None:
             if compose is None:
                 raise ValueError("perturb belongs to the compose tables of _pag_args")
@@ -1442,16 +1508,18 @@ class Diffuser:
         return run
 
     def _run_cond_loop(self, model, x, y, vals, msk, guidance_scale, null_label, progress, mode=None, known=None,
-                       interval=None, rescale=0.0, compose=None, geom=None, perturb=None, start=None):
+                       interval=None, rescale=0.0, compose=None, geom=None, perturb=None, start=None, cache=1):
         """The T loop (diff.py:328-344) over the call's plan (_plan), range-guarded in chunks
         (_guarded_loop): the counter walks timesteps, or the positions of a strided schedule, down
         from plan.start, and a replayed chunk restarts from the x and the solver history it started
         with.  A dmx network with guidance (or a composed call) in device-noise mode runs whole chunks
         on the device (_device_chunks); every other case steps on the host (_step).  An inversion
         (mode "invert") draws nothing and takes the device loop in either noise mode; its source latent
-        travels in the history slot, so a replayed chunk restarts from its x and its src."""
+        travels in the history slot, so a replayed chunk restarts from its x and its src.
+        cache = N > 1 (_cache_args): every guard chunk starts with a refresh step and refreshes every N-th
+        step after it — the device loop passes phase 0 per chunk call, the host loop the step's offset."""
         plan = self._plan(x, mode, guidance_scale, known, interval, rescale, compose, geom=geom, perturb=perturb,
-                          **({} if start is None else dict(start=start)))
+                          **({} if start is None else dict(start=start)), **({} if cache == 1 else dict(cache=cache)))
         x = plan.x_start
         hist = plan.new_hist(x)
         guard = self._guard_target(model, x)
@@ -1467,7 +1535,8 @@ class Diffuser:
             def step_chunk(i_from, i_to, x):
                 for i in range(i_from, i_to, -1):  # i in [1, T]: the public steps' asserts hold by construction
                     t = torch.full((x.shape[0],), i, device=x.device, dtype=torch.long)
-                    x = self._step(model, x, t, plan, plan.guided(i), y, null_label, vals, msk, hist)
+                    x = self._step(model, x, t, plan, plan.guided(i), y, null_label, vals, msk, hist,
+                                   **({} if plan.cache == 1 else dict(phase=i_from - i)))
                     if bar is not None:
                         bar.update(1)
                 return x

@@ -92,6 +92,12 @@ class Perturb(ctypes.Structure):
     _fields_ = [("blocks", ctypes.c_uint32), ("branches", ctypes.c_uint32)]
 
 
+class Cache(ctypes.Structure):
+    """dmx_cache (include/dmx.h): the refresh interval of a feature-cached step or loop and the offset of its
+    first step in the cycle."""
+    _fields_ = [("interval", ctypes.c_int), ("phase", ctypes.c_int)]
+
+
 class GeomGuide(ctypes.Structure):
     """dmx_geom_guide (include/dmx.h): per-sample scales and the per-position sqrt(1 - ab) table of geometry guidance."""
     _fields_ = [("scale", ctypes.c_void_p), ("sig", ctypes.c_void_p), ("S", ctypes.c_int)]
@@ -208,6 +214,12 @@ SIGNATURES = [
                                   ctypes.POINTER(KnownSched), ctypes.POINTER(GeomGuide), _I, _I, _P]),
     ("dmx_geom_mix", _I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     ("dmx_geom_seed", _I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    ("dmx_step_cached", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched), ctypes.POINTER(DpmSched),
+                             ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance), ctypes.POINTER(Cache), _P]),
+    ("dmx_sample_loop_cached", _I, [_P, ctypes.POINTER(StepArgs), ctypes.POINTER(DdimSched),
+                                    ctypes.POINTER(DpmSched), ctypes.POINTER(KnownSched), ctypes.POINTER(Guidance),
+                                    ctypes.POINTER(Cache), _I, _I, _P]),
+    ("dmx_model_cached_features", _I, [_P, ctypes.POINTER(_I64), _P, _P]),
     ("dmx_model_graph_captures", _I64, [_P]),
     ("dmx_vae_decode", _I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_latent_frames_u8", _I, [_P, _P, _I, _I, _I, _I, _P]),

@@ -321,6 +321,17 @@ struct dmx_model {
   int prec = 1;  // 0: fp32 MFMA (exact fp32 products), 1: fp16 hi/lo x3 split MFMA, 2: fp16 (config 4)
   int* range_flag = nullptr;  // device int: an output went non-finite (kernels.h flag_nonfinite)
   int64_t* t_scratch = nullptr;  // device int64: the 8-step graph's second t scalar (own allocation)
+  // Feature caching (include/dmx.h dmx_cache): the deep feature D — sa5's output, (rows, h/2, w/2, C) — of the
+  // last refresh step, in an allocation of its own (never in ws: the arena is rewound by every step), and
+  // what it belongs to.  Captured graphs hold the pointer: reallocating it drops them all (ensure_dcache).
+  float* dcache = nullptr;
+  size_t dcache_cap = 0;  // floats
+  struct DTag {
+    bool valid = false;
+    int rows = 0, n = 0, h = 0, w = 0, prec = 0;
+    int64_t gen = 0;
+  } dtag;
+  int64_t weights_gen = 0;  // bumped by dmx_model_finalize / dmx_model_refresh
 
   std::vector<std::pair<std::string, std::pair<const float*, size_t>>> taps;
   // Weight packing replay (dmx_model_refresh): every device-side repack / copy of the caller's
@@ -1599,11 +1610,13 @@ static bool tok_qkv_wide(const Run& R, int N, int L) { return cdiv(dec_n(R, N) *
 static TokW tokw(const ConvW& c) { return TokW{c.Bh, c.Bl, c.bias, c.inv_scale, c.kpad, c.Fh, c.Fl}; }
 
 // Fused token kernels (tokmlp.h) for the split-precision modes: TA -> attention core -> TB.
-static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt) {
+static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt,
+                               float* out_to) {
   const int C = a.c, M = N * H * W, L = H * W;
   float* qkv = R.ws.get<float>((size_t)M * 3 * C);
   float* ao = R.ws.get<float>((size_t)M * C);
-  float* out = R.ws.get<float>((size_t)M * C);
+  float* out_ws = R.ws.get<float>((size_t)M * C);  // (asked for either way: the arena's plan does not depend on out_to)
+  float* out = out_to != nullptr ? out_to : out_ws;
   const int x1 = R.m->prec == 2 ? 1 : 0;
   if (!R.plan) {
     TokParams tp{};
@@ -1676,19 +1689,23 @@ static float* attn_block_fused(Run& R, const AttnW& a, const float* x, int N, in
 }
 
 // AttenionBlock (models/unet_cond.py:32-52) on NHWC == (N, L, C) tokens.  pt: the block is perturbed
-// (attention_rows); the QKV and the out / FF launches run over all N rows either way.
-static float* attn_block(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt = nullptr) {
+// (attention_rows); the QKV and the out / FF launches run over all N rows either way.  out_to non-null:
+// the block's last launch stores its output there (M * C floats outside the arena: the feature cache of a
+// refresh step) and that is what is returned; the launches and the arena are those of out_to == null.
+static float* attn_block(Run& R, const AttnW& a, const float* x, int N, int H, int W, const Perturb* pt = nullptr,
+                         float* out_to = nullptr) {
   const int C = a.c, M = N * H * W, L = H * W;
   if (R.m->prec >= 1 && (C == 64 || C == 128 || C == 256) && a.qkv.kpad == C &&
       a.o.kpad == C && a.f1.kpad == C && a.f2.kpad == C)
-    return attn_block_fused(R, a, x, N, H, W, pt);
+    return attn_block_fused(R, a, x, N, H, W, pt, out_to);
   float* xl = R.ws.get<float>((size_t)M * C);
   float* qkv = R.ws.get<float>((size_t)M * 3 * C);
   float* ao = R.ws.get<float>((size_t)M * C);
   float* av = R.ws.get<float>((size_t)M * C);
   float* al = R.ws.get<float>((size_t)M * C);
   float* f = R.ws.get<float>((size_t)M * C);
-  float* out = R.ws.get<float>((size_t)M * C);
+  float* out_ws = R.ws.get<float>((size_t)M * C);
+  float* out = out_to != nullptr ? out_to : out_ws;
   layernorm(R, x, xl, a.l1w, a.l1b, M, C);
   gemm(R, plain_src(xl, C), SRC_PLAIN, N, H, W, a.qkv, EPI_BIAS, qkv, nullptr, nullptr, 1);
   attention_rows(R, qkv, ao, N, L, C, pt);
@@ -1716,6 +1733,11 @@ struct FwdIn {
   const int64_t* t_map = nullptr;  // strided sampling: t holds positions in [1, n_pos] and the
   int n_pos = 0;                   // timestep is t_map[position - 1] (null: t holds timesteps)
   Perturb perturb;                 // perturbed-attention guidance: blocks and rows (default: none)
+  // Feature caching (include/dmx.h dmx_cache; the values of StepMode::Kind): 1 = a refresh step, sa5 stores
+  // its output in dcache; 2 = a reuse step, dcache stands for sa5's output and nothing between inc and up3
+  // is launched.  0: no request.
+  int cache = 0;
+  float* dcache = nullptr;
 };
 
 // UnetCond trunk (models/unet_cond_geom.py:52-76): returns the (N,H,W,64) feature
@@ -1786,7 +1808,19 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
   int sh[3], sw[3], sc[3];
   const float* cur = x1;
   int ch = H, cw = W, cc = 64;
-  for (int i = 0; i < 3; ++i) {
+  const bool reuse = in.cache == 2;
+  if (in.cache != 0 && in.dcache == nullptr) throw Error(DMX_E_INTERNAL, "cached step without a feature buffer");
+  if (reuse) {  // the stored deep feature stands where down1 .. sa5 would leave theirs: up3 is next
+    skips[0] = x1;
+    sh[0] = H;
+    sw[0] = W;
+    sc[0] = 64;
+    cur = in.dcache;
+    ch = H / 2;
+    cw = W / 2;
+    cc = m->up[1].cout;
+  }
+  for (int i = 0; i < (reuse ? 0 : 3); ++i) {
     skips[i] = cur;
     sh[i] = ch;
     sw[i] = cw;
@@ -1826,7 +1860,7 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
   }
   // bottleneck
   const _Float16 *cur_h = nullptr, *cur_l = nullptr;  // planes of `cur` (between bottleneck blocks)
-  for (int i = 0; i < m->nbot; ++i) {
+  for (int i = 0; i < (reuse ? 0 : m->nbot); ++i) {
     R.layer = "bot" + std::to_string(i + 1);
     bool hp = false;
     const bool nxt = i + 1 < m->nbot &&  // the last one feeds the upsample
@@ -1838,7 +1872,7 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     cur_l = hp ? cur_h + (size_t)N * ch * cw * cc : nullptr;
   }
   // up path
-  for (int i = 0; i < 3; ++i) {
+  for (int i = reuse ? 2 : 0; i < 3; ++i) {
     const int si = 2 - i;  // skip x3, x2, x1
     SrcDesc u = plain_src(skips[si], sc[si] + cc);
     u.C0 = sc[si];
@@ -1879,7 +1913,8 @@ static float* unet_trunk(Run& R, const FwdIn& in, int N, int H, int W) {
     cw = sw[si];
     cc = m->up[i].cout;
     R.layer = "sa" + std::to_string(4 + i);
-    cur = attn_block(R, m->sa[3 + i], h1, N, ch, cw, perturbed(3 + i));
+    float* keep = in.cache == 1 && i == 1 ? in.dcache : nullptr;  // a refresh step: sa5 stores the deep feature
+    cur = attn_block(R, m->sa[3 + i], h1, N, ch, cw, perturbed(3 + i), keep);
   }
   return const_cast<float*>(cur);
 }
@@ -2254,6 +2289,7 @@ int dmx_model_destroy(dmx_model* m) {
     if (m->split_table) (void)hipFree(m->split_table);
     for (const Workspace* w : m->workspaces())
       if (w->mem) (void)hipFree(w->mem);
+    if (m->dcache) (void)hipFree(m->dcache);
     delete m->tape;
     delete m->vtape;
     delete m;
@@ -2279,6 +2315,7 @@ int dmx_model_set_tensor(dmx_model* m, const char* name, const float* dev_ptr, c
 int dmx_model_finalize(dmx_model* m, void* stream) {
   return guarded([&] {
     REQUIRE(m, "null model");
+    ++m->weights_gen;  // (a cached deep feature belongs to the weights it was computed with)
     finalize_model(m, (hipStream_t)stream);
   });
 }
@@ -2293,6 +2330,7 @@ int64_t dmx_model_workspace_bytes(const dmx_model* m) {
 int dmx_model_refresh(dmx_model* m, void* stream) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
+    ++m->weights_gen;
     refresh_model(m, (hipStream_t)stream);
   });
 }
@@ -2557,6 +2595,43 @@ int dmx_step_perturbed(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sche
                        const dmx_perturb* perturb, void* stream) {
   return guarded([&] {
     sample_step(m, a, StepMode{ddim, dpm, known, guidance, compose, nullptr, perturb}, (hipStream_t)stream);
+  });
+}
+
+int dmx_step_cached(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                    const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_cache* cache,
+                    void* stream) {
+  return guarded([&] {
+    StepMode mode{ddim, dpm, known, guidance};
+    mode.cache = cache;
+    sample_step(m, a, mode, (hipStream_t)stream);
+  });
+}
+
+int dmx_sample_loop_cached(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                           const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                           const dmx_cache* cache, int steps, int use_graph, void* stream) {
+  return guarded([&] {
+    StepMode mode{ddim, dpm, known, guidance};
+    mode.cache = cache;
+    sample_loop(m, a, mode, steps, use_graph, (hipStream_t)stream);
+  });
+}
+
+int dmx_model_cached_features(dmx_model* m, int64_t* shape_out, float* dst, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr && shape_out != nullptr, "null argument");
+    const dmx_model::DTag& g = m->dtag;
+    const bool have = g.valid && m->dcache != nullptr;
+    shape_out[0] = have ? g.rows : 0;
+    shape_out[1] = have ? g.h / 2 : 0;
+    shape_out[2] = have ? g.w / 2 : 0;
+    shape_out[3] = have ? m->up[1].cout : 0;
+    if (!have || dst == nullptr) return;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t el = (size_t)g.rows * (g.h / 2) * (g.w / 2) * m->up[1].cout;
+    HIPCHK(hipMemcpyAsync(dst, m->dcache, el * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
   });
 }
 

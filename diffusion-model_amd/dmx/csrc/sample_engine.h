@@ -105,8 +105,11 @@ struct GraphStep {
 // training forward of the B conditional rows, the loss seed and the data-only backward
 // (train_engine.h) in the same arena — nothing is allocated outside the plan, so the step captures
 // like any other — then materialises the CFG eps as the rescaled step does, mixes the input
-// gradient into it and runs the rule's tail on the mixed eps.
-static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, GraphStep gs = {}) {
+// gradient into it and runs the rule's tail on the mixed eps.  kind: the step's part in a
+// feature-cached call (StepMode::cache_kind) — the trunk stores or reads the model's deep feature
+// (unet_trunk); the head and the tail are the same either way.
+static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, GraphStep gs = {},
+                      StepMode::Kind kind = StepMode::PLAIN) {
   dmx_model* m = R.m;
   const dmx_compose* comp = mode.comp;
   const bool cfg = comp == nullptr && m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr;
@@ -128,6 +131,10 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   }
   in.t_next = gs.t_next;
   in.cond_cached = gs.cond_cached;
+  if (kind != StepMode::PLAIN) {
+    in.cache = (int)kind;
+    in.dcache = m->dcache;
+  }
   if (rule != Rule::DDPM) {
     in.t_map = mode.t_map();
     in.n_pos = mode.positions(a);
@@ -306,6 +313,8 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   REQUIRE(a != nullptr, "null step args");
   const bool cfg = m->kind != DMX_UNET && a->guidance > 0.f && a->y != nullptr;
   if (const char* why = mode.invert_conflict()) throw Error(DMX_E_ARG, why);
+  if (const char* why = mode.cache_conflict()) throw Error(DMX_E_ARG, why);
+  if (mode.cached()) REQUIRE(mode.cache->phase >= 0, "cache phase must be >= 0");
   if (mode.comp != nullptr) {
     const dmx_compose& c = *mode.comp;
     REQUIRE(c.K >= 1 && c.K <= DMX_COMPOSE_MAX, "compose K must lie in [1, DMX_COMPOSE_MAX]");
@@ -382,13 +391,75 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
 }
 
 // ---------------------------------------------------------------------------
+// Feature caching: the model's deep-feature buffer and what it belongs to
+// ---------------------------------------------------------------------------
+// Rows of the trunk in a (validated, uncomposed) step: 2n under CFG batching, else n.
+static int trunk_rows(const dmx_model* m, const dmx_step_args& a) {
+  return m->kind != DMX_UNET && a.guidance > 0.f && a.y != nullptr ? 2 * a.n : a.n;
+}
+
+// Room for the deep feature of a step with these args, before a refresh step is planned.  Growing
+// an existing buffer waits for the stream's earlier work, and drops every captured graph and the
+// stored feature: the graphs of cached loops hold the old pointer.  The first allocation drops
+// nothing — no graph can hold a pointer that did not exist.
+static void ensure_dcache(dmx_model* m, const dmx_step_args& a, hipStream_t st) {
+  const size_t el = (size_t)trunk_rows(m, a) * (a.h / 2) * (a.w / 2) * m->up[1].cout;
+  if (el <= m->dcache_cap) return;
+  if (m->dcache != nullptr) {
+    HIPCHK(hipStreamSynchronize(st));
+    m->owned_bytes.erase(reinterpret_cast<const char*>(m->dcache));
+    HIPCHK(hipFree(m->dcache));
+    drop_graph(m);
+  }
+  m->dcache = nullptr;
+  m->dcache_cap = 0;
+  m->dtag.valid = false;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->dcache), el * sizeof(float)));
+  m->dcache_cap = el;
+  m->owned_bytes[reinterpret_cast<const char*>(m->dcache)] = el * sizeof(float);  // DMX_CHECK ranges
+}
+
+// A reuse step with these args may read the stored feature; else DMX_E_STATE naming what differs.
+static void check_dcache(const dmx_model* m, const dmx_step_args& a) {
+  const dmx_model::DTag& g = m->dtag;
+  auto stale = [](const std::string& why) {
+    throw Error(DMX_E_STATE, "reuse step without a matching cached feature: " + why);
+  };
+  if (!g.valid || m->dcache == nullptr) stale("no refresh step has run (or its buffer was reallocated)");
+  if (g.gen != m->weights_gen) stale("the weights changed since the refresh step (finalize / refresh)");
+  if (g.prec != m->prec)
+    stale("the precision mode changed since the refresh step (" + std::to_string(g.prec) + " -> " +
+          std::to_string(m->prec) + ")");
+  if (g.h != a.h || g.w != a.w)
+    stale("the map size differs (" + std::to_string(g.h) + "x" + std::to_string(g.w) + " stored, " +
+          std::to_string(a.h) + "x" + std::to_string(a.w) + " asked)");
+  const int rows = trunk_rows(m, a);
+  if (g.n != a.n)
+    stale("the batch differs (" + std::to_string(g.n) + " samples stored, " + std::to_string(a.n) + " asked)");
+  if (g.rows != rows)
+    stale("the step kind differs (" + std::to_string(g.rows) + " rows stored, " + std::to_string(rows) +
+          " asked: CFG and unguided steps do not share a feature)");
+}
+
+static void tag_dcache(dmx_model* m, const dmx_step_args& a) {
+  m->dtag = dmx_model::DTag{true, trunk_rows(m, a), a.n, a.h, a.w, m->prec, m->weights_gen};
+}
+
+// ---------------------------------------------------------------------------
 // The step and the loop behind the dmx_step* / dmx_sample_loop* entries
 // ---------------------------------------------------------------------------
 static void sample_step(dmx_model* m, const dmx_step_args* a, const StepMode& mode, hipStream_t st) {
   validate(m, a, mode, false);
+  const StepMode::Kind kind = mode.cache_kind(0);
+  if (kind == StepMode::REUSE) check_dcache(m, *a);  // (before anything is launched)
   ensure_planes(m, st);
   if (mode.geom != nullptr) ensure_train(m, st);
-  run_planned(m, st, [&](Run& R) { step_body(R, *a, mode); });
+  if (kind == StepMode::REFRESH) {
+    ensure_dcache(m, *a, st);
+    m->dtag.valid = false;  // until the step below has been enqueued
+  }
+  run_planned(m, st, [&](Run& R) { step_body(R, *a, mode, {}, kind); });
+  if (kind == StepMode::REFRESH) tag_dcache(m, *a);
 }
 
 // Capture what `body` launches on st into *graph and instantiate it as *exec (both owned by a graph
@@ -415,6 +486,72 @@ static void capture(dmx_model* m, hipStream_t st, F&& body, hipGraph_t* graph, h
 
 static constexpr int kGraphSteps = 8;
 
+// The loop of a feature-cached call (validated, planes ensured): step k is a refresh or a reuse step
+// (StepMode::cache_kind).  Graph replay keeps one slot per kind, each a one-step graph (step +
+// decrement; no 8-step graph: a refresh never repeats, and a run of reuse steps is at most
+// interval - 1 long), and launches them in the pattern.  The two kinds walk different arenas — a
+// reuse step allocates less — so neither graph can use the other's cond-MLP rows: every captured step
+// computes its own.  Both arenas are planned before either kind is captured: a capture that grew
+// the workspace would drop the slot captured just before it.
+static void cached_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mode, int steps, int use_graph,
+                        hipStream_t st) {
+  if (steps == 0) return;
+  int64_t* tdev = const_cast<int64_t*>(a->t);
+  bool need[3] = {false, false, false};
+  for (int k = 0; k < steps && !(need[StepMode::REFRESH] && need[StepMode::REUSE]); ++k)
+    need[mode.cache_kind(k)] = true;
+  if (mode.cache_kind(0) == StepMode::REUSE) check_dcache(m, *a);  // (later reuse steps follow a refresh of this call)
+  if (need[StepMode::REFRESH]) {
+    ensure_dcache(m, *a, st);
+    m->dtag.valid = false;  // until every step has been enqueued
+  }
+  if (!use_graph) {
+    for (int i = 0; i < steps; ++i) {
+      const StepMode::Kind kind = mode.cache_kind(i);
+      run_planned(m, st, [&](Run& R) { step_body(R, *a, mode, {}, kind); });
+      decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
+      HIPCHK(hipGetLastError());
+    }
+  } else {
+    const StepMode::Kind kinds[2] = {StepMode::REFRESH, StepMode::REUSE};
+    GraphSlot* slot[3] = {nullptr, nullptr, nullptr};
+    auto find_all = [&] {
+      bool all = true;
+      for (StepMode::Kind kd : kinds) {
+        slot[kd] = need[kd] ? m->graphs.find(make_graph_key(*a, mode, m->ctx->table_gen, kd)) : nullptr;
+        all = all && (!need[kd] || slot[kd] != nullptr);
+      }
+      return all;
+    };
+    if (!find_all()) {
+      // the refresh kind's arena is the larger one (a reuse step runs a subset of its blocks); it is
+      // planned even where this call holds no refresh step, so a later one grows nothing (the buffer
+      // exists: this call refreshes, or check_dcache has accepted a stored feature)
+      for (StepMode::Kind kd : {StepMode::REUSE, StepMode::REFRESH})
+        plan_ws(m, st, m->ws, [&](Run& R) { step_body(R, *a, mode, {}, kd); });
+      find_all();  // (a grown arena dropped them all)
+      for (StepMode::Kind kd : kinds) {
+        if (!need[kd] || slot[kd] != nullptr) continue;
+        const size_t cap = m->ws.cap;
+        plan_ws(m, st, m->ws, [&](Run& R) { step_body(R, *a, mode, {}, kd); });
+        if (m->ws.cap != cap) throw Error(DMX_E_INTERNAL, "cached loop: the arena grew between its two captures");
+        GraphSlot* s = m->graphs.victim();  // free, or the least recently used: never the other kind's, found or
+        drop_slot(m, s);                    // claimed a moment ago
+        capture(m, st, [&] {
+          Run R{m, st, false, m->ws.a};
+          step_body(R, *a, mode, {}, kd);
+          decrement_t_kernel<<<1, 64, 0, st>>>(tdev);
+        }, &s->val.graph, &s->val.gexec);
+        m->graphs.claim(s, make_graph_key(*a, mode, m->ctx->table_gen, kd));
+        ++m->graph_captures;
+        slot[kd] = s;
+      }
+    }
+    for (int i = 0; i < steps; ++i) HIPCHK(hipGraphLaunch(slot[mode.cache_kind(i)]->val.gexec, st));
+  }
+  if (need[StepMode::REFRESH]) tag_dcache(m, *a);
+}
+
 // `steps` in-place steps.  The scalar a->t counts down by one per step in every mode — timesteps in
 // the DDPM loop, positions of the schedule in the strided ones.  The DPM history buffer is updated
 // in place by every step and the known-region blend reads the position scalar its tail read, so
@@ -427,6 +564,7 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
   ensure_planes(m, st);
   if (mode.geom != nullptr) ensure_train(m, st);  // (packs and synchronises: before any capture)
   int64_t* tdev = const_cast<int64_t*>(a->t);
+  if (mode.cached()) return cached_loop(m, a, mode, steps, use_graph, st);
   if (!use_graph) {
     for (int i = 0; i < steps; ++i) {
       run_planned(m, st, [&](Run& R) { step_body(R, *a, mode); });

@@ -23,6 +23,8 @@ struct StepMode {
                                            // branches of comp
   const dmx_invert_sched* invert = nullptr;  // DDIM inversion: a.t holds countdown positions over the rows; no
                                              // other part may be given (invert_conflict)
+  const dmx_cache* cache = nullptr;  // feature caching: refresh and reuse steps (cache_kind); interval <= 1 is
+                                     // no request at all, as rescale == 0 is no rescale
 
   Rule rule() const {
     return invert != nullptr ? Rule::INVERT : dpm != nullptr ? Rule::DPM : ddim != nullptr ? Rule::DDIM : Rule::DDPM;
@@ -38,6 +40,24 @@ struct StepMode {
     if (comp != nullptr) return "an inversion step takes no composition";
     if (geom != nullptr) return "an inversion step takes no geometry guidance";
     if (perturb != nullptr) return "an inversion step takes no perturbed-attention guidance";
+    return nullptr;
+  }
+  // Is the deep feature cached?  The one place that decides that interval <= 1 is no request.
+  bool cached() const { return cache != nullptr && cache->interval > 1; }
+  // The kind of step k of a call (k = 0: the one-step entry): PLAIN without a request, else REFRESH
+  // where (phase + k) % interval == 0 and REUSE elsewhere.
+  enum Kind { PLAIN = 0, REFRESH = 1, REUSE = 2 };
+  Kind cache_kind(int k) const {
+    if (!cached()) return PLAIN;
+    return (int)(((long long)cache->phase + k) % cache->interval) == 0 ? REFRESH : REUSE;
+  }
+  // The part a cached step cannot be combined with, as the message of its DMX_E_ARG; null: none.
+  const char* cache_conflict() const {
+    if (!cached()) return nullptr;
+    if (invert != nullptr) return "a cached step (cache interval > 1) takes no inversion";
+    if (comp != nullptr) return "a cached step (cache interval > 1) takes no composition";
+    if (perturb != nullptr) return "a cached step (cache interval > 1) takes no perturbed-attention guidance";
+    if (geom != nullptr) return "a cached step (cache interval > 1) takes no geometry guidance";
     return nullptr;
   }
   // phi of a rescaled CFG step, else 0.  The one place that decides that a guidance struct with
@@ -64,6 +84,7 @@ struct GraphKey {
   dmx_perturb perturb;   // perturbed loops: the block and branch bits (all zero otherwise)
   dmx_invert_sched inv;  // inversion loops: tables, source buffer and S = rows (all zero otherwise)
   int table_gen;  // dmx_ctx::table_gen at capture
+  int cache_kind; // cached loops: StepMode::REFRESH or REUSE, the kind of the one step the graph holds (zero otherwise)
   bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
 };
 
@@ -72,8 +93,12 @@ struct GraphKey {
 // S >= 1, which keeps the keys of the four rules, and known-region keys from plain ones, apart;
 // a validated composition has K >= 1, which keeps composed keys from plain ones; validated geometry
 // guidance has non-null tables and S >= 1, which keeps its keys from plain ones; a validated
-// perturbation has blocks >= 1, which keeps perturbed keys from composed ones.
-inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen) {
+// perturbation has blocks >= 1, which keeps perturbed keys from composed ones.  kind: the step kind of
+// a cached loop's graph (StepMode::cache_kind); neither the interval nor the phase enters the key, so
+// every pattern over the same loop replays the same two graphs, and kind PLAIN — every loop without a
+// cache request, interval <= 1 included — leaves the key what it was.
+inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int table_gen,
+                               StepMode::Kind kind = StepMode::PLAIN) {
   GraphKey key;
   std::memset(&key, 0, sizeof(key));
   std::memcpy(&key.a, &a, sizeof(dmx_step_args));
@@ -138,6 +163,7 @@ inline GraphKey make_graph_key(const dmx_step_args& a, const StepMode& mode, int
     key.perturb.branches = mode.perturb->branches;
   }
   key.table_gen = table_gen;
+  key.cache_kind = mode.cached() ? (int)kind : 0;
   return key;
 }
 

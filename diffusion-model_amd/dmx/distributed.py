@@ -173,7 +173,7 @@ class ShardedCondSampler:
                init_latent: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
                strength: Optional[float] = None, guidance_interval=None,
                guidance_rescale: float = 0.0, base="null", also=None, geom_scale=0.0, pag_scale=0.0,
-               pag_blocks=("sa3",)) -> Optional[torch.Tensor]:
+               pag_blocks=("sa3",), cache_interval: Optional[int] = None) -> Optional[torch.Tensor]:
         """Arguments as Diffuser.sample_latent_cond (diff.py:174-369); returns on rank 0 the
         (B, 8H, 8W, 3) uint8 images (decode and a VAE given) or the (B, C, H, W) latents,
         None on the other ranks.  Draw order per rank equals the single-process sampler's
@@ -218,7 +218,11 @@ class ShardedCondSampler:
         pag_scale / pag_blocks as in Diffuser.sample_latent_cond (perturbed-attention guidance), the scale
         a float or B floats for the global batch: the perturbed branch is one more row of the branch
         tables, sharded by columns with them; which blocks and branches are perturbed does not depend
-        on the shard."""
+        on the shard.
+
+        cache_interval as in Diffuser.sample_latent_cond (feature caching): which steps refresh follows from
+        the position and the guard chunk alone, so every rank refreshes at the same steps, and the cached
+        feature is shard-local (no collective)."""
         ws, rank = world()
         d = self.d
         mode = d._sampler_mode(sampler, steps, eta, spacing, d.num_timesteps)
@@ -241,6 +245,8 @@ class ShardedCondSampler:
                           guidance_interval, guidance_rescale, geom_scale, null_label, dev)
         if pag is not None:
             compose = pag[0]
+        cache = d._cache_args(cache_interval, self.model, composed, pag is not None, geom is not None,
+                              guidance_interval, mode is None and not composed and not float(guidance_scale or 0) > 0)
         s, e = shard_range(B, ws, rank)
         y = torch.tensor(y_list[s:e], device=dev, dtype=torch.long)
         v, m = vals[s:e].float().contiguous(), msk[s:e].float().contiguous()
@@ -258,7 +264,8 @@ class ShardedCondSampler:
         # the single-process sampler's plan for this shard's rows; x is its rows of e0
         plan = d._plan(x, mode, guidance_scale, known[:3] if known is not None else None, interval, phi, compose,
                        rows=(s, e), **({} if geom is None else dict(geom=geom)),
-                       **({} if pag is None else dict(perturb=pag[1])))
+                       **({} if pag is None else dict(perturb=pag[1])),
+                       **({} if cache == 1 else dict(cache=cache)))
         x = plan.x_start
         hist = plan.new_hist(x)  # shard-local
         if d.noise_source == "device":
@@ -285,7 +292,7 @@ class ShardedCondSampler:
                             tt = torch.full((xs.shape[0],), i, dtype=torch.long, device=dev)
                             guided = plan.guided(i)
                             nm.step(xs, out, tt, y, null_label, v, m, plan.guidance(guided), plan.tables, noise,
-                                    **plan.kwargs(guided, hist))
+                                    **plan.kwargs(guided, hist, phase=i_from - i))
                             xs = out
                 finally:
                     if pf is not None:

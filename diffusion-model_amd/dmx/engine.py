@@ -428,6 +428,41 @@ class NativeModel:
                              f"(got {tuple(perturb)!r})")
         return _lib.Perturb(blocks, branches)
 
+    @staticmethod
+    def _cache(cache, compose, geom, perturb, invert):
+        """The C view of cache = (interval, phase) (include/dmx.h dmx_cache), or None for no request: None
+        itself and every interval 1.  A cached step takes none of the parts named here."""
+        if cache is None:
+            return None
+        if not isinstance(cache, (tuple, list)) or len(cache) != 2:
+            raise ValueError("cache must be the pair (interval, phase)")
+        n, phase = cache
+        for v, nm, lo in ((n, "interval", 1), (phase, "phase", 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"cache {nm} must be an int >= {lo} (got {v!r})")
+        if n == 1:
+            return None
+        given = [nm for nm, v in (("compose", compose), ("geom", geom), ("perturb", perturb), ("invert", invert))
+                 if v is not None]
+        if given:
+            raise ValueError(f"a cached step (cache interval > 1) takes no {' / '.join(given)}")
+        return _lib.Cache(n, phase)
+
+    def cached_features(self) -> Optional[torch.Tensor]:
+        """A copy of the deep feature D the last refresh step of a cached call left in the model —
+        (rows, h/2, w/2, 64) fp32, rows = 2B in a CFG step (null half first), the output of sa5 — or
+        None while the model holds no valid one.  Read-only diagnostic: for tests, and for measuring
+        how far D drifts between the steps of a real checkpoint."""
+        shape = (ctypes.c_int64 * 4)()
+        with torch.cuda.device(self.device):
+            st = ctypes.c_void_p(_stream(self.device))
+            check(self.lib.dmx_model_cached_features(self.handle, shape, None, st))
+            if shape[0] == 0:
+                return None
+            out = torch.empty(tuple(int(v) for v in shape), device=self.device, dtype=torch.float32)
+            check(self.lib.dmx_model_cached_features(self.handle, shape, _ptr(out), st))
+        return out
+
     def _invert(self, x, invert, sched, hist, known, rescale, compose, geom, perturb, noise=None):
         """The C view of invert = (tables, src) for a step or loop on x, which takes no other optional part;
         makes sure the time table reaches the rows' largest timestep (read back once per table tuple,
@@ -449,7 +484,7 @@ class NativeModel:
 
     def step(self, x_in, x_out, t, y, null_label, vals, mask, guidance, tables, noise=None, seed=0,
              sample_offset=0, t_stride=1, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
-             perturb=None, invert=None):
+             perturb=None, invert=None, cache=None):
         """One denoising step: CFG (2n batched forward) when guidance > 0 and y given.
 
         sched (the 6-tuple of Diffuser.ddim_tables): one strided DDIM step instead; `t` then holds
@@ -474,9 +509,14 @@ class NativeModel:
         invert = (tables, src) (include/dmx.h dmx_invert_sched; tables: Diffuser.invert_tables, src: fp32,
         x's shape, not x): one row of a DDIM inversion instead — `t` holds countdown positions in [1, N],
         x_out = i_x src + i_e eps and src takes it on the last row of a position.  `tables`, `noise` and
-        `seed` are not read, and no other optional part may be given."""
+        `seed` are not read, and no other optional part may be given.
+        cache = (N, phase) (include/dmx.h dmx_cache): feature caching — the step refreshes the model's deep
+        feature (sa5's output) where phase % N == 0, which is the plain step bit for bit, and otherwise runs
+        only inc, up3, sa6 and the head on the stored one.  With sched / hist / known / rescale only; None
+        and N = 1 are the step without the keyword."""
         _check_state(x_in, "x")
         _check_state(x_out, "x_out")
+        ch = self._cache(cache, compose, geom, perturb, invert)
         iv = None
         if invert is not None:
             iv = self._invert(x_in, invert, sched, hist, known, rescale, compose, geom, perturb, noise)
@@ -509,6 +549,9 @@ class NativeModel:
             elif compose is not None:
                 check(self.lib.dmx_step_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                  ctypes.c_void_p(_stream(x_in.device))))
+            elif ch is not None:
+                check(self.lib.dmx_step_cached(self.handle, ctypes.byref(a), *mode, ctypes.byref(ch),
+                                               ctypes.c_void_p(_stream(x_in.device))))
             else:
                 check(self.lib.dmx_step_guided(self.handle, ctypes.byref(a), *mode,
                                                ctypes.c_void_p(_stream(x_in.device))))
@@ -534,7 +577,7 @@ class NativeModel:
 
     def sample_loop(self, x, t_dev, y, null_label, vals, mask, guidance, tables, steps, seed=0, sample_offset=0,
                     use_graph=True, sched=None, hist=None, known=None, rescale=0.0, compose=None, geom=None,
-                    perturb=None, invert=None):
+                    perturb=None, invert=None, cache=None):
         """`steps` in-place steps on x with Philox noise; t_dev (device int64 scalar) is
         decremented on the device after each step.  Runs on a side stream (graph capture
         needs a non-default stream) ordered against the current stream.
@@ -555,8 +598,12 @@ class NativeModel:
         perturb as in step(): every step of the loop is a perturbed composed step, with graphs of its own.
         invert = (tables, src) as in step(): `steps` rows of a DDIM inversion, t_dev counting the rows
         down from N; nothing is drawn (`seed` is not read) and the graphs hold the pointers of the four
-        tables and of src."""
+        tables and of src.
+        cache = (N, phase) as in step(): step k of the loop refreshes where (phase + k) % N == 0 and reuses
+        the stored feature otherwise; the loop keeps one captured graph per step kind (graph_captures
+        counts two) and replays them in the pattern."""
         _check_state(x, "x")
+        ch = self._cache(cache, compose, geom, perturb, invert)
         iv = None
         if invert is not None:
             iv = self._invert(x, invert, sched, hist, known, rescale, compose, geom, perturb)
@@ -605,6 +652,9 @@ class NativeModel:
                 check(self.lib.dmx_sample_loop_composed(self.handle, ctypes.byref(a), *mode, ctypes.byref(comp),
                                                         int(steps), int(use_graph),
                                                         ctypes.c_void_p(side.cuda_stream)))
+            elif ch is not None:
+                check(self.lib.dmx_sample_loop_cached(self.handle, ctypes.byref(a), *mode, ctypes.byref(ch),
+                                                      int(steps), int(use_graph), ctypes.c_void_p(side.cuda_stream)))
             else:
                 check(self.lib.dmx_sample_loop_guided(self.handle, ctypes.byref(a), *mode, int(steps),
                                                       int(use_graph), ctypes.c_void_p(side.cuda_stream)))

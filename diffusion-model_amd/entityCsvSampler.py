@@ -55,13 +55,14 @@ class EntityCsvSampler:
                sampler: str = "ddpm", steps: Optional[int] = None, eta: float = 0.0,
                spacing: Optional[str] = None, init_latent=None, mask=None, strength: Optional[float] = None,
                guidance_interval=None, guidance_rescale: float = 0.0, base: str = "null", geom_scale=0.0,
-               pag_scale=0.0, pag_blocks=("sa3",)):
+               pag_scale=0.0, pag_blocks=("sa3",), cache_interval: Optional[int] = None):
         """entityCsvSampler.py:50-80; sampler / steps / eta / spacing, init_latent / mask / strength and
         guidance_interval / guidance_rescale as in Diffuser.sample_latent_cond.  base = "null" (the
         default) or "dropped": the base branch of the guidance, as there (a condition spec as the base
         and `also=` are not offered here).  geom_scale as there: geometry guidance towards the CSV
         rows' own values (a float, or one per selected row).  pag_scale / pag_blocks as there:
-        perturbed-attention guidance, which also steers rows whose geometry mask is all zero."""
+        perturbed-attention guidance, which also steers rows whose geometry mask is all zero.
+        cache_interval as there: feature caching, a full network step every N-th step only."""
         if base not in ("null", "dropped"):
             raise ValueError(f'base must be "null" or "dropped" (got {base!r})')
         vals, cond_mask = self._rows(csv_path, count, start)  # (`mask` is the latent mask of the keywords)
@@ -75,7 +76,9 @@ class EntityCsvSampler:
                                                 **(dict(geom_scale=geom_scale)
                                                    if Diffuser._per_sample(geom_scale) or geom_scale else {}),
                                                 **(dict(pag_scale=pag_scale, pag_blocks=pag_blocks)
-                                                   if Diffuser._per_sample(pag_scale) or pag_scale else {}))
+                                                   if Diffuser._per_sample(pag_scale) or pag_scale else {}),
+                                                **({} if cache_interval is None
+                                                   else dict(cache_interval=cache_interval)))
 
     def load_cond(self, csv_path: str, count: Optional[int] = None, start: int = 0):
         """entityCsvSampler.py:82-98."""

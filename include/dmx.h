@@ -459,12 +459,49 @@ int dmx_unet_forward_perturbed(dmx_model* m, const float* x, const int64_t* t, c
  * C in {64, 128, 256}; n, L >= 1; n*L*C < 2^41. */
 int dmx_attn_identity(const float* qkv, float* out, int n, int L, int C, void* stream);
 
+/* ---- Feature caching: reuse the deep U-Net feature between steps (DeepCache, Ma et al. 2024; no
+ * reference counterpart).  The deep feature D is the output of sa5 — up3's upsampled input,
+ * (rows, h/2, w/2, 64) fp32 in the engine's layout, rows = 2n in a CFG step (null half first) and n in
+ * an unguided one.  Step k of a call (k = 0 in the one-step entry) is a REFRESH step iff
+ * (phase + k) % interval == 0: the plain step, bit for bit, which also leaves D in a buffer the model
+ * owns (outside its workspace, allocated on first use; sa5's last launch writes there, so a refresh
+ * step launches what the plain step launches).  Every other step is a REUSE step: the embedding, inc
+ * (once for the n shared rows under CFG batching), then up3 and sa6 on the stored D, the head and the
+ * same tail — nothing between inc and up3 is launched.  An approximation: the stored D belongs to an
+ * earlier x and t.  NULL or interval <= 1 is the plain call and shares its graphs. */
+typedef struct dmx_cache {
+  int interval; /* N: a refresh every N-th step; <= 1: no caching */
+  int phase;    /* >= 0: the call's first step stands at this offset of the cycle */
+} dmx_cache;
+
+/* dmx_step_guided / dmx_sample_loop_guided with the cache request: at most one of ddim / dpm is
+ * non-NULL (both NULL: the DDPM step), known and guidance may be NULL.  A cached step takes no
+ * composition, perturbed-attention guidance, geometry guidance or inversion (these entries have no
+ * such argument; the rule is DMX_E_ARG wherever the parts could meet).  The model records what D
+ * belongs to — rows, n, h, w, the precision mode and the generation of the weights (finalize /
+ * dmx_model_refresh start a new one) — and a reuse step without a matching D is DMX_E_STATE, naming
+ * the part that differs, before anything is launched.  A cached loop keeps two captured graphs, one
+ * per step kind, each a one-step graph, and replays them in the pattern; dmx_model_graph_captures
+ * counts each.  Reallocating the D buffer (more rows, a larger map) drops every captured graph. */
+int dmx_step_cached(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim, const dmx_dpm_sched* dpm,
+                    const dmx_known_sched* known, const dmx_guidance* guidance, const dmx_cache* cache,
+                    void* stream);
+int dmx_sample_loop_cached(dmx_model* m, const dmx_step_args* a, const dmx_ddim_sched* ddim,
+                           const dmx_dpm_sched* dpm, const dmx_known_sched* known, const dmx_guidance* guidance,
+                           const dmx_cache* cache, int steps, int use_graph, void* stream);
+/* Diagnostic: what the D buffer holds.  shape_out[4] receives (rows, h/2, w/2, 64) — all zero when no
+ * valid D is stored; dst (NULL: shape only) receives the rows*(h/2)*(w/2)*64 floats in that layout,
+ * copied on `stream`, which is synchronised. */
+int dmx_model_cached_features(dmx_model* m, int64_t* shape_out, float* dst, void* stream);
+
 /* Captured sample-loop graphs.  A model keeps the graph pairs (1-step and 8-step) of the last 4
  * distinct loops (distinct dmx_step_args / schedule / inversion / known region / guidance / composition / perturbation / geometry guidance / time-table
  * generation) and evicts the least recently used, so a sampler that alternates unguided, guided
  * and rescaled segments captures each kind once.  All pairs replay on the caller's stream, one
  * after another, inside the model's one workspace; whatever reallocates or invalidates it (a
  * larger batch, dmx_model_set_precision to another mode, dmx_model_refresh) drops every pair.
+ * A feature-cached loop (dmx_sample_loop_cached, interval > 1) takes two of the slots, one per step
+ * kind, each holding a one-step graph only and each counted as one capture.
  * Returns the number of pairs captured since the model was created (-1: NULL model). */
 int64_t dmx_model_graph_captures(const dmx_model* m);
 

@@ -2,7 +2,7 @@
 one JSON line.
 
   python tools/sampler_bench.py [--rounds 5]
-      [--groups loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end]
+      [--groups loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end,cache]
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -38,6 +38,13 @@ Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise
    the same run: its loop alternates unguided / guided / unguided segments, so it shows whether their
    graphs are reused.  Last, invert_latent_cond(S = 20, strength 0.3, R = 2) followed by
    sample_latent_cond(start_latent=..., ddim) and the decode: the edit round trip, in images/s.
+3. Feature caching (group `cache`, not in the default groups): the DDPM loop plain and with
+   cache = (N, 0) for N = 2, 3, 5, legs plain_a, n2, n3, n5, plain_b interleaved in one process, 8 steps
+   untimed and then 60 (whole cycles of every N) between two device events: ms per step, each cached leg
+   as a ratio to the plain mean, the spread of the two plain legs.  The plain leg replays its 8-step
+   graph, a cached leg one one-step graph per step.  Then the refresh step against the plain step, both as
+   60 one-step loop calls (one-step graph replays with the same host work).  Then images/s of
+   sample_latent_cond(ddpm, T = 1000) with the decode, plain against cache_interval = 3.
 
 There is no fallback: without a GPU this fails."""
 import argparse
@@ -358,6 +365,88 @@ def pag_legs(nm, d, dev, rounds):
     return out
 
 
+def cache_legs(nm, d, dev, rounds):
+    """The DDPM loop plain and feature-cached (refresh every N-th step): see the module docstring."""
+    x0, y, vals, mask = make_inputs(dev)
+    x = torch.empty_like(x0)
+    t_dev = torch.zeros((1,), dtype=torch.long, device=dev)
+    tables = d.coef_tables(dev, True)
+    timed = 60
+
+    def leg(n, calls=1):
+        kw = dict(seed=1234, **({} if n == 1 else dict(cache=(n, 0))))
+        per = timed // calls
+        x.copy_(x0)
+        t_dev.fill_(T)
+        nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tables, WARM if calls == 1 else 1, **kw)
+        x.copy_(x0)
+        t_dev.fill_(T)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            nm.sample_loop(x, t_dev, y, 0, vals, mask, GUIDANCE, tables, per, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        assert int(t_dev.item()) == T - timed and bool(torch.isfinite(x).all())
+        return e0.elapsed_time(e1) / timed
+
+    ms = {"plain_a": [], "n2": [], "n3": [], "n5": [], "plain_b": [], "plain_1step": [], "refresh_1step": []}
+    leg(1)  # workspace, split planes, time table
+    c0 = nm.graph_captures()
+    for _ in range(rounds):
+        ms["plain_a"].append(leg(1))
+        ms["n2"].append(leg(2))
+        ms["n3"].append(leg(3))
+        ms["n5"].append(leg(5))
+        ms["plain_b"].append(leg(1))
+    for _ in range(rounds):  # every call is one step: the plain one-step graph against the refresh kind's
+        ms["plain_1step"].append(leg(1, calls=timed))
+        ms["refresh_1step"].append(leg(2, calls=timed))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    plain = 0.5 * (med["plain_a"] + med["plain_b"])
+    out = {"ms_per_step_" + k: round(v, 4) for k, v in med.items()}
+    out.update({"plain_spread_ms": round(abs(med["plain_a"] - med["plain_b"]), 4),
+                "n2_over_plain_mean": round(med["n2"] / plain, 4), "n3_over_plain_mean": round(med["n3"] / plain, 4),
+                "n5_over_plain_mean": round(med["n5"] / plain, 4),
+                "refresh_minus_plain_1step_ms": round(med["refresh_1step"] - med["plain_1step"], 4),
+                "graph_captures_in_rounds": nm.graph_captures() - c0, "workspace_bytes": nm.workspace_bytes(),
+                "per_round_ms": {k: [round(v, 4) for v in vs] for k, vs in ms.items()}})
+    return out
+
+
+def cache_end_to_end(model, dev):
+    """sample_latent_cond(ddpm, T = 1000) with the decode: plain, cache_interval = 3, plain again."""
+    import diff
+    from dmx import synth
+    from models.vae import VAE
+    vae = VAE()
+    vae.load_state_dict(synth.vae_weights(1))
+    vae = vae.to(dev).eval()
+    _, y, vals, mask = make_inputs(dev, seed=11)
+    counts = [(c, int((y == c).sum())) for c in (1, 2, 3)]
+    order = torch.argsort(y, stable=True)
+    vals, mask = vals[order].contiguous(), mask[order].contiguous()
+    kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
+              cond_mask=mask)
+    d = diff.Diffuser(T, device=dev)
+    d.noise_source = "device"
+    d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
+    out = {}
+    for name, extra in (("plain_a", {}), ("n3", dict(cache_interval=3)), ("plain_b", {})):
+        secs = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            imgs = d.sample_latent_cond(model, counts, **kw, **extra)
+            secs.append(time.perf_counter() - t0)
+            assert len(imgs) == B and imgs[0].size == (8 * HW, 8 * HW)
+        out[name] = {"first_call_s": round(secs[0], 4), "steady_s": round(secs[1], 4),
+                     "steady_images_per_s": round(B / secs[1], 2)}
+    out["range_fallbacks"] = d.range_fallbacks
+    return out
+
+
 def end_to_end(model, dev):
     import diff
     from dmx import synth
@@ -439,6 +528,9 @@ def main():
             res[name] = fn(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
     if "end_to_end" in groups:
         res["end_to_end"] = end_to_end(model, dev)
+    if "cache" in groups:
+        res["cache"] = cache_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
+        res["cache"]["ddpm_T1000_end_to_end"] = cache_end_to_end(model, dev)
     print(json.dumps(res))
 
 

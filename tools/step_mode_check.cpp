@@ -366,6 +366,76 @@ int main() {
       CHECK(in.inv_mode(4).invert_conflict() != nullptr);
     }
   }
+  // 13. feature caching: no request, interval <= 1 and kind PLAIN leave every key what it was; a cached
+  // loop has one key per step kind, which hold neither the interval nor the phase; the step kinds follow
+  // (phase + k) % interval; the excluded parts are refused with a message
+  for (int mode = 0; mode < 3; ++mode) {
+    const bool ddim = mode == 1, dpm = mode == 2;
+    Inputs in;
+    const GraphKey plain = in.key(ddim, dpm, true, true);
+    StepMode sm{ddim ? &in.ddim : nullptr, dpm ? &in.dpm : nullptr, &in.known, &in.gd};
+    CHECK(plain.cache_kind == 0);
+    dmx_cache c{1, 0};
+    sm.cache = &c;
+    CHECK(!sm.cached() && sm.cache_kind(0) == StepMode::PLAIN && sm.cache_conflict() == nullptr);
+    CHECK(make_graph_key(in.a, sm, 1) == plain);
+    CHECK(make_graph_key(in.a, sm, 1, StepMode::REFRESH) == plain);  // (a kind without a request is no kind)
+    c.interval = 0;
+    CHECK(!sm.cached() && make_graph_key(in.a, sm, 1, StepMode::REUSE) == plain);
+    c.interval = -3;
+    CHECK(!sm.cached() && make_graph_key(in.a, sm, 1, StepMode::REUSE) == plain);
+    c.interval = 3;
+    CHECK(sm.cached());
+    const GraphKey refresh = make_graph_key(in.a, sm, 1, StepMode::REFRESH);
+    const GraphKey reuse = make_graph_key(in.a, sm, 1, StepMode::REUSE);
+    CHECK(!(refresh == plain) && !(reuse == plain) && !(refresh == reuse));
+    CHECK(refresh.cache_kind == (int)StepMode::REFRESH && reuse.cache_kind == (int)StepMode::REUSE);
+    c.interval = 5;
+    c.phase = 2;
+    CHECK(make_graph_key(in.a, sm, 1, StepMode::REFRESH) == refresh);
+    CHECK(make_graph_key(in.a, sm, 1, StepMode::REUSE) == reuse);
+    // everything else the loop's graphs hold stays in both keys
+    in.known.z0 = mem + 40;
+    CHECK(!(make_graph_key(in.a, sm, 1, StepMode::REFRESH) == refresh));
+    CHECK(!(make_graph_key(in.a, sm, 1, StepMode::REUSE) == reuse));
+    CHECK(!(make_graph_key(Inputs().a, sm, 2, StepMode::REUSE) == reuse));
+  }
+  {
+    const Inputs in;
+    dmx_cache c{3, 0};
+    StepMode sm;
+    sm.cache = &c;
+    const int want3[7] = {1, 2, 2, 1, 2, 2, 1};
+    for (int k = 0; k < 7; ++k) CHECK((int)sm.cache_kind(k) == want3[k]);
+    c.phase = 2;
+    const int want32[5] = {2, 1, 2, 2, 1};
+    for (int k = 0; k < 5; ++k) CHECK((int)sm.cache_kind(k) == want32[k]);
+    c.interval = 2;
+    c.phase = 2147483647;  // (the sum does not overflow)
+    CHECK(sm.cache_kind(0) == StepMode::REUSE && sm.cache_kind(1) == StepMode::REFRESH);
+    CHECK(StepMode{}.cache == nullptr && StepMode{}.cache_kind(0) == StepMode::PLAIN && !StepMode{}.cached());
+    // alone, or beside a schedule, a known region and a rescale, it is legal; beside the rest it is refused
+    c = dmx_cache{3, 0};
+    CHECK(sm.cache_conflict() == nullptr);
+    sm.ddim = &in.ddim;
+    sm.known = &in.known;
+    sm.gd = &in.gd;
+    CHECK(sm.cache_conflict() == nullptr);
+    const char* words[4] = {"composition", "geometry", "perturbed", "inversion"};
+    for (int part = 0; part < 4; ++part) {
+      StepMode bad;
+      bad.cache = &c;
+      if (part == 0) bad.comp = &in.comp;
+      if (part == 1) bad.geom = &in.geom;
+      if (part == 2) bad.perturb = &in.perturb;
+      if (part == 3) bad.invert = &in.inv;
+      const char* why = bad.cache_conflict();
+      CHECK(why != nullptr && std::strstr(why, "cached") != nullptr && std::strstr(why, words[part]) != nullptr);
+      c.interval = 1;  // without a request there is nothing to refuse
+      CHECK(bad.cache_conflict() == nullptr);
+      c.interval = 3;
+    }
+  }
   if (fails == 0) std::puts("step_mode_check: ok");
   return fails == 0 ? 0 : 1;
 }
