@@ -115,6 +115,20 @@ class _NoisePrefetch:
 
 
 @dataclasses.dataclass
+class TrainingLoss:
+    """What Diffuser.training_loss returns: `loss` carries the graph (requires_grad when the model
+    trains); the rest is detached, for logging and for replaying the batch."""
+    loss: torch.Tensor                     # 0-dim: noise_loss + geom_lambda * geom_loss
+    noise_loss: torch.Tensor               # 0-dim
+    geom_loss: torch.Tensor                # 0-dim (0 without a geometry term)
+    per_sample: torch.Tensor               # (B,) weighted noise losses
+    t: torch.Tensor                        # (B,) the timesteps used
+    drop: torch.Tensor                     # (B,) bool: rows trained as unconditional
+    eps: torch.Tensor                      # the network's prediction on the noised latent
+    geom: Optional[torch.Tensor]           # the GeomHead's output, None without one
+
+
+@dataclasses.dataclass
 class _SamplerPlan:
     """What a sampling call's steps have in common, derived once (Diffuser._plan; the public one-step
     entries fill in the fields they need): the loops of the single-process and the sharded sampler
@@ -861,6 +875,165 @@ class Diffuser:
         ab = self.alpha_bars[t - 1].view(-1, 1, 1, 1)
         noise = torch.randn_like(x_0, device=self.device)
         return torch.sqrt(ab) * x_0 + torch.sqrt(1 - ab) * noise, noise
+
+    # ---- the training objective (no reference counterpart as one call: train_latent_cond.py:136-162) ----
+    def noise_tables(self, device):
+        """(sa, s1) = sqrt(ab), sqrt(1 - ab) per t-1: add_noise's two coefficients, evaluated by torch on
+        `device` (the bits add_noise gets there)."""
+        key = ("noise", str(device))
+        if key not in self._tables:
+            ab = self._host[1].to(device)
+            self._tables[key] = (torch.sqrt(ab).contiguous(), torch.sqrt(1 - ab).contiguous())
+        return self._tables[key]
+
+    def loss_weights(self, weighting="uniform", snr_gamma=5.0, device=None):
+        """Per-timestep weights of the noise loss, (T,) fp32, index t-1.  "uniform": ones (the reference's
+        F.mse_loss).  "min_snr": min(SNR_t, gamma) / SNR_t with SNR_t = ab_t / (1 - ab_t), the
+        eps-prediction form of min-SNR-gamma (Hang et al. 2023, "Efficient diffusion training via min-SNR
+        weighting strategy"), evaluated in float64 and rounded once."""
+        try:
+            gamma = float(snr_gamma)
+        except (TypeError, ValueError):
+            gamma = float("nan")
+        if isinstance(snr_gamma, (bool, str)) or not (gamma > 0.0 and math.isfinite(gamma)):
+            raise ValueError(f"snr_gamma must be a positive finite number (got {snr_gamma!r})")
+        if weighting not in ("uniform", "min_snr"):
+            raise ValueError(f'weighting must be "uniform" or "min_snr" (got {weighting!r})')
+        device = self.device if device is None else device
+        key = ("weights", weighting, gamma, str(device))
+        if key not in self._tables:
+            if weighting == "uniform":
+                w = torch.ones(self.num_timesteps, dtype=torch.float32)
+            else:
+                ab = self._host[1].double()
+                snr = ab / (1 - ab)
+                w = (torch.clamp(snr, max=gamma) / snr).float()
+            self._tables[key] = w.contiguous().to(device)
+        return self._tables[key]
+
+    def training_loss(self, model, z, classes, cond=None, cond_mask=None, *, geom_lambda=0.0, cfg_drop_prob=0.0,
+                      null_label=0, weighting="uniform", snr_gamma=5.0, t=None, noise=None, drop=None,
+                      geom_denom=None, sample_offset=0):
+        """One training iteration's objective on the latents z (B,C,h,w) with labels `classes` (B,) and the
+        numeric condition cond / cond_mask (B,gd) -> TrainingLoss.  What train_latent_cond.py:136-159 spells
+        out in torch ops:
+            t ~ U{1..T};  z_noisy = sqrt(ab_t) z + sqrt(1 - ab_t) noise;  drop ~ (u < cfg_drop_prob)
+            y_used = where(drop, null_label, classes);  vals_used, mask_used = cond, cond_mask zeroed where drop
+            eps, geom = model(z_noisy, t, y_used, cond_vals=vals_used, cond_mask=mask_used)
+            per_sample[n] = w[t_n] mean_chw (eps - noise)^2;  noise_loss = mean_n per_sample[n]
+            geom_loss = sum mask_used (geom - cond)^2 / max(denom, 1e-6)   (denom = sum mask_used unless geom_denom)
+            loss = noise_loss + geom_lambda geom_loss
+        with w = loss_weights(weighting, snr_gamma): "uniform" is the reference's loss.  t, noise and drop
+        given are used as they are (t is range-checked, which reads it back); each one omitted is drawn.
+
+        A dmx U-Net on the GPU: the draws are Philox's on the device under one seed taken from torch's
+        global generator (torch.manual_seed fixes the batch), addressed by the rows' global indices
+        sample_offset + n, so a data-parallel rank with sample_offset = rank * B draws its rows of the
+        global batch; the objective runs in the native kernels (dmx_train_noise / dmx_objective_loss), and in
+        training mode with autograd recording `loss` is one autograd node over the parameters whose backward
+        seeds the native backward on the device (dmx_objective_seed): loss.backward(), (loss / k).backward()
+        and loss * scale work without a host synchronisation, and with drawn t the call itself issues
+        none.  In eval mode or under no_grad the same kernels run around the ordinary forward, no tape.
+        Any other model (or device): the same definition in torch ops, draws from torch's generators on z's
+        device (sample_offset is not used), autograd for the backward."""
+        T = int(self.num_timesteps)
+        if weighting not in ("uniform", "min_snr"):
+            raise ValueError(f'weighting must be "uniform" or "min_snr" (got {weighting!r})')
+        if z.dim() != 4 or min(z.shape) < 1:
+            raise ValueError(f"z must be a non-empty (B,C,h,w) tensor (got {tuple(z.shape)})")
+        B = int(z.shape[0])
+        if classes.dim() != 1 or classes.shape[0] != B:
+            raise ValueError(f"classes must be ({B},) (got {tuple(classes.shape)})")
+        if (cond is None) != (cond_mask is None):
+            raise ValueError("cond and cond_mask go together")
+        if cond is not None and (cond.dim() != 2 or cond.shape[0] != B or cond.shape[1] < 1
+                                 or tuple(cond_mask.shape) != tuple(cond.shape)):
+            raise ValueError(f"cond / cond_mask must be equal ({B}, gd) tensors (got {tuple(cond.shape)}, "
+                             f"{tuple(cond_mask.shape)})")
+        for v, nm, shape in ((t, "t", (B,)), (noise, "noise", tuple(z.shape)), (drop, "drop", (B,))):
+            if v is not None and tuple(v.shape) != shape:
+                raise ValueError(f"{nm} must be {shape} (got {tuple(v.shape)})")
+        lam, p = float(geom_lambda), float(cfg_drop_prob)
+        if not (lam >= 0.0 and math.isfinite(lam)):
+            raise ValueError(f"geom_lambda must be finite and >= 0 (got {geom_lambda})")
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"cfg_drop_prob must be in [0, 1] (got {cfg_drop_prob})")
+        if drop is not None and p != 0.0:
+            raise ValueError("drop is given: cfg_drop_prob must be 0")
+        kind = _native_kind(model)
+        has_head = kind == 1 if kind else getattr(model, "geom_head", None) is not None
+        if lam != 0.0 and (not has_head or cond is None):
+            raise ValueError("geom_lambda != 0 needs a model with a GeomHead and cond / cond_mask (its target)")
+        if kind == 2 and model.training and float(model.cfg_drop_prob) > 0.0:
+            raise ValueError("UnetCond draws a dropout of its own in forward (cfg_drop_prob > 0): construct it with "
+                             "cfg_drop_prob=0 and give the probability to training_loss")
+        weights = self.loss_weights(weighting, snr_gamma, z.device)
+        if t is not None and not bool(((t >= 1) & (t <= T)).all()):
+            raise ValueError(f"t must lie in [1, {T}]")
+        if geom_denom is not None:
+            geom_denom = torch.as_tensor(geom_denom, dtype=torch.float32).to(z.device)
+        if kind in (1, 2) and z.is_cuda:
+            return self._training_loss_native(model, z, classes, cond, cond_mask, lam, p, null_label,
+                                              None if weighting == "uniform" else weights, t, noise, drop,
+                                              geom_denom, sample_offset)
+        dev = z.device
+        if t is None:
+            t = torch.randint(1, T + 1, (B,), device=dev)
+        if noise is None:
+            noise = torch.randn_like(z)
+        if drop is None:
+            drop = torch.rand(B, device=dev) < p
+        t, drop = t.to(dev), drop.to(device=dev, dtype=torch.bool)
+        ab = self._host[1].to(dev)[t - 1].view(-1, 1, 1, 1)
+        z_noisy = torch.sqrt(ab) * z + torch.sqrt(1 - ab) * noise
+        y_used = torch.where(drop, torch.full_like(classes, null_label), classes)
+        if cond is not None:
+            keep = (~drop).float().unsqueeze(1)
+            vals_used, mask_used = cond * keep, cond_mask * keep
+            out = model(z_noisy, t, y_used, cond_vals=vals_used, cond_mask=mask_used)
+        else:
+            out = model(z_noisy, t, y_used)
+        eps, geom = out if isinstance(out, tuple) else (out, None)
+        per_sample = weights[t - 1] * (eps - noise).pow(2).flatten(1).mean(dim=1)
+        noise_loss = per_sample.mean()
+        geom_loss = torch.zeros((), device=dev)
+        if geom is not None and cond is not None:
+            from losses.geom_losses import masked_geom_mse
+            geom_loss = masked_geom_mse(geom, cond, mask_used, denom=geom_denom)
+        loss = noise_loss + lam * geom_loss
+        return TrainingLoss(loss, noise_loss.detach(), geom_loss.detach(), per_sample.detach(), t, drop,
+                            eps.detach(), geom.detach() if geom is not None else None)
+
+    def _training_loss_native(self, model, z, classes, cond, cond_mask, lam, p, null_label, weights, t, noise, drop,
+                              geom_denom, sample_offset):
+        """training_loss on a dmx conditional U-Net on the GPU (arguments checked there)."""
+        from models._native import _NativeObjectiveFn
+        T = int(self.num_timesteps)
+        sa, s1 = self.noise_tables(z.device)
+        seed = self._seed() if (t is None or noise is None or drop is None) else 0
+        z_noisy, noise, t, drop, y_used, vals_used, mask_used = _engine.train_noise(
+            z, sa, s1, t, noise, drop, classes, null_label, cond, cond_mask, p, seed, sample_offset)
+        if model.training and model._dmx_training():
+            bad = [n for n, q in model.named_parameters() if q.dtype != torch.float32 or not q.is_contiguous()]
+            if bad:
+                raise NotImplementedError(f"dmx training needs contiguous fp32 parameters ({bad[0]})")
+            # t lies in [1, T] (drawn so, or checked by training_loss): train_forward need not read it back
+            job = dict(z_noisy=z_noisy, t=t, y=y_used, vals_used=vals_used, mask_used=mask_used, noise=noise,
+                       vals=cond, weight=weights, geom_lambda=lam, denom=geom_denom, tmax=T)
+            names = [n for n, _ in model.named_parameters()]
+            loss, out, per_sample, eps, geom = _NativeObjectiveFn.apply(model, names, job, *model.parameters())
+            geom = geom if geom.numel() else None
+        else:
+            with torch.no_grad():
+                res = (model(z_noisy, t, y_used, cond_vals=vals_used, cond_mask=mask_used) if cond is not None
+                       else model(z_noisy, t, y_used))
+                eps, geom = res if isinstance(res, tuple) else (res, None)
+                use_geom = geom is not None and cond is not None
+                obj = _engine.objective_loss(eps, noise, t, weights, geom if use_geom else None,
+                                             cond if use_geom else None, mask_used if use_geom else None, lam,
+                                             geom_denom)
+            loss, out, per_sample = obj.loss, obj._out, obj.per_sample
+        return TrainingLoss(loss, out[1], out[2], per_sample, t, drop, eps, geom)
 
     # ---- one step -----------------------------------------------------------------------------
     def denoise(self, model, x, t):

@@ -122,6 +122,32 @@ class OptimTensor(ctypes.Structure):
                 ("omb2", ctypes.c_float), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+DMX_DRAW_NOISE = 0x8000000000000001
+DMX_DRAW_T = 0x8000000000000002
+DMX_DRAW_DROP = 0x8000000000000003
+
+
+class NoiseArgs(ctypes.Structure):
+    """dmx_noise_args (include/dmx.h): forward diffusion, its draws and the CFG dropout of one training batch."""
+    _fields_ = [("z", ctypes.c_void_p), ("sa", ctypes.c_void_p), ("s1", ctypes.c_void_p), ("T", ctypes.c_int),
+                ("draw", ctypes.c_int), ("t", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("drop", ctypes.c_void_p),
+                ("seed", ctypes.c_uint64), ("sample_offset", ctypes.c_int64), ("cfg_drop_prob", ctypes.c_float),
+                ("gd", ctypes.c_int), ("y", ctypes.c_void_p), ("null_label", ctypes.c_int64),
+                ("vals", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("z_noisy", ctypes.c_void_p),
+                ("y_used", ctypes.c_void_p), ("vals_used", ctypes.c_void_p), ("mask_used", ctypes.c_void_p),
+                ("B", ctypes.c_int), ("C", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int)]
+
+
+class ObjectiveArgs(ctypes.Structure):
+    """dmx_objective_args (include/dmx.h): the operands of the training loss and of its gradient seed."""
+    _fields_ = [("eps", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("t", ctypes.c_void_p),
+                ("weight", ctypes.c_void_p), ("T", ctypes.c_int), ("geom", ctypes.c_void_p),
+                ("vals", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("gd", ctypes.c_int),
+                ("denom", ctypes.c_void_p), ("geom_lambda", ctypes.c_float), ("part", ctypes.c_void_p),
+                ("per_sample", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("B", ctypes.c_int), ("C", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int)]
+
+
 class ModelConfig(ctypes.Structure):
     """dmx_model_config (include/dmx.h): reference constructor arguments that shape the network."""
     _fields_ = [("kind", ctypes.c_int), ("in_ch", ctypes.c_int), ("remove_deep_conv", ctypes.c_int),
@@ -239,6 +265,9 @@ SIGNATURES = [
     ("dmx_optim_destroy", _I, [_P]),
     ("dmx_optim_set_step", _I, [_P, _P, _I, _P]),
     ("dmx_optim_step", _I, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
+    ("dmx_train_noise", _I, [ctypes.POINTER(NoiseArgs), _P]),
+    ("dmx_objective_loss", _I, [ctypes.POINTER(ObjectiveArgs), _P]),
+    ("dmx_objective_seed", _I, [ctypes.POINTER(ObjectiveArgs), _P, _P, _P, _P]),
 ]
 
 _lib = None

@@ -2774,6 +2774,33 @@ int dmx_cfg_rescale(const float* eu, const float* ec, float guidance, float resc
   });
 }
 
+int dmx_train_noise(const dmx_noise_args* a, void* stream) {
+  return guarded([&] {
+    const char* bad = train_noise_error(a);
+    REQUIRE(bad == nullptr, bad);
+    launch_train_noise(*a, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_objective_loss(const dmx_objective_args* a, void* stream) {
+  return guarded([&] {
+    const char* bad = objective_error(a);
+    REQUIRE(bad == nullptr, bad);
+    launch_objective_loss(*a, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_objective_seed(const dmx_objective_args* a, const float* up, float* d_eps, float* d_geom, void* stream) {
+  return guarded([&] {
+    const char* bad = objective_seed_error(a, up, d_eps, d_geom);
+    REQUIRE(bad == nullptr, bad);
+    launch_objective_seed(*a, up, d_eps, d_geom, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
 int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* recs, int cap, int* n_out,
                      void* stream) {
   return guarded([&] {

@@ -23,25 +23,7 @@ namespace dmx {
 // No atomics; a sample's partials depend on that sample alone, so its result does not depend on
 // the batch.  A constant sample gives exactly zero deviations in every block and hence r = 1.
 // ---------------------------------------------------------------------------
-// Sums of two doubles over the block's 256 threads, a fixed binary tree over LDS (sh: 512 doubles).
-// Every thread of the block must call it; every thread gets the same bits.
-DMX_DEV void block_sum2(double& a, double& b, double* sh) {
-  const int t = threadIdx.x;
-  __syncthreads();  // (an earlier call's result may still be being read)
-  sh[t] = a;
-  sh[256 + t] = b;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      sh[t] += sh[t + s];
-      sh[256 + t] += sh[256 + t + s];
-    }
-    __syncthreads();
-  }
-  a = sh[0];
-  b = sh[256];
-}
-
+// (the moments go through block_sum2, tail_math.h)
 // r from the centred sums of squares of ec and eg over the same element count (which cancels):
 // formed in double, rounded to fp32 once; 1 where std(eg) is not a positive finite number.
 DMX_DEV float rescale_ratio(double m2c, double m2g, float phi) {

@@ -8,6 +8,7 @@
 #include "dmx.h"
 #include "igemm.h"
 #include "igemm_x3.h"
+#include "objective_args.h"
 #include "tail_math.h"
 #include "tokmlp.h"
 
@@ -110,5 +111,10 @@ struct OptimLaunch {
   float* norm_out;
 };
 void launch_optim_step(const OptimLaunch& o, hipStream_t st);
+// The training objective (objective.h), k_objective.hip; arguments as checked by objective_args.h.
+// noise: one launch; loss: one block per sample, then the one-block finish; seed: one launch.
+void launch_train_noise(const dmx_noise_args& a, hipStream_t st);
+void launch_objective_loss(const dmx_objective_args& a, hipStream_t st);
+void launch_objective_seed(const dmx_objective_args& a, const float* up, float* d_eps, float* d_geom, hipStream_t st);
 
 }  // namespace dmx

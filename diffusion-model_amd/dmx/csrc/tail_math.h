@@ -36,6 +36,26 @@ DMX_DEV float group_sum16(float s) {  // sum over aligned 16-lane rows (DPP), sa
   return s;
 }
 
+// Sums of two doubles over the block's 256 threads, a fixed binary tree over LDS (sh: 512 doubles).
+// Every thread of the block must call it; every thread gets the same bits.  (The CFG-rescale moments,
+// guidance.h, and the training objective's loss sums, objective.h.)
+DMX_DEV void block_sum2(double& a, double& b, double* sh) {
+  const int t = threadIdx.x;
+  __syncthreads();  // (an earlier call's result may still be being read)
+  sh[t] = a;
+  sh[256 + t] = b;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      sh[t] += sh[t + s];
+      sh[256 + t] += sh[256 + t + s];
+    }
+    __syncthreads();
+  }
+  a = sh[0];
+  b = sh[256];
+}
+
 // ---------------------------------------------------------------------------
 // Philox4x32-10 counter RNG + Box-Muller -> 4 N(0,1) per counter (perf mode K8).
 // ---------------------------------------------------------------------------

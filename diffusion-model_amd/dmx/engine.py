@@ -156,12 +156,17 @@ class NativeModel:
             check(self.lib.dmx_model_refresh(self.handle, ctypes.c_void_p(_stream(self.device))))
 
     # ---- training (include/dmx.h dmx_train_forward / dmx_train_backward) --------------------
-    def train_forward(self, x, t, y, vals=None, mask=None):
-        """Forward with a tape for dmx_train_backward -> (eps, geom or None, tape id)."""
+    def train_forward(self, x, t, y, vals=None, mask=None, tmax=None):
+        """Forward with a tape for dmx_train_backward -> (eps, geom or None, tape id).  tmax: an upper
+        bound of t the caller vouches for (timesteps drawn in [1, tmax]); t is then not read back, so
+        the call does not wait for the device."""
         require_cuda(x, "x")
         n, c, h, w = x.shape
         dev = x.device
-        self.ctx.ensure_time_table(max(1000, int(t.max().item()) if t.numel() else 1))
+        if tmax is not None:
+            self.ctx.ensure_time_table(max(1000, int(tmax)))
+        else:
+            self.ctx.ensure_time_table(max(1000, int(t.max().item()) if t.numel() else 1))
         x = x.detach().to(dtype=torch.float32).contiguous()
         t = t.to(device=dev, dtype=torch.long).contiguous()
         y = y.to(device=dev, dtype=torch.long).contiguous()
@@ -851,6 +856,169 @@ def geom_mix(eps, grad, scale, sig, pos):
                                0 if p_c.numel() == 1 and n > 1 else 1, _ptr(out), n, c, h, w,
                                ctypes.c_void_p(_stream(dev))))
     return out
+
+
+def train_noise(z, sa, s1, t=None, noise=None, drop=None, y=None, null_label=0, vals=None, mask=None,
+                cfg_drop_prob=0.0, seed=0, sample_offset=0):
+    """The front half of a training iteration (include/dmx.h dmx_train_noise; train_latent_cond.py:136-145) ->
+    (z_noisy, noise, t, drop, y_used, vals_used, mask_used):
+        z_noisy = sa[t - 1] z + s1[t - 1] noise     (torch's bits: two products and a sum, no FMA)
+        y_used = where(drop, null_label, y);  vals_used / mask_used = the rows of vals / mask, zero where drop
+    z: (B,C,h,w) on the GPU, any C, h, w >= 1; sa, s1: (T,) fp32 tables sqrt(ab), sqrt(1 - ab).  t (B,) in
+    [1, T], noise (z's shape) and drop (B,) bool are used as given; each one left None is drawn on the
+    device by Philox under `seed` from the rows' global indices sample_offset + n (t uniform on [1, T],
+    drop = u < cfg_drop_prob, noise standard normal), so a shard of a batch draws the batch's rows.
+    y, vals / mask may be None (their outputs are then None).  No host synchronisation.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(z, "z")
+    dev = z.device
+    z_c = z.detach().to(dtype=torch.float32).contiguous()
+    if z_c.dim() != 4 or min(z_c.shape) < 1:
+        raise ValueError(f"z must be a non-empty (B,C,h,w) tensor (got {tuple(z.shape)})")
+    B, C, h, w = z_c.shape
+    sa_c = sa.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    s1_c = s1.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    T = int(sa_c.numel())
+    if T < 1 or s1_c.numel() != T:
+        raise ValueError(f"sa and s1 must be equal non-empty tables (got {sa_c.numel()}, {s1_c.numel()})")
+    p = float(cfg_drop_prob)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"cfg_drop_prob must be in [0, 1] (got {cfg_drop_prob})")
+    draw = 0
+    if t is None:
+        draw |= 1
+        t_c = torch.empty((B,), device=dev, dtype=torch.long)
+    else:
+        t_c = t.to(device=dev, dtype=torch.long).contiguous().reshape(-1)
+    if noise is None:
+        draw |= 2
+        nz_c = torch.empty_like(z_c)
+    else:
+        nz_c = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if drop is None:
+        draw |= 4
+        d_c = torch.empty((B,), device=dev, dtype=torch.bool)
+    else:
+        d_c = drop.to(device=dev, dtype=torch.bool).contiguous().reshape(-1)
+    if t_c.numel() != B or d_c.numel() != B or tuple(nz_c.shape) != tuple(z_c.shape):
+        raise ValueError(f"t / drop need {B} entries and noise z's shape (got {t_c.numel()}, {d_c.numel()}, "
+                         f"{tuple(nz_c.shape)})")
+    if (vals is None) != (mask is None):
+        raise ValueError("vals and mask go together")
+    y_c = y_u = v_c = m_c = v_u = m_u = None
+    gd = 0
+    if y is not None:
+        y_c = y.to(device=dev, dtype=torch.long).contiguous().reshape(-1)
+        if y_c.numel() != B:
+            raise ValueError(f"y has {y_c.numel()} entries for a batch of {B}")
+        y_u = torch.empty_like(y_c)
+    if vals is not None:
+        v_c = vals.detach().to(device=dev, dtype=torch.float32).contiguous()
+        m_c = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if v_c.dim() != 2 or v_c.shape[0] != B or v_c.shape[1] < 1 or tuple(m_c.shape) != tuple(v_c.shape):
+            raise ValueError(f"vals / mask must be equal ({B}, gd) tensors (got {tuple(vals.shape)}, "
+                             f"{tuple(mask.shape)})")
+        gd = int(v_c.shape[1])
+        v_u, m_u = torch.empty_like(v_c), torch.empty_like(m_c)
+    out = torch.empty_like(z_c)
+    a = _lib.NoiseArgs(z=_ptr(z_c), sa=_ptr(sa_c), s1=_ptr(s1_c), T=T, draw=draw, t=_ptr(t_c), noise=_ptr(nz_c),
+                       drop=_ptr(d_c), seed=int(seed) & (2 ** 64 - 1), sample_offset=int(sample_offset),
+                       cfg_drop_prob=p, gd=gd, y=_ptr(y_c), null_label=int(null_label), vals=_ptr(v_c),
+                       mask=_ptr(m_c), z_noisy=_ptr(out), y_used=_ptr(y_u), vals_used=_ptr(v_u),
+                       mask_used=_ptr(m_u), B=B, C=C, h=h, w=w)
+    with torch.cuda.device(dev):
+        check(lib.dmx_train_noise(ctypes.byref(a), ctypes.c_void_p(_stream(dev))))
+    return out, nz_c, t_c, d_c, y_u, v_u, m_u
+
+
+class Objective:
+    """What objective_loss computed and what objective_seed reads again: loss, noise_loss, geom_loss
+    (0-dim views of one device buffer), per_sample (B,), and the operands, kept alive."""
+
+    def __init__(self, args, keep, out, per_sample, has_geom):
+        self._args, self._keep, self._out, self.has_geom = args, keep, out, has_geom
+        self.loss, self.noise_loss, self.geom_loss = out[0], out[1], out[2]
+        self.per_sample = per_sample
+
+
+def objective_loss(eps, noise, t=None, weight=None, geom=None, vals=None, mask=None, geom_lambda=0.0, denom=None):
+    """The training loss (include/dmx.h dmx_objective_loss; train_latent_cond.py:151-159) -> Objective:
+        per_sample[n] = weight[t_n - 1] mean_chw (eps - noise)^2;  noise_loss = mean_n per_sample[n]
+        geom_loss = sum mask (geom - vals)^2 / max(denom, 1e-6), denom = sum mask unless given
+        loss = noise_loss + geom_lambda geom_loss
+    fp32 differences and squares, double sums in a fixed order: the same bits from run to run.  eps, noise:
+    (B,C,h,w) on the GPU; weight: (T,) fp32 with t (B,) in [1, T], or None for 1; geom, vals, mask: (B,gd)
+    or None (no geometry term); denom: a 0-dim tensor or a float.  No host synchronisation."""
+    lib = _lib.load()
+    require_cuda(eps, "eps")
+    dev = eps.device
+    e_c = eps.detach().to(dtype=torch.float32).contiguous()
+    n_c = noise.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if e_c.dim() != 4 or min(e_c.shape) < 1 or tuple(n_c.shape) != tuple(e_c.shape):
+        raise ValueError(f"eps / noise must be equal non-empty (B,C,h,w) tensors (got {tuple(eps.shape)}, "
+                         f"{tuple(noise.shape)})")
+    B, C, h, w = e_c.shape
+    lam = float(geom_lambda)
+    if not (lam >= 0.0 and lam < float("inf")):
+        raise ValueError(f"geom_lambda must be finite and >= 0 (got {geom_lambda})")
+    t_c = w_c = g_c = v_c = m_c = d_c = None
+    T = gd = 0
+    if weight is not None:
+        if t is None:
+            raise ValueError("a weight table needs t")
+        w_c = weight.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+        t_c = t.to(device=dev, dtype=torch.long).contiguous().reshape(-1)
+        T = int(w_c.numel())
+        if T < 1 or t_c.numel() != B:
+            raise ValueError(f"weight must be a non-empty table and t have {B} entries (got {T}, {t_c.numel()})")
+    if geom is not None:
+        if vals is None or mask is None:
+            raise ValueError("the geometry term needs vals and mask")
+        g_c = geom.detach().to(device=dev, dtype=torch.float32).contiguous()
+        v_c = vals.detach().to(device=dev, dtype=torch.float32).contiguous()
+        m_c = mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if g_c.dim() != 2 or g_c.shape[0] != B or g_c.shape[1] < 1 or tuple(v_c.shape) != tuple(g_c.shape) or \
+                tuple(m_c.shape) != tuple(g_c.shape):
+            raise ValueError(f"geom / vals / mask must be equal ({B}, gd) tensors (got {tuple(geom.shape)}, "
+                             f"{tuple(vals.shape)}, {tuple(mask.shape)})")
+        gd = int(g_c.shape[1])
+        if denom is not None:
+            d_c = torch.as_tensor(denom, dtype=torch.float32).to(device=dev).reshape(-1).contiguous()
+            if d_c.numel() != 1:
+                raise ValueError("denom must be one number")
+    part = torch.empty((3 * B,), device=dev, dtype=torch.float64)
+    per_sample = torch.empty((B,), device=dev, dtype=torch.float32)
+    out = torch.empty((4,), device=dev, dtype=torch.float32)
+    a = _lib.ObjectiveArgs(eps=_ptr(e_c), noise=_ptr(n_c), t=_ptr(t_c), weight=_ptr(w_c), T=T, geom=_ptr(g_c),
+                           vals=_ptr(v_c), mask=_ptr(m_c), gd=gd, denom=_ptr(d_c), geom_lambda=lam, part=_ptr(part),
+                           per_sample=_ptr(per_sample), out=_ptr(out), B=B, C=C, h=h, w=w)
+    with torch.cuda.device(dev):
+        check(lib.dmx_objective_loss(ctypes.byref(a), ctypes.c_void_p(_stream(dev))))
+    return Objective(a, (e_c, n_c, t_c, w_c, g_c, v_c, m_c, d_c, part), out, per_sample, g_c is not None)
+
+
+def objective_seed(obj, up=None, want_geom=True):
+    """The gradient of an Objective's loss (include/dmx.h dmx_objective_seed) -> (d_eps, d_geom or None):
+        d_eps = up 2 w_n (eps - noise) / (B C h w);  d_geom = up geom_lambda 2 mask (geom - vals) / max(denom, 1e-6)
+    what NativeModel.train_backward takes.  up: the upstream gradient as a one-element fp32 tensor on the
+    GPU, read by the kernel (None: 1); no host synchronisation."""
+    lib = _lib.load()
+    e_c, g_c = obj._keep[0], obj._keep[4]
+    dev = e_c.device
+    if up is None:
+        up_c = torch.ones((1,), device=dev, dtype=torch.float32)
+    else:
+        up_c = up.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+        if up_c.numel() != 1:
+            raise ValueError(f"up must hold one number (got {up_c.numel()})")
+    d_eps = torch.empty_like(e_c)
+    d_geom = torch.empty_like(g_c) if (want_geom and g_c is not None) else None
+    with torch.cuda.device(dev):
+        check(lib.dmx_objective_seed(ctypes.byref(obj._args), _ptr(up_c), _ptr(d_eps), _ptr(d_geom),
+                                     ctypes.c_void_p(_stream(dev))))
+    obj._live_seed = (up_c, d_eps, d_geom)
+    return d_eps, d_geom
 
 
 def _update_operands(x, eu, ec, noise, pos, pos_name):

@@ -123,6 +123,49 @@ class _NativeTrainFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, *out)
 
 
+class _NativeObjectiveFn(torch.autograd.Function):
+    """The whole training objective as one node over the parameters (Diffuser.training_loss): native
+    taped forward on the noised latent, native loss (dmx_objective_loss); backward = the loss's seed
+    scaled by the upstream gradient on the device (dmx_objective_seed) into the native backward.
+
+    Inputs after (module, names, job): *parameters (named_parameters order).  job: z_noisy, t, y, vals_used,
+    mask_used (the network's inputs), noise, vals (the targets), weight, geom_lambda, denom, tmax (None:
+    t is the caller's and is read back).  Outputs (loss, [loss, noise_loss, geom_loss, denom], per_sample, eps, geom);
+    only loss is differentiable.  The rules for unused branches are _NativeTrainFn's: cond_mlp.* get None
+    without cond, geom_head.* where the loss has no geometry term (geom_lambda == 0)."""
+
+    @staticmethod
+    def forward(ctx, module, names, job, *params):
+        nm = module.native()
+        eps, geom, tape = nm.train_forward(job["z_noisy"], job["t"], job["y"], job["vals_used"], job["mask_used"],
+                                           tmax=job["tmax"])
+        use_geom = geom is not None and job["vals"] is not None
+        obj = _engine.objective_loss(eps, job["noise"], job["t"], job["weight"], geom if use_geom else None,
+                                     job["vals"] if use_geom else None, job["mask_used"] if use_geom else None,
+                                     job["geom_lambda"], job["denom"])
+        ctx.nm, ctx.tape, ctx.names, ctx.obj = nm, tape, names, obj
+        ctx.cond, ctx.geom_term = job["vals_used"] is not None, use_geom and job["geom_lambda"] != 0.0
+        ctx.set_materialize_grads(False)
+        if geom is None:
+            geom = eps.new_empty(0)
+        loss = obj.loss.clone()  # (the other scalars stay views of the kernel's output buffer)
+        outs = (obj._out, obj.per_sample, eps, geom)
+        ctx.mark_non_differentiable(*outs)
+        return (loss, *outs)
+
+    @staticmethod
+    def backward(ctx, up, *_):
+        if up is None:
+            return (None, None, None, *[None for _ in ctx.names])
+        d_eps, d_geom = _engine.objective_seed(ctx.obj, up, want_geom=ctx.geom_term)
+        grads = ctx.nm.train_backward(ctx.tape, d_eps, d_geom)
+        out = []
+        for n in ctx.names:
+            unused = (not ctx.cond and n.startswith("cond_mlp.")) or (d_geom is None and n.startswith("geom_head."))
+            out.append(None if unused else grads[n])
+        return (None, None, None, *out)
+
+
 class _NativeVaeTrainFn(torch.autograd.Function):
     """Native forward with a tape / native backward of VAE.forward's network part (models/vae.py:51-69).
 

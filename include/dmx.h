@@ -669,6 +669,94 @@ int dmx_optim_set_step(dmx_optim* o, const dmx_optim_tensor* rows, int n, void* 
  * is set).  A set of rows is consumed by one step. */
 int dmx_optim_step(dmx_optim* o, float max_norm, float ema_d, float ema_omd, float* norm_out, void* stream);
 
+/* ---- training objective (replaces the torch ops around the network in train_latent_cond.py:136-159:
+ * the timestep draw, diff.py:18-30 add_noise, the CFG dropout of label / values / mask, F.mse_loss,
+ * masked_geom_mse and the autograd walk back to dLoss/deps, dLoss/dgeom).  Stateless: device pointers
+ * and a stream, no model handle, so the pieces also serve a foreign model.  All tensors contiguous.
+ *
+ * dmx_train_noise, per sample n of B and element i of its C*h*w:
+ *   z_noisy = sa[t_n - 1] * z + s1[t_n - 1] * noise       (sa = sqrt(ab), s1 = sqrt(1 - ab), [T] fp32,
+ *                                                           tabulated by the caller)
+ * two products and a sum, one IEEE rounding each, never contracted: given t and noise the result has
+ * the bits of torch's expression.  y_used[n] = drop_n ? null_label : y[n]; vals_used / mask_used =
+ * the rows of vals / mask, exactly zero where drop_n (kept rows bit for bit).
+ * t, noise and drop are each read, or, where its bit of `draw` is set (DMX_DRAWS_T, DMX_DRAWS_NOISE,
+ * DMX_DRAWS_DROP), written.  Read: drop == NULL drops nothing; a t outside [1, T] is clamped for the
+ * table reads (the caller checks its range).  Written: drawn by Philox4x32-10 under `seed`, with
+ * g = sample_offset + n the row's index in the global batch and Q = ceil(C*h*w / 4):
+ *   noise[n][4q .. 4q+3] = the four normals of counter (DMX_DRAW_NOISE, g * Q + q)
+ *   t_n    = 1 + floor(word0(DMX_DRAW_T, g) * T / 2^32)        (multiply-high; bias <= T / 2^32)
+ *   drop_n = (word0(DMX_DRAW_DROP, g) >> 8) * 2^-24 < cfg_drop_prob   (0 drops none, 1 drops all)
+ * so a rank that holds rows [k, k + B) of a global batch draws exactly those rows' values.
+ * y, vals, mask may be NULL (then y_used / vals_used / mask_used are not written); gd = row width. */
+#define DMX_DRAW_NOISE 0x8000000000000001ull
+#define DMX_DRAW_T 0x8000000000000002ull
+#define DMX_DRAW_DROP 0x8000000000000003ull
+#define DMX_DRAWS_T 1
+#define DMX_DRAWS_NOISE 2
+#define DMX_DRAWS_DROP 4
+
+typedef struct dmx_noise_args {
+  const float* z;      /* (B,C,h,w) */
+  const float* sa;     /* [T], index t - 1 */
+  const float* s1;
+  int T;
+  int draw;            /* DMX_DRAWS_* bits */
+  int64_t* t;          /* (B,) */
+  float* noise;        /* (B,C,h,w) */
+  uint8_t* drop;       /* (B,) 0 / 1 */
+  uint64_t seed;
+  int64_t sample_offset;
+  float cfg_drop_prob; /* in [0, 1]; read when drop is drawn */
+  int gd;
+  const int64_t* y;    /* (B,) or NULL */
+  int64_t null_label;
+  const float* vals;   /* (B,gd) or NULL together with mask */
+  const float* mask;
+  float* z_noisy;      /* (B,C,h,w) */
+  int64_t* y_used;
+  float* vals_used;
+  float* mask_used;
+  int B, C, h, w;
+} dmx_noise_args;
+
+int dmx_train_noise(const dmx_noise_args* a, void* stream);
+
+/* dmx_objective_loss: with N = C*h*w, w_n = weight[t_n - 1] (weight == NULL: 1), g / v / m the rows of
+ * geom / vals / mask (geom == NULL: no geometry term, gd not read)
+ *   per_sample[n] = w_n * sum_i (eps - noise)^2 / N         noise_loss = sum_n per_sample[n] / B
+ *   geom_loss = sum m (g - v)^2 / max(denom, 1e-6)          denom = *denom if given, else sum m
+ *   loss = noise_loss + geom_lambda * geom_loss
+ * Differences, squares and the mask product are fp32 with one rounding each; every sum is double in a
+ * fixed order (one block per sample, then the B partials in index order in one block), each result
+ * rounded to fp32 once: the same bits from run to run, no atomics.  out[0..3] = loss, noise_loss,
+ * geom_loss, max(denom, 1e-6).  part: B * 3 doubles of scratch.
+ * dmx_objective_seed: the gradient of `loss` scaled by the upstream scalar *up (a device pointer:
+ * no host synchronisation), reading out[3] of the dmx_objective_loss call on the same arguments
+ *   d_eps[n][i]  = (up * 2 w_n / (B N)) * (eps - noise)
+ *   d_geom[n][j] = (up * geom_lambda * 2 / max(denom, 1e-6)) * (m * (g - v))      (d_geom NULL: skipped)
+ * each coefficient formed in double and rounded once.  Both feed dmx_train_backward. */
+typedef struct dmx_objective_args {
+  const float* eps;    /* (B,C,h,w) */
+  const float* noise;
+  const int64_t* t;    /* (B,), read where weight is given */
+  const float* weight; /* [T], index t - 1, or NULL */
+  int T;
+  const float* geom;   /* (B,gd) or NULL */
+  const float* vals;
+  const float* mask;
+  int gd;
+  const float* denom;  /* one device float or NULL */
+  float geom_lambda;   /* finite, >= 0 */
+  double* part;
+  float* per_sample;   /* (B,) */
+  float* out;          /* [4] */
+  int B, C, h, w;
+} dmx_objective_args;
+
+int dmx_objective_loss(const dmx_objective_args* a, void* stream);
+int dmx_objective_seed(const dmx_objective_args* a, const float* up, float* d_eps, float* d_geom, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
