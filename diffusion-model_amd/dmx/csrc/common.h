@@ -134,6 +134,19 @@ DMX_DEV void split4(floatx4 v, half4& h, half4& l) {
   l = __builtin_bit_cast(half4, (u32x2){l0, l1});
 }
 
+// split4 of v * s.  The product is rounded to fp32 once and hi and lo are both taken from that one value
+// (split2u's asm reads it from a register).  Written as plain C — h = (_Float16)(v * s), l = (_Float16)(v * s
+// - (float)h) — the compiler contracts the two uses of the product differently: the stored hi from the
+// fp32-rounded product (v_mul_f32 + v_cvt_pk_f16_f32), lo as v_fma_mix(v, s, -hi') with hi' = f16 of the
+// unrounded product.  Where the product lies within an fp32 rounding of an f16 tie, hi and hi' are different
+// neighbours and the pair is off by a whole f16 ulp of hi (2^-11 relative instead of 2^-22): about one
+// element in 2^13.
+DMX_DEV void split4_scaled(floatx4 v, float s, half4& h, half4& l) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] *= s;
+  split4(v, h, l);
+}
+
 // Input-source modes of a convolution / token GEMM (how the A operand's
 // element (n, iy, ix, c) is produced from HBM).
 enum SrcMode : int {

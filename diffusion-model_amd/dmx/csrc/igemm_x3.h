@@ -443,14 +443,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
       a = ld4(r);
       b = ld4(r + 4);
     }
+    half4 ha, la, hb, lb;  // (one fp32 rounding of q * qscale, hi and lo from that value: common.h)
+    split4_scaled(a, qscale, ha, la);
+    split4_scaled(b, qscale, hb, lb);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float va = a[j] * qscale, vb = b[j] * qscale;
-      const _Float16 ha = (_Float16)va, hb = (_Float16)vb;
-      qh[ks][j] = ha;
-      ql[ks][j] = (_Float16)(va - (float)ha);
-      qh[ks][j + 4] = hb;
-      ql[ks][j + 4] = (_Float16)(vb - (float)hb);
+      qh[ks][j] = ha[j];
+      ql[ks][j] = la[j];
+      qh[ks][j + 4] = hb[j];
+      ql[ks][j + 4] = lb[j];
     }
   }
   // D < 32: V^T is padded to 32 rows; row D holds ones so O^T row D accumulates the
@@ -758,14 +759,15 @@ __global__ __launch_bounds__(NW * 64) void attention16_kernel(const float* qkv, 
         a = ld4(r);
         b = ld4(r + 4);
       }
+      half4 ha, la, hb, lb;  // (one fp32 rounding of q * qscale, hi and lo from that value: common.h)
+      split4_scaled(a, qscale, ha, la);
+      split4_scaled(b, qscale, hb, lb);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float va = a[j] * qscale, vb = b[j] * qscale;
-        const _Float16 ha = (_Float16)va, hb = (_Float16)vb;
-        qh[j] = ha;
-        ql[j] = (_Float16)(va - (float)ha);
-        qh[j + 4] = hb;
-        ql[j + 4] = (_Float16)(vb - (float)hb);
+        qh[j] = ha[j];
+        ql[j] = la[j];
+        qh[j + 4] = hb[j];
+        ql[j + 4] = lb[j];
       }
     }
     // Lazily rescaled online softmax: the first S^T MFMA of a tile takes C = -mref, so scores
