@@ -33,6 +33,10 @@ What changes is where the work happens:
 * Geometry guidance (not in the reference): ``sample_latent_cond(..., geom_scale=s)`` adds the input
   gradient of the GeomHead's masked regression loss against the call's own condition to every step's
   guided prediction (classifier guidance; libdmx ``dmx_step_geom`` / ``dmx_geom_mix``).
+* v-prediction (not in the reference): ``Diffuser(..., prediction="v")`` reads the network's output as the
+  velocity v = sqrt(ab_t) noise - sqrt(1 - ab_t) x0.  Every sampling entry mixes in output space, converts once
+  (eps = sqrt(ab_t) v + sqrt(1 - ab_t) x_t, in the native tail; ``dmx_model_set_prediction`` /
+  ``dmx_pred_to_eps``) and runs the eps-form update; ``training_loss`` regresses on v.
 """
 from __future__ import annotations
 
@@ -124,8 +128,10 @@ class TrainingLoss:
     per_sample: torch.Tensor               # (B,) weighted noise losses
     t: torch.Tensor                        # (B,) the timesteps used
     drop: torch.Tensor                     # (B,) bool: rows trained as unconditional
-    eps: torch.Tensor                      # the network's prediction on the noised latent
+    eps: torch.Tensor                      # the network's prediction on the noised latent (a v-model's: v)
     geom: Optional[torch.Tensor]           # the GeomHead's output, None without one
+    target: Optional[torch.Tensor] = None  # what eps is regressed on: `noise` itself, or a v-model's
+                                           # sqrt(ab_t) noise - sqrt(1 - ab_t) z
 
 
 @dataclasses.dataclass
@@ -205,7 +211,18 @@ class _SamplerPlan:
 
 
 class Diffuser:
-    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, device="cpu"):
+    PREDICTIONS = ("eps", "v")
+
+    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, device="cpu", *, prediction="eps"):
+        """prediction (not in the reference): what the network's output means.  "eps": the noise, as the
+        reference trains it.  "v": the velocity v = sqrt(ab_t) noise - sqrt(1 - ab_t) x0 (Salimans & Ho
+        2022).  A checkpoint does not record it, so the caller states it.  With "v" every sampling entry
+        mixes in output space (CFG, composition, perturbed branch, CFG rescale — whose standard deviations
+        are then v's — and geometry guidance), converts once, eps = sqrt(ab_t) out + sqrt(1 - ab_t) x_t,
+        and runs the eps-form update; training_loss regresses on v."""
+        if not isinstance(prediction, str) or prediction not in self.PREDICTIONS:
+            raise ValueError(f'prediction must be "eps" or "v" (got {prediction!r})')
+        self.prediction = prediction
         # diff.py:11-16, evaluated on the CPU (torch's CPU cumprod accumulates in double)
         self.num_timesteps = num_timesteps
         self.device = device
@@ -538,11 +555,61 @@ class Diffuser:
 
     def geom_sig(self, device):
         """sqrt(1 - alpha_bar[t]) at index t - 1, fp32 from the fp32 alpha_bars: the sig table of a
-        geometry-guided DDPM step (the strided rules use their schedule's k_e, the same quantity per position)."""
+        geometry-guided DDPM step (the strided rules use their schedule's k_e, the same quantity per position).
+        A v-model's mix happens in output space, where eps += s sig dL/dx reads v += s (sig / sqrt(ab)) dL/dx:
+        the table is then sqrt(1 - ab) / sqrt(ab), one fp32 division of the two fp32 roots."""
         cache = self.__dict__.setdefault("_geom_sig", {})
-        if str(device) not in cache:
-            cache[str(device)] = torch.sqrt(1 - self._host[1]).contiguous().to(device)
-        return cache[str(device)]
+        key = (str(device), self.prediction)
+        if key not in cache:
+            sig = torch.sqrt(1 - self._host[1])
+            if self.prediction == "v":
+                sig = sig / torch.sqrt(self._host[1])
+            cache[key] = sig.contiguous().to(device)
+        return cache[key]
+
+    def _sched_sig(self, sched):
+        """geom_sig per position of a strided schedule (t_map, k_e, k_a, ..): k_e, over k_a for a v-model."""
+        return sched[1] if self.prediction != "v" else (sched[1] / sched[2]).contiguous()
+
+    # ---- what the network predicts -------------------------------------------------------------
+    def pred_tables(self, device):
+        """(p_o, p_x) = sqrt(ab), sqrt(1 - ab) per t-1: the coefficients of a v-model's conversion
+        eps = p_o[t-1] out + p_x[t-1] x_t — the values noise_tables builds on the host, copied to `device`
+        (not evaluated a second time there)."""
+        host = self.noise_tables("cpu")
+        if torch.device(device).type == "cpu":
+            return host
+        key = ("pred", str(device))
+        if key not in self._tables:
+            self._tables[key] = tuple(k.to(device) for k in host)
+        return self._tables[key]
+
+    def _native(self, model):
+        """model.native() with its prediction set to this Diffuser's (a repeated setting costs nothing)."""
+        nm = model.native()
+        self._set_prediction(nm)
+        return nm
+
+    def _set_prediction(self, nm):
+        """Tell the native model `nm` this Diffuser's prediction.  A stand-in for NativeModel that knows no
+        predictions reads eps: it is left alone in eps-mode and refused in v-mode."""
+        setter = getattr(nm, "set_prediction", None)
+        if self.prediction == "v":
+            if setter is None:
+                raise TypeError(f'prediction="v" needs a native model that can be told so ({type(nm).__name__} has '
+                                f"no set_prediction)")
+            setter("v", *self.pred_tables(nm.device))
+        elif setter is not None:
+            setter("eps")
+
+    def _to_eps(self, eu, ec, g, x, t):
+        """A foreign model's operands (eu, ec, g) as eps: unchanged for an eps-model; a v-model's are mixed
+        in output space, eu + g (ec - eu) in torch ops (the update's own expression), then converted at the
+        network timesteps t on the latent x the model saw (engine.pred_to_eps) -> (eps, None, 0.0)."""
+        if self.prediction != "v":
+            return eu, ec, g
+        out = eu if ec is None else eu + g * (ec - eu)
+        return _engine.pred_to_eps(out, x, t, *self.pred_tables(x.device)), None, 0.0
 
     @staticmethod
     def _geom_loss_grad(model, x, t, y, cond_vals, cond_mask):
@@ -890,7 +957,8 @@ class Diffuser:
         """Per-timestep weights of the noise loss, (T,) fp32, index t-1.  "uniform": ones (the reference's
         F.mse_loss).  "min_snr": min(SNR_t, gamma) / SNR_t with SNR_t = ab_t / (1 - ab_t), the
         eps-prediction form of min-SNR-gamma (Hang et al. 2023, "Efficient diffusion training via min-SNR
-        weighting strategy"), evaluated in float64 and rounded once."""
+        weighting strategy"), evaluated in float64 and rounded once.  A v-model (prediction="v") takes the
+        paper's v-prediction form min(SNR_t, gamma) / (SNR_t + 1), formed the same way."""
         try:
             gamma = float(snr_gamma)
         except (TypeError, ValueError):
@@ -900,14 +968,14 @@ class Diffuser:
         if weighting not in ("uniform", "min_snr"):
             raise ValueError(f'weighting must be "uniform" or "min_snr" (got {weighting!r})')
         device = self.device if device is None else device
-        key = ("weights", weighting, gamma, str(device))
+        key = ("weights", weighting, gamma, str(device), self.prediction)
         if key not in self._tables:
             if weighting == "uniform":
                 w = torch.ones(self.num_timesteps, dtype=torch.float32)
             else:
                 ab = self._host[1].double()
                 snr = ab / (1 - ab)
-                w = (torch.clamp(snr, max=gamma) / snr).float()
+                w = (torch.clamp(snr, max=gamma) / (snr + 1 if self.prediction == "v" else snr)).float()
             self._tables[key] = w.contiguous().to(device)
         return self._tables[key]
 
@@ -920,7 +988,8 @@ class Diffuser:
             t ~ U{1..T};  z_noisy = sqrt(ab_t) z + sqrt(1 - ab_t) noise;  drop ~ (u < cfg_drop_prob)
             y_used = where(drop, null_label, classes);  vals_used, mask_used = cond, cond_mask zeroed where drop
             eps, geom = model(z_noisy, t, y_used, cond_vals=vals_used, cond_mask=mask_used)
-            per_sample[n] = w[t_n] mean_chw (eps - noise)^2;  noise_loss = mean_n per_sample[n]
+            per_sample[n] = w[t_n] mean_chw (eps - target)^2;  noise_loss = mean_n per_sample[n]
+            target = noise, or for a v-model (prediction="v") sqrt(ab_t) noise - sqrt(1 - ab_t) z
             geom_loss = sum mask_used (geom - cond)^2 / max(denom, 1e-6)   (denom = sum mask_used unless geom_denom)
             loss = noise_loss + geom_lambda geom_loss
         with w = loss_weights(weighting, snr_gamma): "uniform" is the reference's loss.  t, noise and drop
@@ -994,7 +1063,8 @@ class Diffuser:
         else:
             out = model(z_noisy, t, y_used)
         eps, geom = out if isinstance(out, tuple) else (out, None)
-        per_sample = weights[t - 1] * (eps - noise).pow(2).flatten(1).mean(dim=1)
+        target = noise if self.prediction != "v" else torch.sqrt(ab) * noise - torch.sqrt(1 - ab) * z
+        per_sample = weights[t - 1] * (eps - target).pow(2).flatten(1).mean(dim=1)
         noise_loss = per_sample.mean()
         geom_loss = torch.zeros((), device=dev)
         if geom is not None and cond is not None:
@@ -1002,7 +1072,7 @@ class Diffuser:
             geom_loss = masked_geom_mse(geom, cond, mask_used, denom=geom_denom)
         loss = noise_loss + lam * geom_loss
         return TrainingLoss(loss, noise_loss.detach(), geom_loss.detach(), per_sample.detach(), t, drop,
-                            eps.detach(), geom.detach() if geom is not None else None)
+                            eps.detach(), geom.detach() if geom is not None else None, target.detach())
 
     def _training_loss_native(self, model, z, classes, cond, cond_mask, lam, p, null_label, weights, t, noise, drop,
                               geom_denom, sample_offset):
@@ -1011,14 +1081,17 @@ class Diffuser:
         T = int(self.num_timesteps)
         sa, s1 = self.noise_tables(z.device)
         seed = self._seed() if (t is None or noise is None or drop is None) else 0
-        z_noisy, noise, t, drop, y_used, vals_used, mask_used = _engine.train_noise(
-            z, sa, s1, t, noise, drop, classes, null_label, cond, cond_mask, p, seed, sample_offset)
+        # a v-model: the noising launch also stores the target, and the loss kernels read it where they read noise
+        front = _engine.train_noise(z, sa, s1, t, noise, drop, classes, null_label, cond, cond_mask, p, seed,
+                                    sample_offset, **({"target": True} if self.prediction == "v" else {}))
+        z_noisy, noise, t, drop, y_used, vals_used, mask_used = front[:7]
+        target = front[7] if self.prediction == "v" else noise
         if model.training and model._dmx_training():
             bad = [n for n, q in model.named_parameters() if q.dtype != torch.float32 or not q.is_contiguous()]
             if bad:
                 raise NotImplementedError(f"dmx training needs contiguous fp32 parameters ({bad[0]})")
             # t lies in [1, T] (drawn so, or checked by training_loss): train_forward need not read it back
-            job = dict(z_noisy=z_noisy, t=t, y=y_used, vals_used=vals_used, mask_used=mask_used, noise=noise,
+            job = dict(z_noisy=z_noisy, t=t, y=y_used, vals_used=vals_used, mask_used=mask_used, noise=target,
                        vals=cond, weight=weights, geom_lambda=lam, denom=geom_denom, tmax=T)
             names = [n for n, _ in model.named_parameters()]
             loss, out, per_sample, eps, geom = _NativeObjectiveFn.apply(model, names, job, *model.parameters())
@@ -1029,11 +1102,11 @@ class Diffuser:
                        else model(z_noisy, t, y_used))
                 eps, geom = res if isinstance(res, tuple) else (res, None)
                 use_geom = geom is not None and cond is not None
-                obj = _engine.objective_loss(eps, noise, t, weights, geom if use_geom else None,
+                obj = _engine.objective_loss(eps, target, t, weights, geom if use_geom else None,
                                              cond if use_geom else None, mask_used if use_geom else None, lam,
                                              geom_denom)
             loss, out, per_sample = obj.loss, obj._out, obj.per_sample
-        return TrainingLoss(loss, out[1], out[2], per_sample, t, drop, eps, geom)
+        return TrainingLoss(loss, out[1], out[2], per_sample, t, drop, eps, geom, target)
 
     # ---- one step -----------------------------------------------------------------------------
     def denoise(self, model, x, t):
@@ -1046,11 +1119,11 @@ class Diffuser:
             model.train()
             noise = self._step_noise(x)
             out = torch.empty_like(x)
-            model.native().step(x, out, t.to(x.device), None, 0, None, None, 0.0, tables, noise,
-                                seed=self._seed() if noise is None else 0)
+            self._native(model).step(x, out, t.to(x.device), None, 0, None, None, 0.0, tables, noise,
+                                     seed=self._seed() if noise is None else 0)
             return out
         with torch.no_grad():
-            eps = model(x, t)
+            eps = self._to_eps(model(x, t), None, 0.0, x, t)[0]
         model.train()
         noise = self._step_noise(x)
         return _engine.ddpm_update(x, eps, None, 0.0, t, tables, noise, seed=self._seed() if noise is None else 0)
@@ -1107,9 +1180,10 @@ class Diffuser:
                 x_in = x.contiguous() if rule == "ddpm" else x.float().contiguous()
                 out = torch.empty_like(x_in)
                 use = cond_vals is not None and cond_mask is not None
-                model.native().step(x_in, out, pos.to(x.device), None if y is None else y.to(x.device), null_label,
-                                    cond_vals if use else None, cond_mask if use else None, g, plan.tables, noise,
-                                    **plan.kwargs(g > 0, hist, seed=seed, phase=phase))
+                nm = self._native(model)
+                nm.step(x_in, out, pos.to(x.device), None if y is None else y.to(x.device), null_label,
+                        cond_vals if use else None, cond_mask if use else None, g, plan.tables, noise,
+                        **plan.kwargs(g > 0, hist, seed=seed, phase=phase))
                 return out
             if plan.cache > 1:
                 raise ValueError("cache_interval needs a dmx network on the GPU: only the native step can reuse "
@@ -1122,12 +1196,15 @@ class Diffuser:
                 if plan.geom is not None and ec is not None:  # the guided eps, then the gradient's share
                     grad = self._geom_loss_grad(model, x, t, y, cond_vals, cond_mask)
                     eu, ec, g = _engine.geom_mix(eu + g * (ec - eu), grad, plan.geom[0], plan.geom[1], pos), None, 0.0
+                eu, ec, g = self._to_eps(eu, ec, g, x, t)
             elif y is None:  # diff.py:152-156 literally, including its UnboundLocalError when y is given
                 y = torch.full((x.size(0),), null_label, device=x.device, dtype=torch.long)
                 eu, ec = model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask), None
         noise, seed = draw()
         if mirror and not isinstance(eu, torch.Tensor):
             raise TypeError(f"unsupported operand type(s) for *: 'Tensor' and '{type(eu).__name__}'")
+        if mirror:
+            eu, ec, g = self._to_eps(eu, ec, g, x, t)
         if rule == "ddpm":
             out = _engine.ddpm_update(x, eu, ec, g, pos, plan.tables, noise, seed=seed or 0)
         elif rule == "ddim":
@@ -1659,14 +1736,14 @@ class Diffuser:
             entered = known is not None or start is not None
             plan.sched = self.dpm_tables(mode[1], mode[2], dev, plan.start if entered else None)
         if geom is not None:
-            sig = self.geom_sig(dev) if rule == "ddpm" else plan.sched[1]
+            sig = self.geom_sig(dev) if rule == "ddpm" else self._sched_sig(plan.sched)
             plan.geom = (geom[cut].to(device=dev, dtype=torch.float32).contiguous(), sig)
         return plan
 
     def _device_chunks(self, nm, plan, x, y, null_label, vals, msk, hist, seed, bar=None):
         """The chunk runner of the device loop on x: Philox noise, hipGraph replay, the position scalar
         decremented in-graph — it runs on across a chunk's segments (plan.segments).  An empty shard
-        launches nothing."""
+        launches nothing.  nm: the native model, told this Diffuser's prediction by the caller (_native)."""
         t_dev = torch.full((1,), plan.start, device=x.device, dtype=torch.long)
 
         def run(i_from, i_to, x):
@@ -1702,7 +1779,7 @@ class Diffuser:
         if device_loop:
             x = x.contiguous().clone()
             seed = 0 if plan.rule in ("dpm", "invert") else self._seed()  # (these draw nothing)
-            run = self._device_chunks(model.native(), plan, x, y, null_label, vals.float().contiguous(),
+            run = self._device_chunks(self._native(model), plan, x, y, null_label, vals.float().contiguous(),
                                       msk.float().contiguous(), hist, seed, bar)
         else:
             def step_chunk(i_from, i_to, x):

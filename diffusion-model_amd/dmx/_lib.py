@@ -192,6 +192,9 @@ SIGNATURES = [
     ("dmx_train_backward_input", _I, [_P, _I64, _P, _P, _P, _P]),
     ("dmx_model_set_precision", _I, [_P, _I]),
     ("dmx_model_get_precision", _I, [_P]),
+    ("dmx_model_set_prediction", _I, [_P, _I, _P, _P, _I, _P]),
+    ("dmx_model_get_prediction", _I, [_P]),
+    ("dmx_pred_to_eps", _I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     ("dmx_model_range_check", _I, [_P, _I, ctypes.POINTER(_I), _P]),
     ("dmx_unet_forward", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_step", _I, [_P, ctypes.POINTER(StepArgs), _P]),
@@ -266,6 +269,7 @@ SIGNATURES = [
     ("dmx_optim_set_step", _I, [_P, _P, _I, _P]),
     ("dmx_optim_step", _I, [_P, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
     ("dmx_train_noise", _I, [ctypes.POINTER(NoiseArgs), _P]),
+    ("dmx_train_noise_target", _I, [ctypes.POINTER(NoiseArgs), _P, _P]),
     ("dmx_objective_loss", _I, [ctypes.POINTER(ObjectiveArgs), _P]),
     ("dmx_objective_seed", _I, [ctypes.POINTER(ObjectiveArgs), _P, _P, _P, _P]),
 ]

@@ -27,7 +27,7 @@ DMX_DEV float pick4(const float (&e)[4], int c) { return c == 0 ? e[0] : c == 1 
 // The lane's four products are accumulated with explicit FMAs from 0 in j order — what the plain
 // tail's `s += w * a` compiles to — so that no vectorisation of this longer body can split a
 // multiply from its add (tests/test_gpu_compose.py pins K = 1 against the plain step bit for bit).
-template <bool DDIM, bool DPM = false>
+template <bool DDIM, bool DPM = false, bool VPRED = false>  // (VPRED: a v-model's instances, as in kernels.h)
 static __global__ __launch_bounds__(256) void compose_tail4_kernel(const StepTailParams p, const ComposeParams q) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -66,12 +66,13 @@ static __global__ __launch_bounds__(256) void compose_tail4_kernel(const StepTai
 #pragma unroll
   for (int k = 2; k <= DMX_COMPOSE_MAX; ++k)
     if (k <= K) s = rnd(s + rnd(q.weight[(size_t)(k - 1) * p.B + n] * rnd(e[k] - e[0])));
-  const float eps = rnd(e[0] + s);
+  float eps = rnd(e[0] + s);
+  const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
+  if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t);  // a v-model
   flag_nonfinite(p.range_flag, eps);
   float nz = 0.f, kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
   const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
-  const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
   if (noisy) {
     if (p.noise != nullptr) {
       nz = p.noise[idx];

@@ -332,6 +332,13 @@ struct dmx_model {
     int64_t gen = 0;
   } dtag;
   int64_t weights_gen = 0;  // bumped by dmx_model_finalize / dmx_model_refresh
+  // What the network's output means (include/dmx.h dmx_model_set_prediction): DMX_PRED_EPS, or
+  // DMX_PRED_V with device copies of the caller's tables p_o | p_x in one allocation of 2 pred_T floats
+  // (captured graphs hold the pointer) and their values on the host, to tell a repeated call from a change.
+  int pred = DMX_PRED_EPS;
+  int pred_T = 0;
+  float* pred_tab = nullptr;
+  std::vector<float> pred_host;
 
   std::vector<std::pair<std::string, std::pair<const float*, size_t>>> taps;
   // Weight packing replay (dmx_model_refresh): every device-side repack / copy of the caller's
@@ -2290,6 +2297,7 @@ int dmx_model_destroy(dmx_model* m) {
     for (const Workspace* w : m->workspaces())
       if (w->mem) (void)hipFree(w->mem);
     if (m->dcache) (void)hipFree(m->dcache);
+    if (m->pred_tab) (void)hipFree(m->pred_tab);
     delete m->tape;
     delete m->vtape;
     delete m;
@@ -2453,6 +2461,59 @@ int dmx_model_set_precision(dmx_model* m, int prec) {
 }
 
 int dmx_model_get_precision(const dmx_model* m) { return m ? m->prec : -1; }
+
+int dmx_model_set_prediction(dmx_model* m, int kind, const float* p_o, const float* p_x, int T, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr, "null model");
+    const char* bad = set_prediction_error(kind, p_o, p_x, T);
+    REQUIRE(bad == nullptr, bad);
+    hipStream_t st = (hipStream_t)stream;
+    if (kind == DMX_PRED_EPS) {  // (the tables stay allocated: a later V call may find them unchanged)
+      if (m->pred != DMX_PRED_EPS) {
+        drop_graph(m);
+        m->dtag.valid = false;
+      }
+      m->pred = DMX_PRED_EPS;
+      return;
+    }
+    std::vector<float> host((size_t)2 * T);
+    HIPCHK(hipMemcpyAsync(host.data(), p_o, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(host.data() + T, p_x, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));  // (also: no launch of st still reads the tables replaced below)
+    const bool same_tab = m->pred_tab != nullptr && m->pred_T == T &&
+                          std::memcmp(host.data(), m->pred_host.data(), host.size() * sizeof(float)) == 0;
+    if (same_tab && m->pred == DMX_PRED_V) return;
+    drop_graph(m);
+    m->dtag.valid = false;
+    if (!same_tab) {
+      m->pred = DMX_PRED_EPS;  // until the new tables stand
+      if (m->pred_tab != nullptr && m->pred_T != T) {
+        HIPCHK(hipDeviceSynchronize());  // (steps of other streams may still read the old allocation)
+        HIPCHK(hipFree(m->pred_tab));
+        m->pred_tab = nullptr;
+        m->pred_T = 0;
+      }
+      if (m->pred_tab == nullptr) HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->pred_tab), host.size() * sizeof(float)));
+      HIPCHK(hipMemcpyAsync(m->pred_tab, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st));
+      HIPCHK(hipStreamSynchronize(st));  // (host is this call's local)
+      m->pred_T = T;
+      m->pred_host.swap(host);
+    }
+    m->pred = DMX_PRED_V;
+  });
+}
+
+int dmx_model_get_prediction(const dmx_model* m) { return m ? m->pred : -1; }
+
+int dmx_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                    const float* p_x, int T, int n, int c, int h, int w, float* eps_out, void* stream) {
+  return guarded([&] {
+    const char* bad = pred_to_eps_error(out, x, t, t_stride, p_o, p_x, T, n, c, h, w, eps_out);
+    REQUIRE(bad == nullptr, bad);
+    launch_pred_to_eps(out, x, t, t_stride, p_o, p_x, T, n, (int64_t)c * h * w, eps_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
 
 int dmx_model_range_check(dmx_model* m, int reset, int* flagged, void* stream) {
   return guarded([&] {
@@ -2778,7 +2839,18 @@ int dmx_train_noise(const dmx_noise_args* a, void* stream) {
   return guarded([&] {
     const char* bad = train_noise_error(a);
     REQUIRE(bad == nullptr, bad);
-    launch_train_noise(*a, (hipStream_t)stream);
+    launch_train_noise(*a, nullptr, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_train_noise_target(const dmx_noise_args* a, float* target, void* stream) {
+  return guarded([&] {
+    const char* bad = train_noise_error(a);
+    REQUIRE(bad == nullptr, bad);
+    REQUIRE(target != nullptr, "null target");
+    REQUIRE(target != a->z && target != a->noise && target != a->z_noisy, "target must not alias z / noise / z_noisy");
+    launch_train_noise(*a, target, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
   });
 }
@@ -2807,6 +2879,7 @@ int dmx_step_profile(dmx_model* m, const dmx_step_args* a, dmx_kernel_record* re
     REQUIRE(m != nullptr && recs != nullptr && n_out != nullptr, "null argument");
     validate(m, a, StepMode{}, false);
     hipStream_t st = (hipStream_t)stream;
+    check_prediction(m, *a, StepMode{}, st);
     ensure_planes(m, st);
     Prof prof;
     run_planned(m, st, [&](Run& R) { step_body(R, *a, StepMode{}); }, &prof);

@@ -5,12 +5,12 @@
 
 namespace dmx {
 
-void launch_train_noise(const dmx_noise_args& a, hipStream_t st) {
+void launch_train_noise(const dmx_noise_args& a, float* target, hipStream_t st) {
   const int64_t chw = (int64_t)a.C * a.h * a.w, Q = (chw + 3) / 4, total = (int64_t)a.B * Q;
   const unsigned blocks = (unsigned)((total + 255) / 256);
-  const void* ptrs[] = {a.z, a.noise, a.z_noisy};
-  if (objective_aligned16(chw, ptrs, 3)) train_noise_kernel<true><<<blocks, 256, 0, st>>>(a, chw, Q, total);
-  else train_noise_kernel<false><<<blocks, 256, 0, st>>>(a, chw, Q, total);
+  const void* ptrs[] = {a.z, a.noise, a.z_noisy, target};
+  if (objective_aligned16(chw, ptrs, 4)) train_noise_kernel<true><<<blocks, 256, 0, st>>>(a, target, chw, Q, total);
+  else train_noise_kernel<false><<<blocks, 256, 0, st>>>(a, target, chw, Q, total);
 }
 
 void launch_objective_loss(const dmx_objective_args& a, hipStream_t st) {

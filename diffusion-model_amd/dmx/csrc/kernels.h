@@ -715,7 +715,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* qkv, float*
 // (Philox noise, StepTailParams and the ddpm / ddim / dpm / invert element updates: tail_math.h, shared
 // with the composed tail of compose.h.)  INV: the DDIM-inversion instance — no noise; p.x is the
 // position's source latent (the engine passes the schedule's src), p.src receives y on adv rows.
-template <bool DDIM, bool DPM = false, bool INV = false>
+// VPRED: the instances of a v-model (p.p_o given) — the mixed output is converted to eps before the
+// update (tail_math.h tail_eps); the eps-model instances are the code they were before it existed.
+template <bool DDIM, bool DPM = false, bool INV = false, bool VPRED = false>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int n = blockIdx.y;
@@ -777,9 +779,10 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
     c1 = p.c1[t - 1], c2 = p.c2[t - 1], sd = p.sd[t - 1];
   }
   for (int c = 0; c < Co; ++c) {
-    const float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
-    flag_nonfinite(p.range_flag, eps);
+    float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
     const size_t idx = ((size_t)n * Co + c) * p.HW + pix;
+    if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
+    flag_nonfinite(p.range_flag, eps);
     if (INV) {
       const float y = invert_elem(p.x[idx], eps, ks, kd);
       p.x_out[idx] = y;
@@ -797,7 +800,7 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
 // coalesced, instead of 64 rows at a 256-byte lane stride); the 1x1-conv dot products are
 // reduced over the 16 lanes with DPP (fixed order), then lanes 0..3 of the group finish
 // channel c = lane (CFG mix, posterior mean, Philox noise, store).
-template <bool DDIM, bool DPM = false, bool INV = false>
+template <bool DDIM, bool DPM = false, bool INV = false, bool VPRED = false>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -837,7 +840,8 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
       nz = c == 0 ? r[0] : c == 1 ? r[1] : c == 2 ? r[2] : r[3];
     }
   }
-  const float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
+  float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
+  if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
   flag_nonfinite(p.range_flag, eps);
   if (INV) {
     const float y = invert_elem(p.x[idx], eps, p.i_x[t - 1], p.i_e[t - 1]);

@@ -9,6 +9,7 @@
 #include "igemm.h"
 #include "igemm_x3.h"
 #include "objective_args.h"
+#include "prediction_args.h"
 #include "tail_math.h"
 #include "tokmlp.h"
 
@@ -113,8 +114,13 @@ struct OptimLaunch {
 void launch_optim_step(const OptimLaunch& o, hipStream_t st);
 // The training objective (objective.h), k_objective.hip; arguments as checked by objective_args.h.
 // noise: one launch; loss: one block per sample, then the one-block finish; seed: one launch.
-void launch_train_noise(const dmx_noise_args& a, hipStream_t st);
+// (target: the v-prediction target of dmx_train_noise_target, or null)
+void launch_train_noise(const dmx_noise_args& a, float* target, hipStream_t st);
 void launch_objective_loss(const dmx_objective_args& a, hipStream_t st);
 void launch_objective_seed(const dmx_objective_args& a, const float* up, float* d_eps, float* d_geom, hipStream_t st);
+// v-prediction (prediction.h), k_prediction.hip; arguments as checked by prediction_args.h.
+// eps_out = p_o[t - 1] out + p_x[t - 1] x over [n][chw]; n * chw < 2^39; eps_out may alias out
+void launch_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                        const float* p_x, int T, int n, int64_t chw, float* eps_out, hipStream_t st);
 
 }  // namespace dmx

@@ -42,9 +42,11 @@ DMX_DEV bool draw_drop(uint64_t seed, uint64_t row, float p) {
 // noise the bits are torch's.  Grid cdiv(B * Q, 256).  Every thread of a sample derives the same t_n
 // and drop_n (each read, or drawn from the sample's global row, by its bit of a.draw); the thread of quad 0 stores them and the
 // label, and the sample's threads share its gd value / mask columns (column j: quad j mod Q).
+// target (null: not written): the v-prediction target sa[t] noise - s1[t] z of the same operands, two
+// products and a difference with one rounding each — one more store per quad.
 template <bool VEC>
-static __global__ __launch_bounds__(256) void train_noise_kernel(const dmx_noise_args a, int64_t chw, int64_t Q,
-                                                                 int64_t total) {
+static __global__ __launch_bounds__(256) void train_noise_kernel(const dmx_noise_args a, float* target, int64_t chw,
+                                                                 int64_t Q, int64_t total) {
   const int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (id >= total) return;
   const int64_t n = id / Q, q = id - n * Q;
@@ -77,13 +79,20 @@ static __global__ __launch_bounds__(256) void train_noise_kernel(const dmx_noise
     for (int k = 0; k < 4; ++k) o[k] = rnd(ca * z[k]) + rnd(cb * nz[k]);
     st4g(a.z_noisy + base, o);
     if (draws_nz) st4g(a.noise + base, nz);
+    if (target != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = rnd(ca * nz[k]) - rnd(cb * z[k]);
+      st4g(target + base, o);
+    }
   } else {
     const int64_t left = chw - 4 * q;
     const int cnt = left < 4 ? (int)left : 4;
     for (int k = 0; k < cnt; ++k) {
       const float e = draws_nz ? nz[k] : a.noise[base + k];
-      a.z_noisy[base + k] = rnd(ca * a.z[base + k]) + rnd(cb * e);
+      const float zk = a.z[base + k];
+      a.z_noisy[base + k] = rnd(ca * zk) + rnd(cb * e);
       if (draws_nz) a.noise[base + k] = e;
+      if (target != nullptr) target[base + k] = rnd(ca * e) - rnd(cb * zk);
     }
   }
 }

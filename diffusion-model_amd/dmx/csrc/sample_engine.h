@@ -67,12 +67,25 @@ static void set_sched(StepTailParams& p, const dmx_invert_sched& iv) {
 
 // The tail's launch: the instance of the update rule; head4 = the network head path with Co = 4
 // (16 pixels per block), else one pixel per thread; comp: the composed head4 tail (launch.h).
+// p.p_o given (a v-model): the VPRED instances of the same kernels.
 static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st,
                              const ComposeParams* comp = nullptr) {
   if (comp != nullptr) {
     if (!head4) throw Error(DMX_E_INTERNAL, "the composed tail is the Co = 4 head tail");
     if (rule == Rule::INVERT) throw Error(DMX_E_INTERNAL, "there is no composed inversion tail");
     launch_compose_tail4(p, *comp, rule == Rule::DDIM, rule == Rule::DPM, grid, st);
+  } else if (p.p_o != nullptr) {  // a v-model: the converting instances
+    if (!head4) {
+      if (rule == Rule::INVERT) step_tail_kernel<false, false, true, true><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DPM) step_tail_kernel<false, true, false, true><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail_kernel<true, false, false, true><<<grid, 256, 0, st>>>(p);
+      else step_tail_kernel<false, false, false, true><<<grid, 256, 0, st>>>(p);
+    } else {
+      if (rule == Rule::INVERT) step_tail4_kernel<false, false, true, true><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DPM) step_tail4_kernel<false, true, false, true><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail4_kernel<true, false, false, true><<<grid, 256, 0, st>>>(p);
+      else step_tail4_kernel<false, false, false, true><<<grid, 256, 0, st>>>(p);
+    }
   } else if (!head4) {
     if (rule == Rule::INVERT) step_tail_kernel<false, false, true><<<grid, 256, 0, st>>>(p);
     else if (rule == Rule::DPM) step_tail_kernel<false, true><<<grid, 256, 0, st>>>(p);
@@ -196,9 +209,15 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   p.seed = a.seed;
   p.sample_offset = a.sample_offset;
   p.range_flag = m->range_flag;
+  if (m->pred == DMX_PRED_V) {  // every tail below converts its mixed output (tail_math.h tail_eps)
+    p.p_o = m->pred_tab;
+    p.p_x = m->pred_tab + m->pred_T;
+    p.pred_T = m->pred_T;
+    p.x_net = a.x_in;  // the buffer the trunk read: in an inversion's refinement rows y, not the source latent
+  }
   if (rule == Rule::INVERT) {
     set_sched(p, *mode.invert);
-    p.x = mode.invert->src;  // (the latent the network saw, a.x_in, is not an operand of the update)
+    p.x = mode.invert->src;  // (the latent the network saw, a.x_in, is an operand of the update in v-mode alone)
   } else if (rule == Rule::DPM) {
     set_sched(p, *mode.dpm);
   } else if (rule == Rule::DDIM) {
@@ -390,6 +409,24 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
   }
 }
 
+// A v-model's step or loop (validated) converts with the rows t - 1 of the model's tables: the largest
+// network timestep its schedule names must lie inside them.  The DDPM rule names 1..T of its own
+// tables; a strided rule's timesteps are its t_map, device memory, read back here — one small copy
+// and a wait for st per call, in v-mode only.  Nothing has been launched when this throws.
+static void check_prediction(const dmx_model* m, const dmx_step_args& a, const StepMode& mode, hipStream_t st) {
+  if (m->pred != DMX_PRED_V) return;
+  int64_t t_max = a.T;
+  if (mode.rule() != Rule::DDPM) {
+    std::vector<int64_t> tm((size_t)mode.positions(a));
+    HIPCHK(hipMemcpyAsync(tm.data(), mode.t_map(), tm.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    t_max = 0;
+    for (int64_t v : tm) t_max = v > t_max ? v : t_max;
+  }
+  const char* bad = prediction_range_error(t_max, m->pred_T);
+  REQUIRE(bad == nullptr, bad);
+}
+
 // ---------------------------------------------------------------------------
 // Feature caching: the model's deep-feature buffer and what it belongs to
 // ---------------------------------------------------------------------------
@@ -450,6 +487,7 @@ static void tag_dcache(dmx_model* m, const dmx_step_args& a) {
 // ---------------------------------------------------------------------------
 static void sample_step(dmx_model* m, const dmx_step_args* a, const StepMode& mode, hipStream_t st) {
   validate(m, a, mode, false);
+  check_prediction(m, *a, mode, st);
   const StepMode::Kind kind = mode.cache_kind(0);
   if (kind == StepMode::REUSE) check_dcache(m, *a);  // (before anything is launched)
   ensure_planes(m, st);
@@ -561,6 +599,7 @@ static void sample_loop(dmx_model* m, const dmx_step_args* a, const StepMode& mo
                         hipStream_t st) {
   validate(m, a, mode, true);
   REQUIRE(steps >= 0, "steps must be >= 0");
+  check_prediction(m, *a, mode, st);
   ensure_planes(m, st);
   if (mode.geom != nullptr) ensure_train(m, st);  // (packs and synchronises: before any capture)
   int64_t* tdev = const_cast<int64_t*>(a->t);

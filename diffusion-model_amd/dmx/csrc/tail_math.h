@@ -119,7 +119,25 @@ struct StepTailParams {
   // latent the network saw is not read), src (x's shape) is written where adv != 0
   const float* i_x; const float* i_e; const int* adv;
   float* src;
+  // v-prediction (include/dmx.h dmx_model_set_prediction): p_o null => the mixed output is eps and the
+  // launchers pick the plain instances; else their VPRED instances, which convert it:
+  // p_o / p_x [pred_T], index = the row's network timestep - 1, and x_net (x's shape) is the latent the
+  // network was evaluated at — p.x itself except in the inversion instance, whose p.x is the source latent
+  const float* p_o; const float* p_x; const float* x_net;
+  int pred_T;
 };
+
+// v-prediction -> eps (Salimans & Ho 2022, v = sqrt(ab) noise - sqrt(1-ab) x0, so with x = sqrt(ab) x0 +
+// sqrt(1-ab) noise: eps = sqrt(ab) v + sqrt(1-ab) x): two products and a sum, one rounding each.
+DMX_DEV float pred_to_eps_elem(float out, float x_net, float po, float px) { return rnd(po * out) + rnd(px * x_net); }
+
+// The tails' use of it, in their VPRED instances (launched where p.p_o is given): the mixed network
+// output of element idx, converted once.  tnet: the row's network timestep — t itself in the DDPM rule,
+// t_map[pos - 1] in the strided ones — clamped to the tables like every table read.
+DMX_DEV float tail_eps(const StepTailParams& p, float out, size_t idx, int64_t tnet) {
+  const int r = (int)(tnet < 1 ? 1 : (tnet > p.pred_T ? p.pred_T : tnet)) - 1;
+  return pred_to_eps_elem(out, p.x_net[idx], p.p_o[r], p.p_x[r]);
+}
 
 DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float nz) {
   const float mu = rnd(x - rnd(c1 * eps)) / c2;

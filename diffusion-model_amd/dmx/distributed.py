@@ -258,7 +258,7 @@ class ShardedCondSampler:
                 raise ValueError("z_shape 省略時は vae が必要です。")
             z_shape = d._latent_shape(self.vae, dummy_input_hw, dev)
         C, H, W = z_shape
-        nm = self.model.native() if e > s else None
+        nm = d._native(self.model) if e > s else None  # (with the Diffuser's prediction set)
         guard = d._guard_target(self.model) if nm is not None else None
         x = torch.randn((B, C, H, W))[s:e].to(dev).contiguous()  # x_T (diff.py:327), global draw
         # the single-process sampler's plan for this shard's rows; x is its rows of e0

@@ -119,6 +119,39 @@ class NativeModel:
         code = self.PRECISIONS[prec] if isinstance(prec, str) else int(prec)
         check(self.lib.dmx_model_set_precision(self.handle, code))
 
+    PREDICTIONS = {"eps": 0, "v": 1}
+
+    def set_prediction(self, kind, p_o=None, p_x=None) -> None:
+        """What the network predicts (include/dmx.h dmx_model_set_prediction): "eps" (the default), or "v"
+        with the (T,) fp32 tables p_o = sqrt(ab), p_x = sqrt(1 - ab) (Diffuser.noise_tables) — every step
+        and loop then converts its mixed output to eps before the update.  The library copies the tables;
+        a change of kind or tables drops the captured graphs and the cached deep feature.  The pair last
+        given is remembered by identity, so repeating a call costs nothing."""
+        if kind not in self.PREDICTIONS:
+            raise ValueError(f'prediction must be "eps" or "v" (got {kind!r})')
+        last = getattr(self, "_prediction", ("eps", None, None))
+        if last[0] == kind and (kind == "eps" or (last[1] is p_o and last[2] is p_x)):
+            return
+        po_c = px_c = None
+        T = 0
+        if kind == "v":
+            if p_o is None or p_x is None:
+                raise ValueError('prediction "v" needs the p_o and p_x tables (Diffuser.noise_tables)')
+            po_c = p_o.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+            px_c = p_x.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+            T = int(po_c.numel())
+            if T < 1 or px_c.numel() != T:
+                raise ValueError(f"p_o and p_x must be equal non-empty tables (got {po_c.numel()}, {px_c.numel()})")
+        with torch.cuda.device(self.device):
+            check(self.lib.dmx_model_set_prediction(self.handle, self.PREDICTIONS[kind], _ptr(po_c), _ptr(px_c), T,
+                                                    ctypes.c_void_p(_stream(self.device))))
+        self._prediction = (kind, p_o, p_x)  # (the tensors are kept: their identity stays valid)
+
+    @property
+    def prediction(self) -> str:
+        code = self.lib.dmx_model_get_prediction(self.handle)
+        return {v: k for k, v in self.PREDICTIONS.items()}[code]
+
     def range_tripped(self, reset: bool = True) -> bool:
         """True when an output kernel saw a non-finite value since the last reset (include/dmx.h
         dmx_model_range_check: the split-precision range guard).  Synchronises the current stream."""
@@ -858,8 +891,44 @@ def geom_mix(eps, grad, scale, sig, pos):
     return out
 
 
+def pred_to_eps(out, x, t, p_o, p_x, inplace=False):
+    """A foreign v-model's (mixed) output as eps (include/dmx.h dmx_pred_to_eps) -> eps:
+        eps = p_o[t - 1] out + p_x[t - 1] x        (torch's bits: two products and a sum, no FMA)
+    out, x: (n,c,h,w) on the GPU, any c, h, w >= 1, x the latent the model was evaluated at; t: (n,) network
+    timesteps (any stride) or one value for every sample, clamped to [1, T] for the table reads; p_o, p_x:
+    (T,) fp32 tables sqrt(ab), sqrt(1 - ab) (Diffuser.noise_tables).  inplace: the result is written over
+    `out` (a contiguous fp32 tensor, e.g. a network's fresh output) and `out` is returned, else a new tensor.
+    Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
+    lib = _lib.load()
+    require_cuda(out, "out")
+    dev = out.device
+    o_c = out.detach().to(dtype=torch.float32).contiguous()
+    x_c = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if o_c.dim() != 4 or tuple(x_c.shape) != tuple(o_c.shape) or min(o_c.shape) < 1:
+        raise ValueError(f"out / x must be equal non-empty (n,c,h,w) tensors (got {tuple(out.shape)}, {tuple(x.shape)})")
+    n, c, h, w = o_c.shape
+    po_c = p_o.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    px_c = p_x.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    T = int(po_c.numel())
+    if T < 1 or px_c.numel() != T:
+        raise ValueError(f"p_o and p_x must be equal non-empty tables (got {po_c.numel()}, {px_c.numel()})")
+    t_c = torch.as_tensor(t).to(device=dev, dtype=torch.long).reshape(-1)
+    if t_c.numel() not in (1, n):
+        raise ValueError(f"t has {t_c.numel()} entries for a batch of {n}")
+    stride = 0 if t_c.numel() == 1 else int(t_c.stride(0))
+    if stride < 1 and t_c.numel() > 1:
+        t_c, stride = t_c.contiguous(), 1
+    if inplace and (o_c.data_ptr() != out.data_ptr() or out.requires_grad or o_c.data_ptr() == x_c.data_ptr()):
+        raise ValueError("inplace needs `out` to be a contiguous fp32 tensor without grad, and not x itself")
+    eps = out if inplace else torch.empty_like(o_c)
+    with torch.cuda.device(dev):
+        check(lib.dmx_pred_to_eps(_ptr(o_c), _ptr(x_c), _ptr(t_c), stride, _ptr(po_c), _ptr(px_c), T, n, c, h, w,
+                                  _ptr(eps), ctypes.c_void_p(_stream(dev))))
+    return eps
+
+
 def train_noise(z, sa, s1, t=None, noise=None, drop=None, y=None, null_label=0, vals=None, mask=None,
-                cfg_drop_prob=0.0, seed=0, sample_offset=0):
+                cfg_drop_prob=0.0, seed=0, sample_offset=0, target=None):
     """The front half of a training iteration (include/dmx.h dmx_train_noise; train_latent_cond.py:136-145) ->
     (z_noisy, noise, t, drop, y_used, vals_used, mask_used):
         z_noisy = sa[t - 1] z + s1[t - 1] noise     (torch's bits: two products and a sum, no FMA)
@@ -869,6 +938,10 @@ def train_noise(z, sa, s1, t=None, noise=None, drop=None, y=None, null_label=0, 
     device by Philox under `seed` from the rows' global indices sample_offset + n (t uniform on [1, T],
     drop = u < cfg_drop_prob, noise standard normal), so a shard of a batch draws the batch's rows.
     y, vals / mask may be None (their outputs are then None).  No host synchronisation.
+    target = True, or a contiguous fp32 tensor of z's shape on z's device to write into (include/dmx.h
+    dmx_train_noise_target): the same launch also stores the v-prediction target
+        target = sa[t - 1] noise - s1[t - 1] z      (torch's bits: two products and a difference, no FMA)
+    and the result gains it as an eighth entry; the other seven keep the bits of the call without it.
     Operands stay bound to locals for the duration of the launch, as in ddpm_update."""
     lib = _lib.load()
     require_cuda(z, "z")
@@ -922,12 +995,23 @@ def train_noise(z, sa, s1, t=None, noise=None, drop=None, y=None, null_label=0, 
         gd = int(v_c.shape[1])
         v_u, m_u = torch.empty_like(v_c), torch.empty_like(m_c)
     out = torch.empty_like(z_c)
+    tg = None
+    if target is True:
+        tg = torch.empty_like(z_c)
+    elif target is not None and target is not False:
+        tg = target
+        if (not isinstance(tg, torch.Tensor) or tg.dtype != torch.float32 or tg.device != dev
+                or tuple(tg.shape) != tuple(z_c.shape) or not tg.is_contiguous()):
+            raise ValueError(f"target must be True or a contiguous fp32 {tuple(z_c.shape)} tensor on {dev}")
     a = _lib.NoiseArgs(z=_ptr(z_c), sa=_ptr(sa_c), s1=_ptr(s1_c), T=T, draw=draw, t=_ptr(t_c), noise=_ptr(nz_c),
                        drop=_ptr(d_c), seed=int(seed) & (2 ** 64 - 1), sample_offset=int(sample_offset),
                        cfg_drop_prob=p, gd=gd, y=_ptr(y_c), null_label=int(null_label), vals=_ptr(v_c),
                        mask=_ptr(m_c), z_noisy=_ptr(out), y_used=_ptr(y_u), vals_used=_ptr(v_u),
                        mask_used=_ptr(m_u), B=B, C=C, h=h, w=w)
     with torch.cuda.device(dev):
+        if tg is not None:
+            check(lib.dmx_train_noise_target(ctypes.byref(a), _ptr(tg), ctypes.c_void_p(_stream(dev))))
+            return out, nz_c, t_c, d_c, y_u, v_u, m_u, tg
         check(lib.dmx_train_noise(ctypes.byref(a), ctypes.c_void_p(_stream(dev))))
     return out, nz_c, t_c, d_c, y_u, v_u, m_u
 

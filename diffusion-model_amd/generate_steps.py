@@ -223,7 +223,7 @@ def save_reverse_steps_for_csv_row(
     plan = diffuser._plan(x, None, guidance_scale)  # the DDPM walk with CFG
     if device_loop:
         x = x.contiguous().clone()  # stepped in place: the captured graph keeps its pointer
-        step_one = diffuser._device_chunks(model_noise.native(), plan, x, y, null_label, vals.float().contiguous(),
+        step_one = diffuser._device_chunks(diffuser._native(model_noise), plan, x, y, null_label, vals.float().contiguous(),
                                            mask.float().contiguous(), None, diffuser._seed())
 
     def run(i_from, i_to, x):

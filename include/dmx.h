@@ -99,6 +99,28 @@ int dmx_model_refresh(dmx_model* m, void* stream);
  * 2 = fp16 operands (BASELINE config 4: one MFMA, fp32 accumulate, fp32 norms/softmax/scheduler). */
 int dmx_model_set_precision(dmx_model* m, int prec);
 int dmx_model_get_precision(const dmx_model* m);
+/* What the network's output means.  DMX_PRED_EPS (the default): the noise eps.  DMX_PRED_V: the
+ * velocity v = sqrt(ab_t) noise - sqrt(1 - ab_t) x0 (Salimans & Ho 2022).  A v-model's step mixes in
+ * output space (CFG, composition, perturbed branch, CFG rescale, geometry guidance) and then converts
+ * once per element, immediately before the rule's update:
+ *   eps = p_o[t - 1] * out + p_x[t - 1] * x_net       p_o = sqrt(ab), p_x = sqrt(1 - ab), [T] fp32
+ * two products and a sum, one IEEE rounding each, never contracted; t is the row's network timestep
+ * (clamped to [1, T] for the table read) and x_net the latent the network was evaluated at.  p_o /
+ * p_x are device pointers tabulated by the caller; the model keeps device copies (the call waits for
+ * `stream`).  Every dmx_step* / dmx_sample_loop* entry honours the setting; a step or loop whose
+ * schedule names a timestep above T is DMX_E_ARG before anything is launched (the strided rules'
+ * t_map is read back for that: one small device-to-host copy per call, in v-mode only).  A change of
+ * kind or tables drops every captured graph and the cached deep feature.  DMX_E_ARG: an unknown kind,
+ * DMX_PRED_V with a NULL table, or T < 1; DMX_PRED_EPS reads neither table nor T. */
+#define DMX_PRED_EPS 0
+#define DMX_PRED_V 1
+int dmx_model_set_prediction(dmx_model* m, int kind, const float* p_o, const float* p_x, int T, void* stream);
+int dmx_model_get_prediction(const dmx_model* m);
+/* The conversion alone, for a foreign v-model: eps_out = p_o[t_n - 1] * out + p_x[t_n - 1] * x with
+ * the arithmetic above, t (n,) int64 read at n * t_stride (0: one value for all) and clamped to
+ * [1, T]; out, x, eps_out NCHW (n,c,h,w), any c*h*w; eps_out may alias out (not x). */
+int dmx_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                    const float* p_x, int T, int n, int c, int h, int w, float* eps_out, void* stream);
 /* Range guard of the split-precision modes (1, 2): an operand beyond the f16 range turns a
  * network output (eps / decoded pixel / encoder head) non-finite, and the output kernels then
  * raise a sticky per-model flag.  Reads it (synchronising `stream`), optionally clearing it;
@@ -721,6 +743,12 @@ typedef struct dmx_noise_args {
 } dmx_noise_args;
 
 int dmx_train_noise(const dmx_noise_args* a, void* stream);
+/* dmx_train_noise plus the v-prediction target of the same draws, in the same launch:
+ *   target = sa[t_n - 1] * noise - s1[t_n - 1] * z          ((B,C,h,w); two products and a difference,
+ *                                                             one rounding each, never contracted)
+ * Every other output has dmx_train_noise's bits.  dmx_objective_loss / dmx_objective_seed then take
+ * `target` where they take `noise`. */
+int dmx_train_noise_target(const dmx_noise_args* a, float* target, void* stream);
 
 /* dmx_objective_loss: with N = C*h*w, w_n = weight[t_n - 1] (weight == NULL: 1), g / v / m the rows of
  * geom / vals / mask (geom == NULL: no geometry term, gd not read)

@@ -13,7 +13,10 @@ clock per iteration is printed beside it.  Per loop: the median over the turns, 
 (the turn-to-turn spread).  The native leg is skipped where Diffuser.training_loss does not exist, so
 the same file run on an older checkout gives that checkout's torch-op loop.
 
-    python tools/objective_bench.py [--steps 20] [--turns 9] [--once LEG] [--json FILE]
+    python tools/objective_bench.py [--steps 20] [--turns 9] [--once LEG] [--json FILE] [--prediction v]
+
+--prediction v adds a third loop that takes its turns with the other two: the native objective of a
+v-model (Diffuser(prediction="v")), whose noising launch stores one more latent-sized tensor, the target.
 
 --once LEG runs one warmed-up iteration of one leg ("torch" or "native") between two synchronisations
 and nothing else: the region to look at in a kernel trace of its own run.
@@ -34,7 +37,7 @@ for p in (os.path.join(REPO, "diffusion-model_amd"), REPO):
         sys.path.insert(0, p)
 
 
-def make_legs(dev, B=32, hw=28, lam=0.5, p_drop=0.1):
+def make_legs(dev, B=32, hw=28, lam=0.5, p_drop=0.1, prediction="eps"):
     import diff
     import dmx.optim as O
     from dmx import synth
@@ -65,7 +68,7 @@ def make_legs(dev, B=32, hw=28, lam=0.5, p_drop=0.1):
         loss.backward()
         opt.step()
 
-    def native():
+    def native(d=d):
         res = d.training_loss(model, z, classes, vals, mask, geom_lambda=lam, cfg_drop_prob=p_drop)
         opt.zero_grad(set_to_none=True)
         res.loss.backward()
@@ -74,6 +77,9 @@ def make_legs(dev, B=32, hw=28, lam=0.5, p_drop=0.1):
     legs = {"torch": ("torch-op loop", torch_loop)}
     if hasattr(diff.Diffuser, "training_loss"):
         legs["native"] = ("native objective", native)
+        if prediction == "v":
+            dv = diff.Diffuser(1000, device=dev, prediction="v")
+            legs["native_v"] = ("native objective v", lambda: native(dv))
     return legs
 
 
@@ -94,13 +100,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=20, help="iterations per turn")
     ap.add_argument("--turns", type=int, default=9)
-    ap.add_argument("--once", default=None, choices=["torch", "native"])
+    ap.add_argument("--once", default=None, choices=["torch", "native", "native_v"])
+    ap.add_argument("--prediction", default="eps", choices=["eps", "v"])
     ap.add_argument("--json", default=None, help="also write the records to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("objective_bench needs the GPU: there is nothing to time on the host")
     dev = torch.device("cuda:0")
-    legs = make_legs(dev)
+    legs = make_legs(dev, prediction="v" if args.once == "native_v" else args.prediction)
     for _, fn in legs.values():  # warm-up: code objects, the tape and backward arenas, the allocator
         for _ in range(3):
             fn()

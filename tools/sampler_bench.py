@@ -1,8 +1,12 @@
 """Few-step sampling (strided DDIM, DPM-Solver++(2M)) against the full DDPM walk on one MI355X: prints
 one JSON line.
 
-  python tools/sampler_bench.py [--rounds 5]
+  python tools/sampler_bench.py [--rounds 5] [--prediction eps|v]
       [--groups loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end,cache]
+
+--prediction v runs every group with the model read as a v-predictor (Diffuser(prediction="v")): the same
+launches, each tail converting its mixed output to eps before the update.  Run it beside the default on
+one build for the cost of the conversion.
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -415,7 +419,7 @@ def cache_legs(nm, d, dev, rounds):
     return out
 
 
-def cache_end_to_end(model, dev):
+def cache_end_to_end(model, dev, prediction="eps"):
     """sample_latent_cond(ddpm, T = 1000) with the decode: plain, cache_interval = 3, plain again."""
     import diff
     from dmx import synth
@@ -429,7 +433,7 @@ def cache_end_to_end(model, dev):
     vals, mask = vals[order].contiguous(), mask[order].contiguous()
     kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
               cond_mask=mask)
-    d = diff.Diffuser(T, device=dev)
+    d = diff.Diffuser(T, device=dev, prediction=prediction)
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
@@ -447,7 +451,7 @@ def cache_end_to_end(model, dev):
     return out
 
 
-def end_to_end(model, dev):
+def end_to_end(model, dev, prediction="eps"):
     import diff
     from dmx import synth
     from models.vae import VAE
@@ -460,7 +464,7 @@ def end_to_end(model, dev):
     vals, mask = vals[order].contiguous(), mask[order].contiguous()
     kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
               cond_mask=mask)
-    d = diff.Diffuser(T, device=dev)
+    d = diff.Diffuser(T, device=dev, prediction=prediction)
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
@@ -508,6 +512,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--groups", default="loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end")
+    ap.add_argument("--prediction", default="eps", choices=["eps", "v"], help="what the network's output is read as")
     args = ap.parse_args()
     groups = args.groups.split(",")
     if not torch.cuda.is_available():
@@ -521,16 +526,21 @@ def main():
     model.load_state_dict(synth.unet_cond_geom_weights(0))
     model.to(dev).eval()
     res = {"workload": f"B={B}, {HW}x{HW}x4, CFG {GUIDANCE}, device noise, synthetic weights; T={T}, S={S}",
-           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds}
+           "device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "prediction": args.prediction}
+
+    def diffuser():  # (the loop legs drive the native model themselves: it is told the prediction here)
+        d = diff.Diffuser(T, device=dev, prediction=args.prediction)
+        d._set_prediction(model.native())
+        return d
     for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs),
                      ("composed_loops", composed_legs), ("pag_loops", pag_legs)):
         if name in groups:
-            res[name] = fn(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
+            res[name] = fn(model.native(), diffuser(), dev, args.rounds)
     if "end_to_end" in groups:
-        res["end_to_end"] = end_to_end(model, dev)
+        res["end_to_end"] = end_to_end(model, dev, args.prediction)
     if "cache" in groups:
-        res["cache"] = cache_legs(model.native(), diff.Diffuser(T, device=dev), dev, args.rounds)
-        res["cache"]["ddpm_T1000_end_to_end"] = cache_end_to_end(model, dev)
+        res["cache"] = cache_legs(model.native(), diffuser(), dev, args.rounds)
+        res["cache"]["ddpm_T1000_end_to_end"] = cache_end_to_end(model, dev, args.prediction)
     print(json.dumps(res))
 
 
