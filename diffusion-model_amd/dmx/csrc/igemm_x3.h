@@ -676,7 +676,9 @@ DMX_DEV float max_halves(float v) {
 
 // v_mfma_f32_32x32x16_f16 with its accumulator input (the loop-invariant -mref) in other registers
 // than its result: the builtin's tied form copies negm into the result registers every chunk
-// (eight v_mov_b64 on the VALU issue port this kernel is bound by).
+// (eight v_mov_b64 on the VALU issue port this kernel is bound by).  Nothing pads an MFMA inside an asm
+// string: its result may only feed the next MFMA whole as C (an accumulate chain needs no wait states),
+// never a VALU instruction.
 DMX_DEV floatx16 mfma_untied(half8 a, half8 b, floatx16 c) {
   floatx16 d;
   asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "v"(b), "v"(c));
@@ -792,7 +794,9 @@ __global__ __launch_bounds__(NW * 64) void attention16_kernel(const float* qkv, 
           sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, ql, sc, 0, 0, 0);
           sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh, sc, 0, 0, 0);
         } else {
-          sc = mfma_untied(kh, qh, negm);
+          // (the builtin, not mfma_untied: here the VALU reads and masks sc next, and only the compiler
+          // pads an MFMA result for that; with L < 32 the unpadded form lost the mask of the keys >= L)
+          sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh, negm, 0, 0, 0);
         }
       }
       const int nvalid = L - c0;

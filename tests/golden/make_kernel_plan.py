@@ -34,8 +34,11 @@ def main() -> None:
         for B, hw in T.SHAPES:
             plans[T.case_id(prec, B, hw)] = T.record_plan(model, diffuser, prec, B, hw, dev)
             print(T.case_id(prec, B, hw), len(plans[T.case_id(prec, B, hw)]), "launches", flush=True)
-    note = ("Recorded by tests/golden/make_kernel_plan.py with the library built from the parent of the "
-            "conv-plan refactor (DMX_LIB=%s), not from the code under test." % os.environ.get("DMX_LIB", "libdmx.so"))
+    note = ("Recorded by tests/golden/make_kernel_plan.py, never from the code under test (DMX_LIB=%s): the B1, B5 "
+            "and B32 32x32, B32 28x28 and B3 16x16 plans with the library built from the parent of the conv-plan "
+            "refactor; the B17 32x32 and B21 40x40 plans, added with tests/test_gpu_forward_classes.py, with the "
+            "library built from the parent of that change, which reproduced the earlier plans exactly."
+            % os.environ.get("DMX_LIB", "libdmx.so"))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(HERE, "kernel_plan.json")
     with open(out, "w") as f:
         json.dump({"note": note, "plans": plans}, f, indent=0, separators=(",", ":"))

@@ -317,7 +317,9 @@ def test_rows_do_not_depend_on_the_batch(model, cuda):
 
 # ---- 5: the large batch class -----------------------------------------------------------------------------
 def test_large_batch_class_vs_oracle(model, cuda, unet_sd):
-    """B = 32, K = 2: N = 96 rows run in the 128-sample class (Winograd), the shared prefix of 32 on the halo path."""
+    """B = 32, K = 2: N = 96 rows run in the 128-sample class (Winograd), the shared prefix of 32 on the split
+    implicit GEMMs (igemm_x3_kernel: a prefix of 32 samples is below igemm_halo_kernel's 256-block threshold,
+    tests/golden/kernel_plan.json x3-B32-32x32)."""
     import diff
     d = diff.Diffuser(1000, device=cuda)
     err = composed_step_vs_oracle(model.native(), d, cuda, unet_sd, "ddim", "dropped2", 32, 32)

@@ -4,7 +4,8 @@ Model.step_profile returns the ordered (kernel, layer) labels of one eager CFG s
 tests/golden/kernel_plan.json holds that sequence for the default conditional U-Net in the three
 precision modes, at batches and maps that cover every batch class and low-resolution split
 (tests/golden/make_kernel_plan.py: recorded with the library built from the commit BEFORE the
-conv-plan refactor, never from the code under test).  The library must reproduce each sequence
+conv-plan refactor; the (17, 32) and (21, 40) plans, added later, from the commit before their addition,
+whose library reproduced the earlier plans exactly; never from the code under test).  The library must reproduce each sequence
 exactly; timings are ignored.  Arithmetic is pinned elsewhere (test_gpu_parity.py, goldens)."""
 import json
 import os
@@ -17,8 +18,9 @@ pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_plan.json")
 PRECISIONS = ["x3", "fp32", "f16"]
 # (B, H = W): single sample; small class, ragged; the >= 64-sample class after CFG doubling on the
-# 32- and 28-wide latents; small maps (the low-resolution paths split differently)
-SHAPES = [(1, 32), (5, 32), (32, 32), (32, 28), (3, 16)]
+# 32- and 28-wide latents; small maps (the low-resolution paths split differently); the 32..63-sample
+# class after CFG doubling (igemm_halo_kernel at up3.0); 42 samples on 40-wide maps (igemm_pp_kernel)
+SHAPES = [(1, 32), (5, 32), (32, 32), (32, 28), (3, 16), (17, 32), (21, 40)]
 
 
 def case_id(prec, B, hw):
