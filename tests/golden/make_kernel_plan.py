@@ -28,7 +28,7 @@ from dmx import synth  # noqa: E402
 
 def main() -> None:
     dev = torch.device("cuda:0")
-    model, diffuser = T.make_model(dev, synth.unet_cond_geom_weights(0))
+    model, diffuser = T.model_and_diffuser(dev, synth.unet_cond_geom_weights(0))
     plans = {}
     for prec in T.PRECISIONS:
         for B, hw in T.SHAPES:

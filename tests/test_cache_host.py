@@ -26,12 +26,7 @@ import torch.nn.functional as F
 import diff
 from conftest import REPO
 from oracle import ref
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+from oracle.rules import rel
 
 
 # ---- the oracle of a cached step -------------------------------------------------------------------

@@ -13,15 +13,13 @@ oracle's cached eps differs from its full eps by 0.28 - 0.54 and the x_out built
 4.2e-2.  Trajectories: DDIM S = 6 32x32 N = 3 2.0e-6, N = 2 1.9e-6, 28x28 N = 3 1.8e-6, N = 2 1.8e-6;
 DPM-Solver++(2M) N = 2 1.9e-6; DDPM T = 12 host noise N = 4 6.5e-7 (cached against uncached oracle 0.030 -
 0.097).  Chunks of 4, S = 10, N = 3: 1.5e-6, and the same with one chunk replayed in fp32."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
 from oracle import ref
-from test_cache_host import CachedEps, cached_trajectory, refresh_positions, rel, step_inputs
+from oracle.rules import ddim_update, dpm_update, rel
+from support import make_model, on, run_worker
+from test_cache_host import CachedEps, cached_trajectory, refresh_positions, step_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -32,37 +30,15 @@ G = 3.0
 S50, POS_A, POS_B = 50, 37, 22   # the DDIM schedule of the step tests: t = 740 and t = 440
 
 
-def new_model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
-
-
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    return new_model(cuda, unet_sd)
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def d(cuda):
     import diff
     return diff.Diffuser(1000, device=cuda)
-
-
-def ddim_update_ref(x, eps, p, sched):
-    """DDIM eta = 0 at position p (test_gpu_ddim.py's restatement without its noise term)."""
-    _, k_e, k_a, k_s, k_d, _ = sched
-    x0 = (x - k_e[p - 1] * eps) / k_a[p - 1]
-    return k_s[p - 1] * x0 + k_d[p - 1] * eps
-
-
-def dpm_update_ref(x, eps, p, sched, hist):
-    """test_gpu_dpm.py's restatement at one position for the whole batch -> (x', x0)."""
-    _, k_e, k_a, k_x, k_c, k_p = sched
-    x0 = (x - k_e[p - 1] * eps) / k_a[p - 1]
-    y = k_x[p - 1] * x + k_c[p - 1] * x0
-    return (y + k_p[p - 1] * hist if float(k_p[p - 1]) != 0 else y), x0
 
 
 def ddim_step(nm, sched, x, p, y, vals, mask, g=G, cache=None, out=None):
@@ -72,10 +48,6 @@ def ddim_step(nm, sched, x, p, y, vals, mask, g=G, cache=None, out=None):
     pos = torch.full((x.shape[0],), p, dtype=torch.long, device=dev)
     nm.step(x, out, pos, y, 0, vals, mask, g, None, sched=sched, **({} if cache is None else dict(cache=cache)))
     return out
-
-
-def on(dev, *ts):
-    return tuple(t.to(dev).contiguous() for t in ts)
 
 
 # ---- 1: a refresh step is the plain step -----------------------------------------------------------
@@ -139,9 +111,9 @@ def test_reuse_step_against_the_oracle(model, d, cuda, unet_sd, B, hw, prec, g):
     eps_cached = e(x_b, tb, False)
     eps_full = CachedEps(unet_sd, y, vals, mask, g)(x_b, tb, True)
     gap = rel(eps_cached, eps_full)
-    exp = ddim_update_ref(x_b, eps_cached, POS_B, csched)
+    exp = ddim_update(x_b, eps_cached, POS_B, csched)
     err, err_d = rel(out, exp), rel(D, e.features())
-    wrong = rel(ddim_update_ref(x_b, eps_full, POS_B, csched), exp)
+    wrong = rel(ddim_update(x_b, eps_full, POS_B, csched), exp)
     print(f"[cache reuse {prec}] B={B} {hw}x{hw} g={g}: rel-L2 vs oracle = {err:.3e} (D {err_d:.3e}); oracle cached vs "
           f"full eps {gap:.3e}, x_out {wrong:.3e}")
     assert gap > 1e-2, gap          # a reuse step that silently ran the full network cannot pass:
@@ -199,7 +171,7 @@ def test_loop_forms_are_bit_equal(model, d, cuda, unet_sd, B, hw):
         nm.step(x, out, pos, yd, 0, vd, md, G, None, None, seed=41, sched=sched, cache=(3, k))
         x = out
     outs["steps"] = x
-    outs["fresh model"] = loop(new_model(cuda, unet_sd).native(), True)
+    outs["fresh model"] = loop(make_model(cuda, unet_sd).native(), True)
     assert torch.isfinite(outs["graph"]).all()
     for k, v in outs.items():
         assert torch.equal(v, outs["graph"]), k
@@ -223,9 +195,9 @@ def oracle_trajectory(d, unet_sd, rule, sched, x_T, y, vals, mask, n, chunk, noi
 
     def update(x, eps, p):
         if rule == "ddim":
-            return ddim_update_ref(x, eps, p, sched)
+            return ddim_update(x, eps, p, sched)
         if rule == "dpm":
-            out, hist[0] = dpm_update_ref(x, eps, p, sched, hist[0])
+            out, hist[0] = dpm_update(x, eps, p, sched, hist[0])
             return out
         return ref.ddpm_update(x, eps, torch.full((B,), p, dtype=torch.long), alphas, alpha_bars, noises[p])
 
@@ -265,7 +237,7 @@ def test_trajectory_against_the_oracle(model, cuda, unet_sd, sampler, hw, N):
 
 def test_chunks_restart_the_count_and_a_replayed_chunk_refreshes_first(cuda, unet_sd):
     import diff
-    model = new_model(cuda, unet_sd)
+    model = make_model(cuda, unet_sd)
     nm = model.native()
     B, hw, S, N = 2, 32, 10, 3
     y = torch.tensor([2, 1])
@@ -342,7 +314,7 @@ def test_sharded_sampler_walks_the_same_cached_plan(model, cuda, source, sampler
 # ---- 7: a reuse step never reads a stale feature -------------------------------------------------------
 def test_stale_cache_is_refused_and_nothing_is_written(cuda, unet_sd, d):
     from dmx import _lib
-    model = new_model(cuda, unet_sd)
+    model = make_model(cuda, unet_sd)
     nm = model.native()
     sched = d.ddim_tables(S50, 0.0, cuda)
     x_a, x_b, y, vals, mask = step_inputs(3, 16, 700)
@@ -401,7 +373,7 @@ def test_stale_cache_is_refused_and_nothing_is_written(cuda, unet_sd, d):
 
 # ---- 8, 9: graph captures, and the plain path is untouched ------------------------------------------------
 def test_graph_captures_and_the_plain_loop_is_unaffected(cuda, unet_sd, d):
-    nm = new_model(cuda, unet_sd).native()
+    nm = make_model(cuda, unet_sd).native()
     B, hw = 2, 16
     x_a, _, y, vals, mask = step_inputs(B, hw, 800)
     sched = d.ddim_tables(9, 0.0, cuda)
@@ -431,7 +403,7 @@ def test_graph_captures_and_the_plain_loop_is_unaffected(cuda, unet_sd, d):
     assert n == 0 and torch.equal(off, plain)
     plain2, n = loop(None)
     assert n == 0 and torch.equal(plain2, plain)
-    fresh = new_model(cuda, unet_sd).native()  # a model that never ran a cached call
+    fresh = make_model(cuda, unet_sd).native()  # a model that never ran a cached call
     xf = x_a.to(cuda)
     fresh.sample_loop(xf, torch.full((1,), 9, dtype=torch.long, device=cuda), yd, 0, vd, md, G, None, 9, sched=sched)
     torch.cuda.synchronize()
@@ -439,9 +411,6 @@ def test_graph_captures_and_the_plain_loop_is_unaffected(cuda, unet_sd, d):
 
 
 # ---- 10: poison ------------------------------------------------------------------------------------------
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
 WORKER = r'''
 import os, sys
 import torch
@@ -475,21 +444,9 @@ print("[cache-poison-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + WORKER, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_cached_steps_read_no_unwritten_workspace(cuda, tmp_path):
-    clean = _run(tmp_path, "clean")
-    poisoned = _run(tmp_path, "poison", DMX_POISON="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    poisoned = run_worker(tmp_path, "poison", WORKER, DMX_POISON="1")
     assert len(clean) == 9
     bad = [k for k in clean if not torch.isfinite(poisoned[k]).all() or not torch.equal(clean[k], poisoned[k])]
     assert bad == [], bad

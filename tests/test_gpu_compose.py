@@ -11,33 +11,19 @@ Measured on an MI355X (rel-L2): composed steps against the oracle 2.3e-8 .. 3.9e
 (ddpm), 4.8e-7 (ddim), 4.9e-7 (dpm); the bit-equalities hold."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
-from oracle import ref
+from oracle import ref, rules
+from oracle.rules import compose_mix, composed_eps, ddim_update, dpm_update, rel
+from support import cond, device_noise, make_model, make_vae, mode_tables, run_worker
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 G = 3.0
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def make_model(cuda, sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(cuda).eval()
 
 
 @pytest.fixture(scope="module")
@@ -49,54 +35,6 @@ def model(cuda, unet_sd):
 def model2(cuda, unet_sd):
     """A second network with the same weights: its own arena and its own graph slots."""
     return make_model(cuda, unet_sd)
-
-
-# ---- the torch restatements ---------------------------------------------------------------------
-def mix_ref(es, w):
-    """es: K + 1 tensors (n,c,h,w), es[0] the base; w (K,n).  fp32, one rounding per torch op."""
-    def col(k):
-        return w[k].view(-1, 1, 1, 1)
-    s = col(0) * (es[1] - es[0])
-    for k in range(2, len(es)):
-        s = s + col(k - 1) * (es[k] - es[0])
-    return es[0] + s
-
-
-def ddim_update_ref(x, eps, pos, sched, nz):
-    _, k_e, k_a, k_s, k_d, k_n = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    return row(k_s) * x0 + row(k_d) * eps + row(k_n) * nz
-
-
-def dpm_update_ref(x, eps, pos, sched, hist):
-    _, k_e, k_a, k_x, k_c, k_p = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    y = row(k_x) * x + row(k_c) * x0
-    return torch.where(row(k_p) != 0, y + row(k_p) * hist, y), x0
-
-
-def eps_ref(sd, x, t, comp):
-    """The composed eps from the oracle: one forward per branch, then the mix."""
-    y_rows, v_rows, m_rows, w = comp
-    with torch.no_grad():
-        es = [ref.unet_cond_geom_forward(sd, x, t, y_rows[k], v_rows[k], m_rows[k])[0] for k in range(y_rows.shape[0])]
-    return mix_ref(es, w)
-
-
-def cond(B, seed):
-    g = torch.Generator().manual_seed(seed)
-    y = torch.tensor([1 + i % 3 for i in range(B)])
-    vals = torch.rand((B, 12), generator=g)
-    mask = (torch.rand((B, 12), generator=g) > 0.3).float()
-    return y, vals, mask
 
 
 def weights(B, seed, lo=-2.0, hi=4.0, first=-1.0):
@@ -149,7 +87,7 @@ def test_compose_eps_vs_restatement(cuda, shape, K):
     w = torch.stack([weights(n, 10 * k + n, -3.0, 5.0) for k in range(K)])
     if n == 1:
         w[0, 0] = -1.25
-    exp = mix_ref(es, w)
+    exp = compose_mix(es, w)
     out = engine.compose_eps([e.to(cuda) for e in es], w.to(cuda))
     assert out.shape == exp.shape and torch.equal(out.cpu(), exp)
     stacked = engine.compose_eps(torch.stack(es).to(cuda), w.to(cuda))       # the stacked form
@@ -157,7 +95,7 @@ def test_compose_eps_vs_restatement(cuda, shape, K):
     if K == 1:  # the tails' CFG expression
         assert torch.equal(exp, es[0] + w[0].view(-1, 1, 1, 1) * (es[1] - es[0]))
     const = engine.compose_eps([e.to(cuda) for e in es], [float(k + 1) for k in range(K)])   # (K,) weights
-    assert torch.equal(const.cpu(), mix_ref(es, torch.tensor([[float(k + 1)] * n for k in range(K)])))
+    assert torch.equal(const.cpu(), compose_mix(es, torch.tensor([[float(k + 1)] * n for k in range(K)])))
     with pytest.raises(ValueError):
         engine.compose_eps([e.to(cuda) for e in es], w[:, :1].expand(-1, n + 1).to(cuda))
     with pytest.raises(ValueError):
@@ -253,7 +191,7 @@ def step_ref(unet_sd, d, name, B, hw):
         x, hist, nz = (torch.randn((B, 4, hw, hw), generator=gen) for _ in range(3))
         _, _, _, comp = compose_case(d, name, B, 401 + hw)
         t = torch.full((B,), 600, dtype=torch.long)
-        _STEP_REF[key] = (x, hist, nz, comp, t, eps_ref(unet_sd, x, t, comp))
+        _STEP_REF[key] = (x, hist, nz, comp, t, composed_eps(unet_sd, x, t, comp))
     return _STEP_REF[key]
 
 
@@ -265,9 +203,9 @@ def composed_step_vs_oracle(nm, d, cuda, unet_sd, kind, name, B, hw):
         _, a, ab = ref.schedule(1000)
         exp = ref.ddpm_update(x, eps, t, a, ab, nz)
     elif kind == "ddim":
-        exp = ddim_update_ref(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
+        exp = ddim_update(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
     else:
-        exp, exp_h = dpm_update_ref(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
+        exp, exp_h = dpm_update(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
     h = hist.to(cuda)
     step_call(nm, d, cuda, kind, x.to(cuda), out, None, None, None, 0.0, nz.to(cuda), h, pos.to(cuda), t.to(cuda),
               compose=to(comp, cuda))
@@ -328,16 +266,6 @@ def test_large_batch_class_vs_oracle(model, cuda, unet_sd):
 
 
 # ---- 6: trajectories through sample_latent_cond --------------------------------------------------------------
-def device_noise(d, seed, shape, t, cuda):
-    """The Philox normals the DDPM / DDIM device loop draws at timestep t: an update with x = eps = 0,
-    c2 = sd = 1 returns them unchanged (none at t = 1)."""
-    from dmx import engine
-    T = d.num_timesteps
-    z = torch.zeros(shape, device=cuda)
-    tabs = (torch.zeros(T, device=cuda), torch.ones(T, device=cuda), torch.ones(T, device=cuda))
-    return engine.ddpm_update(z, z, None, 0.0, torch.full((shape[0],), t, device=cuda), tabs, None, seed=seed).cpu()
-
-
 @pytest.mark.parametrize("source", ["host", "device"])
 @pytest.mark.parametrize("case,T,kw", [
     ("ddpm", 12, dict()),
@@ -375,23 +303,7 @@ def test_composed_trajectory_vs_oracle(model, cuda, unet_sd, case, T, kw, source
     else:
         seed = d._seed()  # drawn after x_T, as the sampler does
         noise_of = lambda p: device_noise(d, seed, x.shape, tau[p - 1], cuda)  # noqa: E731
-    if mode is None:
-        _, a, ab = ref.schedule(T)
-    elif mode[0] == "ddim":
-        sched = d.ddim_tables(mode[1], mode[2], "cpu")
-    else:
-        sched = d.dpm_tables(mode[1], mode[2], "cpu")
-    hist = torch.full_like(x, float("nan"))
-    for p in range(len(tau), 0, -1):
-        t = torch.full((B,), tau[p - 1], dtype=torch.long)
-        pos = torch.full((B,), p, dtype=torch.long)
-        eps = eps_ref(unet_sd, x, t, comp)
-        if mode is None:
-            x = ref.ddpm_update(x, eps, t, a, ab, noise_of(p))
-        elif mode[0] == "ddim":
-            x = ddim_update_ref(x, eps, pos, sched, noise_of(p))
-        else:
-            x, hist = dpm_update_ref(x, eps, pos, sched, hist)
+    x = rules.trajectory(x, *mode_tables(d, mode), lambda x, t, pos: composed_eps(unet_sd, x, t, comp), noise_of)
     err = rel(out, x)
     print(f"[composed trajectory {case} {source}] B={B} {hw}x{hw} K=2: rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -527,10 +439,7 @@ def test_entity_csv_sampler_passes_base(model, cuda, vae_sd):
     import numpy as np
     from conftest import GOLDEN
     from entityCsvSampler import EntityCsvSampler
-    from models.vae import VAE
-    vae = VAE()
-    vae.load_state_dict(vae_sd)
-    vae = vae.to(cuda).eval()
+    vae = make_vae(cuda, vae_sd)
     csv = os.path.join(GOLDEN, "entities.csv")
     d = diff.Diffuser(1000, device=cuda)
     s = EntityCsvSampler(d, model, vae, class_id=1, base_wh=(400, 400), device=cuda)
@@ -577,11 +486,11 @@ def test_foreign_model_composed_step_vs_oracle(model, cuda, unet_sd, kind):
         plan = diff._SamplerPlan("ddpm", tables=d.coef_tables(cuda, clamp_prev=True), compose=to(comp, cuda))
         out = d._step(Foreign(), x.to(cuda), t.to(cuda), plan, True)
     elif kind == "ddim":
-        exp = ddim_update_ref(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
+        exp = ddim_update(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
         plan = diff._SamplerPlan("ddim", sched=d.ddim_tables(5, 0.5, cuda), draws=True, compose=to(comp, cuda))
         out = d._step(Foreign(), x.to(cuda), pos.to(cuda), plan, True)
     else:
-        exp, exp_h = dpm_update_ref(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
+        exp, exp_h = dpm_update(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
         h = hist.to(cuda)
         plan = diff._SamplerPlan("dpm", sched=d.dpm_tables(5, "uniform", cuda), draws=False, compose=to(comp, cuda))
         out = d._step(Foreign(), x.to(cuda), pos.to(cuda), plan, True, hist=h)
@@ -691,24 +600,12 @@ print("[compose-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + WORKER, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_composed_step_reads_no_unwritten_workspace(cuda, tmp_path):
     """One composed step (Co = 4 and Co = 3) in fresh processes, with and without DMX_POISON=1 /
     DMX_CHECK=1: finite and bit-identical.  The Co = 3 step (head, mix, update as three launches)
     equals the model's own per-branch forwards mixed by compose_eps within the step bound."""
-    clean = _run(tmp_path, "clean")
-    diag = _run(tmp_path, "diag", DMX_POISON="1", DMX_CHECK="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    diag = run_worker(tmp_path, "diag", WORKER, DMX_POISON="1", DMX_CHECK="1")
     bad = [k for k in clean if not torch.isfinite(diag[k]).all() or not torch.equal(clean[k], diag[k])]
     assert bad == [], bad
     for hw in (16, 28):

@@ -7,7 +7,9 @@ p-1:  x0 = (x - k_e eps)/k_a;  x' = k_s x0 + k_d eps + k_n noise  (torch's evalu
 import pytest
 import torch
 
-from oracle import ref
+from oracle import ref, rules
+from oracle.rules import Foreign, cfg_eps, ddim_update, rel
+from support import make_model, make_vae, overflow_sd
 
 pytestmark = pytest.mark.gpu
 
@@ -15,60 +17,14 @@ TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 
 
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
-
-
-def to_dev(sched, dev):
-    return tuple(v.to(dev) for v in sched)
-
-
-# ---- the torch restatement --------------------------------------------------------------------
-def ddim_update_ref(x, eps, pos, sched, nz):
-    """fp32 torch-CPU, one rounding per op: (k_s*x0 + k_d*eps) + k_n*nz with x0 = (x - k_e*eps)/k_a."""
-    _, k_e, k_a, k_s, k_d, k_n = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    return row(k_s) * x0 + row(k_d) * eps + row(k_n) * nz
-
-
-def cfg_eps_ref(sd, x, pos, sched, y, vals, mask, guidance=3.0, null_label=0):
-    t = sched[0][pos - 1]  # the network sees the timestep, not the position
-    eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.full_like(y, null_label), vals, mask)
-    ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-    return eu + guidance * (ec - eu)
-
-
-def trajectory_ref(sd, x, y, vals, mask, sched, noisy):
-    """Positions S..1 from x; one global randn per step when `noisy` (the DDPM sampler's draw order)."""
-    S = int(sched[0].numel())
-    with torch.no_grad():
-        for p in range(S, 0, -1):
-            pos = torch.full((x.shape[0],), p, dtype=torch.long)
-            nz = torch.randn(x.shape) if noisy else torch.zeros_like(x)
-            x = ddim_update_ref(x, cfg_eps_ref(sd, x, pos, sched, y, vals, mask), pos, sched, nz)
-    return x
+    return make_vae(cuda, vae_sd)
 
 
 # ---- 4: the update, bit for bit ------------------------------------------------------------------
@@ -85,9 +41,9 @@ def test_ddim_update_bit_exact(cuda, eta):
     for C in (4, 3):  # both go through the generic tail; 3 channels: the Co < 4 indexing
         x, eu, ec, nz = (torch.randn((B, C, 16, 16), generator=g) for _ in range(4))
         out = engine.ddim_update(x.to(cuda), eu.to(cuda), ec.to(cuda), 3.0, pos.to(cuda), dsched, nz.to(cuda)).cpu()
-        assert torch.equal(out, ddim_update_ref(x, eu + 3.0 * (ec - eu), pos, sched, nz))
+        assert torch.equal(out, ddim_update(x, eu + 3.0 * (ec - eu), pos, sched, nz))
         out = engine.ddim_update(x.to(cuda), eu.to(cuda), None, 0.0, pos.to(cuda), dsched, nz.to(cuda)).cpu()
-        assert torch.equal(out, ddim_update_ref(x, eu, pos, sched, nz))
+        assert torch.equal(out, ddim_update(x, eu, pos, sched, nz))
     if eta == 0.0:  # no noise anywhere: nothing is read or drawn, given or not
         out2 = engine.ddim_update(x.to(cuda), eu.to(cuda), None, 0.0, pos.to(cuda), dsched, None, seed=5).cpu()
         assert torch.equal(out2, out)
@@ -137,7 +93,7 @@ def test_ddim_step_vs_oracle(model, cuda, unet_sd, prec):
     assert torch.equal(after, torch.get_rng_state())  # one randn(x.shape) per call
     sched = d.ddim_tables(50, 0.5, "cpu")
     with torch.no_grad():
-        exp = ddim_update_ref(x, cfg_eps_ref(unet_sd, x, pos, sched, y, vals, mask), pos, sched, noise)
+        exp = ddim_update(x, cfg_eps(unet_sd, x, sched[0][pos - 1], y, vals, mask), pos, sched, noise)
     err = rel(out, exp)
     print(f"[ddim step {prec}] rel-L2 vs oracle = {err:.3e}")
     assert err < TOL, err
@@ -156,22 +112,18 @@ def test_ddim_step_without_cfg_and_foreign_model(model, cuda, unet_sd):
     sched = d.ddim_tables(7, 0.0, "cpu")
     t = sched[0][pos - 1]
 
-    class Foreign(torch.nn.Module):  # not a dmx network: no .native()
-        def forward(self, x, t, y, cond_vals=None, cond_mask=None):
-            return model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-
     with torch.no_grad():
         e_y, _ = ref.unet_cond_geom_forward(unet_sd, x, t, y)
         e_0, _ = ref.unet_cond_geom_forward(unet_sd, x, t, torch.zeros_like(y))
         e_cfg = e_0 + 3.0 * (e_y - e_0)
     zero = torch.zeros_like(x)
-    for mdl in (model, Foreign()):
+    for mdl in (model, Foreign(model)):
         out = d.ddim_step(mdl, x.to(cuda), pos.to(cuda), 7, y=y.to(cuda))
-        assert rel(out, ddim_update_ref(x, e_y, pos, sched, zero)) < TOL
+        assert rel(out, ddim_update(x, e_y, pos, sched, zero)) < TOL
         out = d.ddim_step(mdl, x.to(cuda), pos.to(cuda), 7)
-        assert rel(out, ddim_update_ref(x, e_0, pos, sched, zero)) < TOL
+        assert rel(out, ddim_update(x, e_0, pos, sched, zero)) < TOL
         out = d.ddim_step(mdl, x.to(cuda), pos.to(cuda), 7, y=y.to(cuda), guidance_scale=3.0)
-        assert rel(out, ddim_update_ref(x, e_cfg, pos, sched, zero)) < TOL
+        assert rel(out, ddim_update(x, e_cfg, pos, sched, zero)) < TOL
 
 
 # ---- 6: trajectories against the oracle ---------------------------------------------------------
@@ -195,7 +147,10 @@ def test_ddim_trajectory_vs_oracle(model, cuda, unet_sd, case, counts, hw, S, et
     assert d.range_fallbacks == 0
     torch.manual_seed(61)
     x_T = torch.randn((B, 4, hw, hw))
-    exp = trajectory_ref(unet_sd, x_T, y, vals, mask, d.ddim_tables(S, eta, "cpu"), noisy=eta > 0)
+    # one global randn per step when eta > 0 (the DDPM sampler's draw order)
+    noise_of = (lambda p: torch.randn(x_T.shape)) if eta > 0 else (lambda p: torch.zeros_like(x_T))
+    exp = rules.trajectory(x_T, "ddim", d.ddim_tables(S, eta, "cpu"),
+                           lambda x, t, pos: cfg_eps(unet_sd, x, t, y, vals, mask), noise_of)
     err = rel(out, exp)
     print(f"[ddim trajectory {case}] B={B} {hw}x{hw} S={S} eta={eta} {source}: rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -324,20 +279,13 @@ def test_ddim_sharded_world1_equals_diffuser(model, cuda, source, eta):
 
 @pytest.fixture
 def unet_sd_overflow():
-    """An overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range in the first block."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
+    return overflow_sd()
 
 
 @pytest.mark.parametrize("source", ["host", "device"])
 def test_ddim_range_guard_replays_in_fp32(cuda, unet_sd_overflow, source):
     import diff
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd_overflow)
-    m.to(cuda).eval()
+    m = make_model(cuda, unet_sd_overflow)
     d = diff.Diffuser(8, device=cuda)
     d.noise_source = source
     g = torch.Generator().manual_seed(35)

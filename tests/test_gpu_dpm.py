@@ -15,7 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref
+from oracle import ref, rules
+from oracle.rules import Foreign, cfg_eps, ddim_update, dpm_update, rel
+from support import make_model, make_vae, overflow_sd
 
 pytestmark = pytest.mark.gpu
 
@@ -23,77 +25,19 @@ TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 
 
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
+    return make_vae(cuda, vae_sd)
 
 
 @pytest.fixture
 def unet_sd_overflow():
-    """An overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range in the first block."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
-
-
-# ---- the torch restatements ---------------------------------------------------------------------
-def dpm_update_ref(x, eps, pos, sched, hist):
-    """One rounding per op in x's dtype: -> (x', x0).  hist is not used where k_p == 0."""
-    _, k_e, k_a, k_x, k_c, k_p = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    y = row(k_x) * x + row(k_c) * x0
-    return torch.where(row(k_p) != 0, y + row(k_p) * hist, y), x0
-
-
-def ddim_update_ref(x, eps, pos, sched):
-    """test_gpu_ddim.py's restatement at eta = 0 (k_n = 0: no noise term)."""
-    _, k_e, k_a, k_s, k_d, _ = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    return row(k_s) * x0 + row(k_d) * eps
-
-
-def cfg_eps_ref(sd, x, pos, sched, y, vals, mask, guidance=3.0, null_label=0):
-    t = sched[0][pos - 1]  # the network sees the timestep, not the position
-    eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.full_like(y, null_label), vals, mask)
-    ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-    return eu + guidance * (ec - eu)
-
-
-def trajectory_ref(x, sched, eps_of):
-    """Positions S..1 from x; eps_of(x, pos) -> eps.  The history starts unread (NaN would show)."""
-    S = int(sched[0].numel())
-    hist = torch.full_like(x, float("nan"))
-    with torch.no_grad():
-        for p in range(S, 0, -1):
-            pos = torch.full((x.shape[0],), p, dtype=torch.long)
-            x, hist = dpm_update_ref(x, eps_of(x, pos), pos, sched, hist)
-    return x
+    return overflow_sd()
 
 
 # ---- 4: the update, bit for bit ------------------------------------------------------------------
@@ -110,12 +54,12 @@ def test_dpm_update_bit_exact(cuda, spacing):
     pos = torch.tensor([S, 4, 1])  # first-order (no history yet), second-order, first-order (s = 0)
     for C in (4, 3):  # both go through the generic tail; 3 channels: the Co < 4 indexing
         x, eu, ec, hist = (torch.randn((B, C, 16, 16), generator=g) for _ in range(4))
-        exp, exp_h = dpm_update_ref(x, eu + 3.0 * (ec - eu), pos, sched, hist)
+        exp, exp_h = dpm_update(x, eu + 3.0 * (ec - eu), pos, sched, hist)
         h = hist.to(cuda)
         out = engine.dpm_update(x.to(cuda), eu.to(cuda), ec.to(cuda), 3.0, pos.to(cuda), dsched, h).cpu()
         assert torch.equal(out, exp) and torch.equal(h.cpu(), exp_h)
         # no CFG operand: eps = eu
-        exp1, exp1_h = dpm_update_ref(x, eu, pos, sched, hist)
+        exp1, exp1_h = dpm_update(x, eu, pos, sched, hist)
         h = hist.to(cuda)
         out1 = engine.dpm_update(x.to(cuda), eu.to(cuda), None, 0.0, pos.to(cuda), dsched, h).cpu()
         assert torch.equal(out1, exp1) and torch.equal(h.cpu(), exp1_h)
@@ -167,15 +111,15 @@ def test_dpm_first_order_rows_are_ddim(cuda):
     # size), so it is held to the 1e-6 of the GPU comparison; both figures are printed.
     for S, p, bound in ((2, 2, 8e-8), (50, 50, 1e-6)):
         pp = torch.full((B,), p)
-        a, _ = dpm_update_ref(x, eps, pp, d.dpm_tables(S, "uniform", "cpu"), nan)
-        b = ddim_update_ref(x, eps, pp, d.ddim_tables(S, 0.0, "cpu"))
+        a, _ = dpm_update(x, eps, pp, d.dpm_tables(S, "uniform", "cpu"), nan)
+        b = ddim_update(x, eps, pp, d.ddim_tables(S, 0.0, "cpu"))
         err = rel(a, b)
         print(f"[dpm first-order row vs ddim, CPU restatements, S={S} p={p}] rel-L2 = {err:.3e}")
         assert err <= bound, err
     for S in (2, 50):
         pp = torch.full((B,), 1)
-        a, a0 = dpm_update_ref(x, eps, pp, d.dpm_tables(S, "uniform", "cpu"), nan)
-        assert torch.equal(a, ddim_update_ref(x, eps, pp, d.ddim_tables(S, 0.0, "cpu"))) and torch.equal(a, a0)
+        a, a0 = dpm_update(x, eps, pp, d.dpm_tables(S, "uniform", "cpu"), nan)
+        assert torch.equal(a, ddim_update(x, eps, pp, d.ddim_tables(S, 0.0, "cpu"))) and torch.equal(a, a0)
 
 
 # ---- 6: one network step against the oracle -----------------------------------------------------
@@ -198,7 +142,7 @@ def step_ref(unet_sd, d, hw):
         with torch.no_grad():
             for p in (4, 3):
                 pos = torch.full((B,), p)
-                xr, hr = dpm_update_ref(xr, cfg_eps_ref(unet_sd, xr, pos, sched, y, vals, mask), pos, sched, hr)
+                xr, hr = dpm_update(xr, cfg_eps(unet_sd, xr, sched[0][pos - 1], y, vals, mask), pos, sched, hr)
                 exp.append((xr, hr))
         _STEP_REF[hw] = (x, hist, y, vals, mask, exp)
     return _STEP_REF[hw]
@@ -236,20 +180,16 @@ def test_dpm_step_without_cfg_and_foreign_model(model, cuda, unet_sd):
     sched = d.dpm_tables(7, "logsnr", "cpu")
     t = sched[0][pos - 1]
 
-    class Foreign(torch.nn.Module):  # not a dmx network: no .native()
-        def forward(self, x, t, y, cond_vals=None, cond_mask=None):
-            return model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-
     with torch.no_grad():
         e_y, _ = ref.unet_cond_geom_forward(unet_sd, x, t, y)
         e_0, _ = ref.unet_cond_geom_forward(unet_sd, x, t, torch.zeros_like(y))
         e_cfg = e_0 + 3.0 * (e_y - e_0)
     outs = {}
-    for name, mdl in (("native", model), ("foreign", Foreign())):
+    for name, mdl in (("native", model), ("foreign", Foreign(model))):
         for case, eps, kw in (("y", e_y, dict(y=y.to(cuda))), ("cfg", e_cfg, dict(y=y.to(cuda), guidance_scale=3.0))):
             h = hist.to(cuda)
             out = d.dpm_step(mdl, x.to(cuda), pos.to(cuda), h, 7, **kw)
-            ex, eh = dpm_update_ref(x, eps, pos, sched, hist)
+            ex, eh = dpm_update(x, eps, pos, sched, hist)
             assert rel(out, ex) <= TOL and rel(h, eh) <= TOL, (name, case)
             outs[name, case] = (out, h)
     for case in ("y", "cfg"):
@@ -280,7 +220,7 @@ def test_dpm_trajectory_vs_oracle(model, cuda, unet_sd, case, counts, hw, S, spa
     torch.manual_seed(61)
     x_T = torch.randn((B, 4, hw, hw))
     sched = d.dpm_tables(S, spacing, "cpu")
-    exp = trajectory_ref(x_T, sched, lambda x, pos: cfg_eps_ref(unet_sd, x, pos, sched, y, vals, mask))
+    exp = rules.trajectory(x_T, "dpm", sched, lambda x, t, pos: cfg_eps(unet_sd, x, t, y, vals, mask))
     err = rel(out, exp)
     print(f"[dpm trajectory {case}] B={B} {hw}x{hw} S={S} {spacing} {source}: rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -392,15 +332,11 @@ def solver_accuracy_cpu(d, x_T, S=20):
     """-> (float64 full-stride 2M reference, fp32 restatement of 2M/logsnr at S, fp32 restatement of DDIM at S)."""
     ab = d._host[1]
     fine = tables64(d, list(range(1, d.num_timesteps + 1)))
-    ref64 = trajectory_ref(x_T.double(), fine, lambda x, pos: mixture_eps(x, ab.double()[fine[0][pos - 1] - 1]))
-    sched = d.dpm_tables(S, "logsnr", "cpu")
-    dpm32 = trajectory_ref(x_T, sched, lambda x, pos: mixture_eps(x, ab[sched[0][pos - 1] - 1]))
-    dsch = d.ddim_tables(S, 0.0, "cpu")
-    x = x_T
-    for p in range(S, 0, -1):
-        pos = torch.full((x.shape[0],), p)
-        x = ddim_update_ref(x, mixture_eps(x, ab[dsch[0][pos - 1] - 1]), pos, dsch)
-    return ref64, dpm32, x
+    ref64 = rules.trajectory(x_T.double(), "dpm", fine, lambda x, t, pos: mixture_eps(x, ab.double()[t - 1]))
+    def eps32(x, t, pos):
+        return mixture_eps(x, ab[t - 1])
+    dpm32 = rules.trajectory(x_T, "dpm", d.dpm_tables(S, "logsnr", "cpu"), eps32)
+    return ref64, dpm32, rules.trajectory(x_T, "ddim", d.ddim_tables(S, 0.0, "cpu"), eps32)
 
 
 def test_dpm_solver_accuracy(cuda):
@@ -450,10 +386,7 @@ def test_dpm_draws_only_x_T(model, cuda, source):
 @pytest.mark.parametrize("source", ["host", "device"])
 def test_dpm_range_guard_replay_restores_history(cuda, unet_sd_overflow, source):
     import diff
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd_overflow)
-    m.to(cuda).eval()
+    m = make_model(cuda, unet_sd_overflow)
     g = torch.Generator().manual_seed(35)
     vals = torch.rand((2, 12), generator=g).to(cuda)
     mask = torch.ones((2, 12), device=cuda)

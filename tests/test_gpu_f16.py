@@ -20,6 +20,8 @@ import pytest
 import torch
 
 from oracle import ref
+from oracle.rules import rel
+from support import make_model
 
 pytestmark = pytest.mark.gpu
 
@@ -29,18 +31,9 @@ TOL_TRAJ = 2e-3
 TOL_VAE = 1e-3
 
 
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
 @pytest.fixture(scope="module")
 def model16(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    m = m.to(cuda).eval()
+    m = make_model(cuda, unet_sd)
     m.native().set_precision("f16")
     assert m.native().precision == "f16"
     return m

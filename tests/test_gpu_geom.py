@@ -18,28 +18,21 @@ the oracle 5.9e-7 .. 2.0e-6 at shares 0.093 .. 0.76 (bounds 2.9e-5 .. 9.6e-5); t
 guided loop lowers the final masked loss 0.28616 -> 0.26291 (8.1 %), as the oracle's loop does."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import ref, train_ref
+from oracle.rules import ddim_update, dpm_update, rel
+from support import make_model, make_vae, per_sample_rel, run_worker
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
-
-from test_gpu_compose import ddim_update_ref, dpm_update_ref, make_model, rel  # noqa: E402
 
 GRAD_TOL = 1e-4   # a gradient against the oracle, per sample (the project's gradient bound)
 TOL = 2e-5        # one step (the project's step bound)
 G = 3.0
 S_STEP = 2000.0   # the guided steps' scale
-ROOT = os.path.dirname(HERE)
 SHAPES = [(3, 8), (3, 16), (2, 28)]
 
 
@@ -89,12 +82,6 @@ def case(B, hw, seed, ts):
     mask = (torch.rand((B, 12), generator=g) > 0.3).float()
     mask[-1] = 0.0
     return x, torch.tensor(ts[:B]), y, vals, mask
-
-
-def per_sample_rel(a, b):
-    a, b = a.double().cpu().flatten(1), b.double().cpu().flatten(1)
-    return [(float((a[i] - b[i]).norm() / b[i].norm()) if float(b[i].norm()) > 0 else float(a[i].norm()))
-            for i in range(a.shape[0])]
 
 
 _GRAD_REF = {}
@@ -265,8 +252,8 @@ def update_ref(d, kind, x, eps, t, pos, nz, hist):
         _, a, ab = ref.schedule(DDPM_T, 1e-4, DDPM_BETA_END)
         return ref.ddpm_update(x, eps, t, a, ab, nz), None
     if kind == "ddim":
-        return ddim_update_ref(x, eps, pos, d.ddim_tables(4, 0.5, "cpu"), nz), None
-    return dpm_update_ref(x, eps, pos, d.dpm_tables(4, "uniform", "cpu"), hist)
+        return ddim_update(x, eps, pos, d.ddim_tables(4, 0.5, "cpu"), nz), None
+    return dpm_update(x, eps, pos, d.dpm_tables(4, "uniform", "cpu"), hist)
 
 
 def guided_step_ref(d, kind, sd, hw, grad, scale, nz=None):
@@ -548,10 +535,7 @@ def test_entity_csv_sampler_passes_geom_scale(model, cuda, vae_sd):
     import diff
     from conftest import GOLDEN
     from entityCsvSampler import EntityCsvSampler
-    from models.vae import VAE
-    vae = VAE()
-    vae.load_state_dict(vae_sd)
-    vae = vae.to(cuda).eval()
+    vae = make_vae(cuda, vae_sd)
     csv = os.path.join(GOLDEN, "entities.csv")
     d = diff.Diffuser(1000, device=cuda)
     s = EntityCsvSampler(d, model, vae, class_id=1, base_wh=(400, 400), device=cuda)
@@ -745,22 +729,10 @@ print("[geom-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + WORKER, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_guided_step_reads_no_unwritten_workspace(cuda, tmp_path):
     """One guided step and one geom_grad (in_ch = 4 and 3; 16x16 and 28x28) in fresh processes, with and
     without DMX_POISON=1 / DMX_CHECK=1: finite and bit-identical."""
-    clean = _run(tmp_path, "clean")
-    diag = _run(tmp_path, "diag", DMX_POISON="1", DMX_CHECK="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    diag = run_worker(tmp_path, "diag", WORKER, DMX_POISON="1", DMX_CHECK="1")
     bad = [k for k in clean if not torch.isfinite(diag[k]).all() or not torch.equal(clean[k], diag[k])]
     assert bad == [], bad

@@ -19,26 +19,15 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref
+from oracle import ref, rules
+from oracle.rules import cfg_rescale, ddim_update, dpm_update, rel
+from support import cond, device_noise, make_model, make_vae, mode_tables, overflow_sd, ulps
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 G = 3.0
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def make_model(cuda, sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(cuda).eval()
 
 
 @pytest.fixture(scope="module")
@@ -54,100 +43,20 @@ def model2(cuda, unet_sd):
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
+    return make_vae(cuda, vae_sd)
 
 
 @pytest.fixture
 def unet_sd_overflow():
-    """test_gpu_dpm.py's overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
+    return overflow_sd()
 
 
-# ---- the torch restatements ---------------------------------------------------------------------
-def rescale_ref(eu, ec, g, phi):
-    """-> (eg, r as double): fp32 eg, double std over each sample's elements."""
-    eg = eu + g * (ec - eu)
-    sg = eg.double().flatten(1).std(1)
-    sc = ec.double().flatten(1).std(1)
-    ok = torch.isfinite(sg) & (sg > 0)
-    r = torch.where(ok, 1.0 + phi * (sc / torch.where(ok, sg, torch.ones_like(sg)) - 1.0), torch.ones_like(sg))
-    return eg, r
-
-
-def ddim_update_ref(x, eps, pos, sched, nz):
-    _, k_e, k_a, k_s, k_d, k_n = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    return row(k_s) * x0 + row(k_d) * eps + row(k_n) * nz
-
-
-def dpm_update_ref(x, eps, pos, sched, hist):
-    _, k_e, k_a, k_x, k_c, k_p = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    y = row(k_x) * x + row(k_c) * x0
-    return torch.where(row(k_p) != 0, y + row(k_p) * hist, y), x0
-
-
-def eps_ref(sd, x, t, y, vals, mask, guided, phi=0.0, g=G):
-    """The step's eps from the oracle: conditional only, CFG, or rescaled CFG -> (eps, r or None)."""
-    ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-    if not guided:
-        return ec, None
-    eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.zeros_like(y), vals, mask)
-    eg, r = rescale_ref(eu, ec, g, phi)
-    return (eg * r.float().view(-1, 1, 1, 1) if phi > 0 else eg), r
-
-
-def trajectory_ref(sd, d, mode, x, y, vals, mask, interval, phi, noise_of, p0=None):
-    """Positions p0 (default S) .. 1 of the mode's schedule from x; noise_of(p) -> the step's noise."""
-    tau = d._mode_timesteps(mode)
-    S = len(tau)
-    B = x.shape[0]
-    if mode is None:
-        _, a, ab = ref.schedule(d.num_timesteps)
-    elif mode[0] == "ddim":
-        sched = d.ddim_tables(mode[1], mode[2], "cpu")
-    else:
-        sched = d.dpm_tables(mode[1], mode[2], "cpu")
-    hist = torch.full_like(x, float("nan"))
-    with torch.no_grad():
-        for p in range(S if p0 is None else p0, 0, -1):
-            t = torch.full((B,), tau[p - 1], dtype=torch.long)
-            pos = torch.full((B,), p, dtype=torch.long)
-            guided = interval is None or interval[0] <= tau[p - 1] <= interval[1]
-            eps, _ = eps_ref(sd, x, t, y, vals, mask, guided, phi)
-            if mode is None:
-                x = ref.ddpm_update(x, eps, t, a, ab, noise_of(p))
-            elif mode[0] == "ddim":
-                x = ddim_update_ref(x, eps, pos, sched, noise_of(p))
-            else:
-                x, hist = dpm_update_ref(x, eps, pos, sched, hist)
-    return x
-
-
-def cond(B, seed, cuda=None):
-    g = torch.Generator().manual_seed(seed)
-    y = torch.tensor([1 + i % 3 for i in range(B)])
-    vals = torch.rand((B, 12), generator=g)
-    mask = (torch.rand((B, 12), generator=g) > 0.3).float()
-    return y, vals, mask
-
-
-def ulps(a, b):
-    return (a.contiguous().view(torch.int32).long() - b.contiguous().view(torch.int32).long()).abs()
+def interval_trajectory(sd, d, mode, x, y, vals, mask, interval, phi, noise_of):
+    """rules.trajectory over the mode's schedule, a step guided iff its timestep lies in `interval`."""
+    def eps_of(x, t, pos):
+        guided = interval is None or interval[0] <= int(t[0]) <= interval[1]
+        return rules.guided_eps(sd, x, t, y, vals, mask, guided, phi)[0]
+    return rules.trajectory(x, *mode_tables(d, mode), eps_of, noise_of)
 
 
 # ---- 1: cfg_rescale against the restatement ------------------------------------------------------
@@ -160,7 +69,7 @@ def test_cfg_rescale_vs_restatement(cuda, shape):
     ec[1] = 0.375   # a constant conditional prediction ...
     eu[1] = -1.25   # ... and unconditional one: eg is constant, std 0 after guidance
     phi = 0.7
-    eg, r_ref = rescale_ref(eu, ec, G, phi)
+    eg, r_ref = cfg_rescale(eu, ec, G, phi)
     eps, r = engine.cfg_rescale(eu.to(cuda), ec.to(cuda), G, phi)
     eps, r = eps.cpu(), r.cpu()
     n = shape[0]
@@ -215,7 +124,7 @@ def test_rescaled_step_vs_oracle(model, cuda, unet_sd, kind, B, hw):
     nm = model.native()
     phi = 0.7
     x, hist, nz, y, vals, mask, t, eu, ec = step_ref(unet_sd, B, hw)
-    eg, r_ref = rescale_ref(eu, ec, G, phi)
+    eg, r_ref = cfg_rescale(eu, ec, G, phi)
     eps = eg * r_ref.float().view(-1, 1, 1, 1)
     pos = torch.full((B,), 3, dtype=torch.long)
     out = torch.empty((B, 4, hw, hw), device=cuda)
@@ -225,10 +134,10 @@ def test_rescaled_step_vs_oracle(model, cuda, unet_sd, kind, B, hw):
         exp = ref.ddpm_update(x, eps, t, a, ab, nz)
         nm.step(x.to(cuda), out, t.to(cuda), *args, d.coef_tables(cuda, True), nz.to(cuda), rescale=phi)
     elif kind == "ddim":
-        exp = ddim_update_ref(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
+        exp = ddim_update(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
         nm.step(x.to(cuda), out, pos.to(cuda), *args, None, nz.to(cuda), sched=d.ddim_tables(5, 0.5, cuda), rescale=phi)
     else:
-        exp, exp_h = dpm_update_ref(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
+        exp, exp_h = dpm_update(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
         h = hist.to(cuda)
         nm.step(x.to(cuda), out, pos.to(cuda), *args, None, None, sched=d.dpm_tables(5, "uniform", cuda), hist=h,
                 rescale=phi)
@@ -399,23 +308,13 @@ def test_unguided_device_loop(model, model2, cuda, unet_sd, B):
         pos = torch.full((B,), 25, dtype=torch.long)
         with torch.no_grad():
             ec, _ = ref.unet_cond_geom_forward(unet_sd, x0c, cs[0][pos - 1], yc, valsc, maskc)
-        exp, _ = dpm_update_ref(x0c, ec, pos, cs, torch.zeros_like(x0c))
+        exp, _ = dpm_update(x0c, ec, pos, cs, torch.zeros_like(x0c))
         err = rel(first, exp)
         print(f"[unguided step B={B}] rel-L2 vs oracle = {err:.3e}")
         assert err <= TOL, err
 
 
 # ---- 5: interval trajectories against the oracle -------------------------------------------------------
-def device_noise(d, seed, shape, t, cuda):
-    """The Philox normals the DDPM device loop draws at timestep t (none at t = 1): an update with
-    x = eps = 0, c2 = sd = 1 returns them unchanged."""
-    from dmx import engine
-    T = d.num_timesteps
-    z = torch.zeros(shape, device=cuda)
-    tabs = (torch.zeros(T, device=cuda), torch.ones(T, device=cuda), torch.ones(T, device=cuda))
-    return engine.ddpm_update(z, z, None, 0.0, torch.full((shape[0],), t, device=cuda), tabs, None, seed=seed).cpu()
-
-
 @pytest.mark.parametrize("case,T,kw,ipos,phi,B,hw,source", [
     ("a", 1000, dict(sampler="dpmpp_2m", steps=6), (2, 4), 0.0, 2, 8, "device"),
     ("b", 1000, dict(sampler="ddim", steps=5, eta=1.0), (4, 5), 0.0, 2, 8, "host"),
@@ -450,7 +349,7 @@ def test_interval_trajectory_vs_oracle(model, cuda, unet_sd, case, T, kw, ipos, 
     else:
         seed = d._seed()  # drawn after x_T, as the sampler does
         noise_of = lambda p: device_noise(d, seed, x_T.shape, tau[p - 1], cuda)  # noqa: E731
-    exp = trajectory_ref(unet_sd, d, mode, x_T, y, vals, mask, interval, phi, noise_of)
+    exp = interval_trajectory(unet_sd, d, mode, x_T, y, vals, mask, interval, phi, noise_of)
     err = rel(out, exp)
     print(f"[interval trajectory {case}] B={B} {hw}x{hw} interval={interval} phi={phi} {source}: "
           f"rel-L2 vs oracle = {err:.3e}")
@@ -641,7 +540,7 @@ def test_foreign_model_interval_and_rescale(model, cuda, unet_sd, name, kw):
     torch.manual_seed(911)
     x_T = torch.randn((2, 4, 8, 8))
     noise_of = (lambda p: torch.randn(x_T.shape)) if mode is None else (lambda p: torch.zeros_like(x_T))
-    exp = trajectory_ref(unet_sd, d, mode, x_T, y, vals, mask, interval, phi, noise_of)
+    exp = interval_trajectory(unet_sd, d, mode, x_T, y, vals, mask, interval, phi, noise_of)
     err = rel(out, exp)
     print(f"[foreign model {name}, interval + rescale] rel-L2 vs restatement = {err:.3e}")
     assert err <= TRAJ_TOL, err

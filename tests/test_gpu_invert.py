@@ -11,44 +11,27 @@ of z0, so that parity at those bounds is a statement about the kernels and not a
 Measured on an MI355X (rel-L2): one row against the oracle 1.4e-7 .. 5.4e-7 (native and foreign paths);
 trajectories (a) 1.6e-6, (b) 1.0e-6, (c) 2.6e-6, (d) 1.2e-6 with CPU perturbation gains 0.20 / 0.80 / 0.69 /
 0.21; round trip R = 0 2.399e-1, R = 3 1.587e-3 (the CPU restatement: the same to four digits)."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
-from test_invert_host import (cfg_eps_ref, ddim_back_ref, invert_ref, invert_update_ref, perturbation_gain, rel,
-                              round_trip_inputs)
+from oracle.rules import Foreign, cfg_eps, invert_update, rel
+from support import make_model, on, overflow_sd, run_worker
+from test_invert_host import invert_ref, perturbation_gain, round_trip_inputs
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
 
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture
 def unet_sd_overflow():
-    """An overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range in the first block."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
-
-
-def to(dev, *ts):
-    return tuple(t.to(dev) for t in ts)
+    return overflow_sd()
 
 
 # ---- 1: the update, bit for bit --------------------------------------------------------------------
@@ -66,7 +49,7 @@ def test_invert_update_bit_exact(cuda, C):
     x, eu, ec, src = (torch.randn((B, C, 16, 16), generator=g) for _ in range(4))
     for guided in (True, False):
         eps = eu + 3.0 * (ec - eu) if guided else eu
-        exp, exp_src = invert_update_ref(src, eps, pos, tables)
+        exp, exp_src = invert_update(src, eps, pos, tables)
         s = src.to(cuda)
         out = engine.invert_update(x.to(cuda), eu.to(cuda), ec.to(cuda) if guided else None, 3.0 if guided else 0.0,
                                    pos.to(cuda), dtab, s)
@@ -75,7 +58,7 @@ def test_invert_update_bit_exact(cuda, C):
     # out may alias x: x's values are not an operand
     xa, s = x.to(cuda), src.to(cuda)
     res = engine.invert_update(xa, eu.to(cuda), ec.to(cuda), 3.0, pos.to(cuda), dtab, s, out=xa)
-    exp, exp_src = invert_update_ref(src, eu + 3.0 * (ec - eu), pos, tables)
+    exp, exp_src = invert_update(src, eu + 3.0 * (ec - eu), pos, tables)
     assert res.data_ptr() == xa.data_ptr()
     assert torch.equal(xa.cpu(), exp) and torch.equal(s.cpu(), exp_src)
 
@@ -135,10 +118,10 @@ def step_ref(unet_sd, d, guidance, with_y=True):
         assert tables[0][pos - 1].tolist() == [50, 100, 150] and tables[3][pos - 1].tolist() == [0, 0, 1]
         with torch.no_grad():
             if with_y:
-                eps = cfg_eps_ref(unet_sd, x, tables[0][pos - 1], y, vals, mask, guidance)
+                eps = cfg_eps(unet_sd, x, tables[0][pos - 1], y, vals, mask, guidance)
             else:  # y omitted: the null label, no condition
-                eps = cfg_eps_ref(unet_sd, x, tables[0][pos - 1], torch.zeros_like(y), None, None, 0.0)
-        _STEP_REF[key] = invert_update_ref(src, eps, pos, tables)
+                eps = cfg_eps(unet_sd, x, tables[0][pos - 1], torch.zeros_like(y), None, None, 0.0)
+        _STEP_REF[key] = invert_update(src, eps, pos, tables)
     return _STEP_REF[key]
 
 
@@ -152,7 +135,7 @@ def test_invert_step_vs_oracle(model, cuda, unet_sd, prec):
     s = src.to(cuda)
     state = torch.get_rng_state()
     with model.native().precision_override(prec):
-        out = d._step(model, x.to(cuda), pos.to(cuda), plan, True, *to(cuda, y), 0, *to(cuda, vals, mask), hist=s)
+        out = d._step(model, x.to(cuda), pos.to(cuda), plan, True, *on(cuda, y), 0, *on(cuda, vals, mask), hist=s)
     e_x, e_s = rel(out, exp), rel(s, exp_src)
     print(f"[invert step {prec} 32x32 cfg 3.0] rel-L2 vs oracle: y {e_x:.3e}, src {e_s:.3e}")
     assert e_x <= TOL and e_s <= TOL, (e_x, e_s)
@@ -167,17 +150,13 @@ def test_invert_step_without_cfg_and_foreign_model(model, cuda, unet_sd):
     d = diff.Diffuser(1000, device=cuda)
     x, src, y, vals, mask, pos = step_inputs()
 
-    class Foreign(torch.nn.Module):  # not a dmx network: no .native()
-        def forward(self, x, t, y, cond_vals=None, cond_mask=None):
-            return model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-
     outs = {}
-    for name, mdl in (("native", model), ("foreign", Foreign())):
+    for name, mdl in (("native", model), ("foreign", Foreign(model))):
         for case, g, with_y in (("cfg", 3.0, True), ("y", 0.0, True), ("no-y", 0.0, False)):
             exp, exp_src = step_ref(unet_sd, d, g, with_y)
             plan = d._plan(x.to(cuda), ("invert", 20, 0.3, 2), g)
             s = src.to(cuda)
-            cond = to(cuda, vals, mask) if with_y else (None, None)
+            cond = on(cuda, vals, mask) if with_y else (None, None)
             out = d._step(mdl, x.to(cuda), pos.to(cuda), plan, True, y.to(cuda) if with_y else None, 0, *cond, hist=s)
             e_x, e_s = rel(out, exp), rel(s, exp_src)
             print(f"[invert step {name} {case}] rel-L2 vs oracle: y {e_x:.3e}, src {e_s:.3e}")
@@ -208,7 +187,7 @@ def test_invert_trajectory_vs_restatement(model, cuda, unet_sd, case, counts, hw
     # is the case well conditioned?  (case c at four of its rows: the check costs two more trajectories)
     rows = torch.arange(B) if B <= 4 else torch.tensor([0, 11, 22, B - 1])
     gain = perturbation_gain(z0[rows], tables,
-                             lambda x, t: cfg_eps_ref(unet_sd, x, t, y[rows], vals[rows], mask[rows], g))
+                             lambda x, t: cfg_eps(unet_sd, x, t, y[rows], vals[rows], mask[rows], g))
     print(f"[invert trajectory {case}] gain of a 1e-5 perturbation of z0 on the CPU: {gain:.2f}")
     assert gain < 2.0, gain
     state = torch.get_rng_state()
@@ -217,7 +196,7 @@ def test_invert_trajectory_vs_restatement(model, cuda, unet_sd, case, counts, hw
     assert d.range_fallbacks == 0
     assert torch.equal(torch.get_rng_state(), state)
     assert out.dtype == torch.float32 and tuple(out.shape) == tuple(z0.shape)
-    exp = invert_ref(z0, tables, lambda x, t: cfg_eps_ref(unet_sd, x, t, y, vals, mask, g))
+    exp = invert_ref(z0, tables, lambda x, t: cfg_eps(unet_sd, x, t, y, vals, mask, g))
     err = rel(out, exp)
     print(f"[invert trajectory {case}] B={B} {hw}x{hw} S={S} strength={strength} R={R} g={g}: "
           f"rel-L2 vs restatement = {err:.3e}")
@@ -328,10 +307,7 @@ def test_invert_round_trip(model, cuda):
 # ---- 6: the range guard replays a chunk from its x and its src --------------------------------------
 def test_invert_range_guard_replays_in_fp32(cuda, unet_sd_overflow):
     import diff
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd_overflow)
-    m.to(cuda).eval()
+    m = make_model(cuda, unet_sd_overflow)
     g = torch.Generator().manual_seed(35)
     vals = torch.rand((2, 12), generator=g).to(cuda)
     mask = torch.ones((2, 12), device=cuda)
@@ -384,21 +360,9 @@ print("[invert-poison-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + WORKER, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_invert_loop_reads_no_unwritten_workspace(cuda, tmp_path):
-    clean = _run(tmp_path, "clean")
-    poisoned = _run(tmp_path, "poison", DMX_POISON="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    poisoned = run_worker(tmp_path, "poison", WORKER, DMX_POISON="1")
     bad = [k for k in clean if not torch.isfinite(poisoned[k]).all() or not torch.equal(clean[k], poisoned[k])]
     assert bad == [], bad
     for what in ("x", "src"):

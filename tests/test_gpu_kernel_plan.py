@@ -42,17 +42,15 @@ def record_plan(model, diffuser, prec, B, hw, dev):
     return [[r["kernel"], r["layer"]] for r in recs]
 
 
-def make_model(dev, sd):
+def model_and_diffuser(dev, sd):
     import diff
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(dev).eval(), diff.Diffuser(1000, device=dev)
+    from support import make_model
+    return make_model(dev, sd), diff.Diffuser(1000, device=dev)
 
 
 @pytest.fixture(scope="module")
 def plan_model(cuda, unet_sd):
-    return make_model(cuda, unet_sd)
+    return model_and_diffuser(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")

@@ -14,7 +14,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref
+from oracle import rules
+from oracle.rules import cfg_eps, known_blend, rel
+from support import make_model, make_vae, overflow_sd
 
 pytestmark = pytest.mark.gpu
 
@@ -22,39 +24,19 @@ TOL = 2e-5        # one step (the project's step bound)
 TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 
 
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def load_model(cuda, sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(cuda).eval()
-
-
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    return load_model(cuda, unet_sd)
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
+    return make_vae(cuda, vae_sd)
 
 
 @pytest.fixture
 def unet_sd_overflow():
-    """An overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range in the first block."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
+    return overflow_sd()
 
 
 def box_mask(B, hw, generator=None, fractional=False):
@@ -69,64 +51,17 @@ def box_mask(B, hw, generator=None, fractional=False):
     return m
 
 
-# ---- the torch restatements ---------------------------------------------------------------------
-def row(k, pos):
-    return k[pos - 1].view(-1, 1, 1, 1)
-
-
-def known_blend_ref(xg, z0, e0, m, pos, tabs):
-    """One rounding per op in x's dtype.  m None: every element kept."""
-    kn = row(tabs[0], pos) * z0 + row(tabs[1], pos) * e0
-    if m is None:
-        return kn
-    return torch.where(m == 0, kn, torch.where(m == 1, xg, m * xg + (1 - m) * kn))
-
-
-def dpm_update_ref(x, eps, pos, sched, hist):
-    """test_gpu_dpm.py's restatement: -> (x', x0)."""
-    _, k_e, k_a, k_x, k_c, k_p = sched
-    x0 = (x - row(k_e, pos) * eps) / row(k_a, pos)
-    y = row(k_x, pos) * x + row(k_c, pos) * x0
-    return torch.where(row(k_p, pos) != 0, y + row(k_p, pos) * hist, y), x0
-
-
-def ddim_update_ref(x, eps, pos, sched):
-    """test_gpu_ddim.py's restatement at eta = 0 (k_n = 0: no noise term)."""
-    _, k_e, k_a, k_s, k_d, _ = sched
-    x0 = (x - row(k_e, pos) * eps) / row(k_a, pos)
-    return row(k_s, pos) * x0 + row(k_d, pos) * eps
-
-
-def cfg_eps_ref(sd, x, pos, sched, y, vals, mask, guidance=3.0, null_label=0):
-    t = sched[0][pos - 1]  # the network sees the timestep, not the position
-    eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.full_like(y, null_label), vals, mask)
-    ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-    return eu + guidance * (ec - eu)
-
-
-def known_trajectory_ref(d, mode, e0, z0, m, p0, eps_of):
-    """Positions p0..1 of the deterministic samplers (mode = ("ddim", S, 0.0) or ("dpm", S, spacing)) from
-    the start latent, the blend after every step where m is given.  eps_of(x, pos, sched) -> eps.
-    The DPM history starts unread: row p0 of the truncated schedule is first-order (NaN would show)."""
+def known_trajectory(d, mode, e0, z0, m, p0, eps_of):
+    """rules.trajectory over positions p0..1 of the deterministic samplers (mode = ("ddim", S, 0.0) or
+    ("dpm", S, spacing)) from the start latent, the blend after every step where m is given.
+    eps_of(x, t, pos) -> eps.  Row p0 of the truncated DPM schedule is first-order (the NaN history would show)."""
     tau = d._mode_timesteps(mode)
     S = len(tau)
     tabs = d.known_tables(tau, "cpu")
-    dpm = mode[0] == "dpm"
-    sched = d.dpm_tables(S, mode[2], "cpu", start=p0) if dpm else d.ddim_tables(S, 0.0, "cpu")
-    B = e0.shape[0]
-    x = e0 if p0 == S else known_blend_ref(None, z0, e0, None, torch.full((B,), p0 + 1), tabs)
-    hist = torch.full_like(x, float("nan"))
-    with torch.no_grad():
-        for p in range(p0, 0, -1):
-            pos = torch.full((B,), p, dtype=torch.long)
-            eps = eps_of(x, pos, sched)
-            if dpm:
-                x, hist = dpm_update_ref(x, eps, pos, sched, hist)
-            else:
-                x = ddim_update_ref(x, eps, pos, sched)
-            if m is not None:
-                x = known_blend_ref(x, z0, e0, m, pos, tabs)
-    return x
+    sched = d.dpm_tables(S, mode[2], "cpu", start=p0) if mode[0] == "dpm" else d.ddim_tables(S, 0.0, "cpu")
+    x = e0 if p0 == S else known_blend(None, z0, e0, None, torch.full((e0.shape[0],), p0 + 1), tabs)
+    blend = None if m is None else (lambda x, pos: known_blend(x, z0, e0, m, pos, tabs))
+    return rules.trajectory(x, mode[0], sched, eps_of, p0=p0, blend=blend)
 
 
 # ---- 1: the blend, bit for bit -------------------------------------------------------------------
@@ -153,23 +88,23 @@ def test_known_blend_bit_exact(cuda, shape):
         dm = m.to(cuda)
         for pos in (per_sample, torch.tensor([1]), torch.tensor([S]), torch.tensor([5])):
             pfull = pos if pos.numel() == B else pos.expand(B)
-            exp = known_blend_ref(xg, z0, e0, m, pfull, tabs)
+            exp = known_blend(xg, z0, e0, m, pfull, tabs)
             out = engine.known_blend(dx, pos.to(cuda), (dz, de, dm, *dtabs))
             assert torch.equal(out.cpu(), exp), (shape, pos)
         # the mask may also be given as (B,h,w)
         out3 = engine.known_blend(dx, per_sample.to(cuda), (dz, de, dm.reshape(B, h, w), *dtabs))
-        assert torch.equal(out3.cpu(), known_blend_ref(xg, z0, e0, m, per_sample, tabs))
+        assert torch.equal(out3.cpu(), known_blend(xg, z0, e0, m, per_sample, tabs))
     # p = 1 keeps z0 itself (row 0 is (1, 0)); m == 1 passes xg through
     one = torch.tensor([1])
     assert torch.equal(engine.known_blend(dx, one.to(cuda), (dz, de, torch.zeros_like(mixed).to(cuda), *dtabs)).cpu(), z0)
     # positions outside [1, S] are clamped
     for bad, to in ((0, 1), (-3, 1), (S + 5, S)):
         out = engine.known_blend(dx, torch.tensor([bad]).to(cuda), (dz, de, mixed.to(cuda), *dtabs))
-        assert torch.equal(out.cpu(), known_blend_ref(xg, z0, e0, mixed, torch.full((B,), to), tabs))
+        assert torch.equal(out.cpu(), known_blend(xg, z0, e0, mixed, torch.full((B,), to), tabs))
     # mask None: the start-latent form writes kn and does not read x (NaN there changes nothing)
     for pos in (per_sample, torch.tensor([S]), torch.tensor([3])):
         pfull = pos if pos.numel() == B else pos.expand(B)
-        exp = known_blend_ref(None, z0, e0, None, pfull, tabs)
+        exp = known_blend(None, z0, e0, None, pfull, tabs)
         nan = torch.full(shape, float("nan"), device=cuda)
         out = engine.known_blend(nan, pos.to(cuda), (dz, de, None, *dtabs))
         assert torch.equal(out.cpu(), exp)
@@ -178,12 +113,12 @@ def test_known_blend_bit_exact(cuda, shape):
     keep = (mixed == 0).expand(shape)
     bad_x = torch.where(keep, torch.full_like(xg, float("nan")), torch.full_like(xg, float("inf")))
     out = engine.known_blend(bad_x.to(cuda), per_sample.to(cuda), (dz, de, mixed.to(cuda), *dtabs)).cpu()
-    assert torch.equal(out[keep], known_blend_ref(xg, z0, e0, mixed, per_sample, tabs)[keep])
+    assert torch.equal(out[keep], known_blend(xg, z0, e0, mixed, per_sample, tabs)[keep])
     # out may alias x
     xa = xg.to(cuda)
     res = engine.known_blend(xa, per_sample.to(cuda), (dz, de, mixed.to(cuda), *dtabs), out=xa)
     assert res.data_ptr() == xa.data_ptr()
-    assert torch.equal(xa.cpu(), known_blend_ref(xg, z0, e0, mixed, per_sample, tabs))
+    assert torch.equal(xa.cpu(), known_blend(xg, z0, e0, mixed, per_sample, tabs))
 
 
 def test_known_blend_rejects_aliases_and_mismatched_tables(model, cuda):
@@ -312,8 +247,7 @@ def test_known_trajectory_vs_oracle(model, cuda, unet_sd, case, counts, hw, mode
     assert d.range_fallbacks == 0
     torch.manual_seed(161)
     e0 = torch.randn((B, 4, hw, hw))
-    exp = known_trajectory_ref(d, mode, e0, z0, m, p0,
-                               lambda x, pos, sched: cfg_eps_ref(unet_sd, x, pos, sched, y, vals, cmask))
+    exp = known_trajectory(d, mode, e0, z0, m, p0, lambda x, t, pos: cfg_eps(unet_sd, x, t, y, vals, cmask))
     err = rel(out, exp)
     print(f"[known trajectory {case}] B={B} {hw}x{hw} {mode} p0={p0} {source}: rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -355,7 +289,7 @@ def test_known_graph_loop_equals_eager_and_keys_apart(model, cuda, unet_sd, B):
     calls = (mask1, None, mask2)
     got = [loop(nm, mk) for mk in calls]  # known, plain, known with another mask: three graph pairs in turn
     for mk, res in zip(calls, got):  # each as the same call gives it on a model that has no graph yet
-        fresh = load_model(cuda, unet_sd)
+        fresh = make_model(cuda, unet_sd)
         assert torch.equal(loop(fresh.native(), mk), res)
         del fresh
     assert torch.equal(loop(nm, mask1), got[0]) and torch.isfinite(got[0]).all()
@@ -376,7 +310,7 @@ def test_known_graph_loop_equals_eager_and_keys_apart(model, cuda, unet_sd, B):
 @pytest.mark.parametrize("source", ["host", "device"])
 def test_known_range_guard_replay(cuda, unet_sd_overflow, source):
     import diff
-    m = load_model(cuda, unet_sd_overflow)
+    m = make_model(cuda, unet_sd_overflow)
     g = torch.Generator().manual_seed(135)
     vals = torch.rand((2, 12), generator=g).to(cuda)
     cmask = torch.ones((2, 12), device=cuda)
@@ -501,7 +435,7 @@ def test_known_foreign_model_matches_restatement(cuda, mode):
                                strength=strength, **skw)
     torch.manual_seed(301)
     e0 = torch.randn((B, 4, hw, hw))
-    exp = known_trajectory_ref(d, mode, e0, z0, m, p0, lambda x, pos, sched: mixture_eps(x, ab[sched[0][pos - 1] - 1]))
+    exp = known_trajectory(d, mode, e0, z0, m, p0, lambda x, t, pos: mixture_eps(x, ab[t - 1]))
     err = rel(got, exp)
     print(f"[known foreign {mode}] rel-L2 vs the fp32 CPU restatement = {err:.3e}")
     assert err <= TOL, err

@@ -192,10 +192,8 @@ def test_sharded_world1_range_guard_equals_diffuser(cuda, unet_sd_overflow):
 
 @pytest.fixture
 def unet_sd_overflow():
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
+    from support import overflow_sd
+    return overflow_sd()
 
 
 # ---- data-parallel training step ----------------------------------

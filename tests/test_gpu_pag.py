@@ -10,17 +10,15 @@ Measured on an MI355X (rel-L2): perturbed forward rows against the patched oracl
 fp32), 1.04e-3 (f16); the perturbation itself moves eps by 0.080 (sa3) .. 0.47 (all six); PAG steps 6.7e-8 ..
 7.2e-8 (ddpm), 2.1e-6 .. 3.0e-6 (ddim, dpm); B = 22 with three branches 2.6e-6; trajectories 5.7e-7 .. 2.0e-6;
 the bit-equalities hold."""
-import contextlib
 import ctypes
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import ref
+from oracle import ref, rules
+from oracle.rules import ALL6, composed_eps, ddim_update, dpm_update, perturbed_forward, rel
+from support import cond, device_noise, make_model, make_vae, mode_tables, run_worker
 
 pytestmark = pytest.mark.gpu
 
@@ -29,25 +27,10 @@ TRAJ_TOL = 1e-4   # a trajectory (the project's trajectory bound)
 TOL_FWD = 2e-3    # one forward in f16 mode (the project's config-4 bound)
 G = 3.0
 S = 3.0
-ALL6 = ("sa1", "sa2", "sa3", "sa4", "sa5", "sa6")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def bits(names):
     return sum(1 << ALL6.index(n) for n in names)
-
-
-def make_model(cuda, sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(cuda).eval()
 
 
 @pytest.fixture(scope="module")
@@ -59,87 +42,6 @@ def model(cuda, unet_sd):
 def model2(cuda, unet_sd):
     """A second network with the same weights: its own arena and its own graph slots."""
     return make_model(cuda, unet_sd)
-
-
-# ---- the oracle with identity attention -----------------------------------------------------------------
-@contextlib.contextmanager
-def identity_attention(names):
-    """ref.attention with softmax(s) = I in the blocks `names`: the attention output of a token is its own
-    value vector.  unet_trunk looks `attention` up at call time; the original is restored afterwards."""
-    orig = ref.attention
-
-    def attention(sd, p, x):
-        if p not in names:
-            return orig(sd, p, x)
-        n, c, hh, ww = x.shape
-        tok = x.reshape(n, c, hh * ww).transpose(1, 2)
-        xl = F.layer_norm(tok, (c,), sd[f"{p}.ln.weight"], sd[f"{p}.ln.bias"], 1e-5)
-        qkv = F.linear(xl, sd[f"{p}.mha.in_proj_weight"], sd[f"{p}.mha.in_proj_bias"])
-        a = qkv[..., 2 * c:]
-        a = F.linear(a, sd[f"{p}.mha.out_proj.weight"], sd[f"{p}.mha.out_proj.bias"]) + xl
-        f = F.layer_norm(a, (c,), sd[f"{p}.ff_self.0.weight"], sd[f"{p}.ff_self.0.bias"], 1e-5)
-        f = F.linear(f, sd[f"{p}.ff_self.1.weight"], sd[f"{p}.ff_self.1.bias"])
-        f = F.linear(F.gelu(f), sd[f"{p}.ff_self.3.weight"], sd[f"{p}.ff_self.3.bias"])
-        return (f + a).transpose(1, 2).reshape(n, c, hh, ww)
-
-    ref.attention = attention
-    try:
-        yield
-    finally:
-        ref.attention = orig
-
-
-def forward_ref(sd, x, t, y, vals, mask, names=()):
-    with identity_attention(set(names)) if names else contextlib.nullcontext(), torch.no_grad():
-        return ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)[0]
-
-
-def mix_ref(es, w):
-    """es: K + 1 tensors (n,c,h,w), es[0] the base; w (K,n).  fp32, one rounding per torch op."""
-    def col(k):
-        return w[k].view(-1, 1, 1, 1)
-    s = col(0) * (es[1] - es[0])
-    for k in range(2, len(es)):
-        s = s + col(k - 1) * (es[k] - es[0])
-    return es[0] + s
-
-
-def eps_ref(sd, x, t, comp, pt):
-    """The mixed eps from the oracle: one forward per branch, the branches of pt's mask perturbed."""
-    y_rows, v_rows, m_rows, w = comp
-    names = [n for i, n in enumerate(ALL6) if pt[0] >> i & 1]
-    es = [forward_ref(sd, x, t, y_rows[k], v_rows[k], m_rows[k], names if pt[1] >> k & 1 else ())
-          for k in range(y_rows.shape[0])]
-    return mix_ref(es, w)
-
-
-def ddim_update_ref(x, eps, pos, sched, nz):
-    _, k_e, k_a, k_s, k_d, k_n = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    return row(k_s) * x0 + row(k_d) * eps + row(k_n) * nz
-
-
-def dpm_update_ref(x, eps, pos, sched, hist):
-    _, k_e, k_a, k_x, k_c, k_p = sched
-
-    def row(k):
-        return k[pos - 1].view(-1, 1, 1, 1)
-
-    x0 = (x - row(k_e) * eps) / row(k_a)
-    y = row(k_x) * x + row(k_c) * x0
-    return torch.where(row(k_p) != 0, y + row(k_p) * hist, y), x0
-
-
-def cond(B, seed):
-    g = torch.Generator().manual_seed(seed)
-    y = torch.tensor([1 + i % 3 for i in range(B)])
-    vals = torch.rand((B, 12), generator=g)
-    mask = (torch.rand((B, 12), generator=g) > 0.3).float()
-    return y, vals, mask
 
 
 def to(comp, dev):
@@ -167,16 +69,6 @@ def pag_case(d, name, B, seed):
     if name == "sa13":
         return d._pag_args(S, ("sa1", "sa3"), y.tolist(), vals, mask, G)
     raise KeyError(name)
-
-
-def device_noise(d, seed, shape, t, cuda):
-    """The Philox normals a DDPM / DDIM step draws at timestep t: an update with x = eps = 0,
-    c2 = sd = 1 returns them unchanged (none at t = 1)."""
-    from dmx import engine
-    T = d.num_timesteps
-    z = torch.zeros(shape, device=cuda)
-    tabs = (torch.zeros(T, device=cuda), torch.ones(T, device=cuda), torch.ones(T, device=cuda))
-    return engine.ddpm_update(z, z, None, 0.0, torch.full((shape[0],), t, device=cuda), tabs, None, seed=seed).cpu()
 
 
 # ---- 1: the identity kernel ---------------------------------------------------------------------------------
@@ -217,7 +109,7 @@ def fwd_ref(sd, hw, names):
     key = (hw, tuple(names))
     if key not in _FWD_REF:
         B, x, t, y, vals, mask = fwd_inputs(hw)
-        _FWD_REF[key] = forward_ref(sd, x[B:], t[B:], y[B:], vals[B:], mask[B:], names)
+        _FWD_REF[key] = perturbed_forward(sd, x[B:], t[B:], y[B:], vals[B:], mask[B:], names)
     return _FWD_REF[key]
 
 
@@ -305,7 +197,7 @@ def step_ref(unet_sd, d, name, B, hw):
         x, hist, nz = (torch.randn((B, 4, hw, hw), generator=gen) for _ in range(3))
         comp, pt = pag_case(d, name, B, 401 + hw)
         t = torch.full((B,), 600, dtype=torch.long)
-        _STEP_REF[key] = (x, hist, nz, comp, pt, t, eps_ref(unet_sd, x, t, comp, pt))
+        _STEP_REF[key] = (x, hist, nz, comp, pt, t, composed_eps(unet_sd, x, t, comp, pt))
     return _STEP_REF[key]
 
 
@@ -320,9 +212,9 @@ def pag_step_vs_oracle(nm, d, cuda, unet_sd, kind, name, B, hw, philox=False):
         _, a, ab = ref.schedule(1000)
         exp = ref.ddpm_update(x, eps, t, a, ab, nz)
     elif kind == "ddim":
-        exp = ddim_update_ref(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
+        exp = ddim_update(x, eps, pos, d.ddim_tables(5, 0.5, "cpu"), nz)
     else:
-        exp, exp_h = dpm_update_ref(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
+        exp, exp_h = dpm_update(x, eps, pos, d.dpm_tables(5, "uniform", "cpu"), hist)
     h = hist.to(cuda)
     step_call(nm, d, cuda, kind, x.to(cuda), out, None if philox else nz.to(cuda), h, pos.to(cuda), t.to(cuda),
               compose=to(comp, cuda), perturb=pt, **kw)
@@ -405,23 +297,7 @@ def test_pag_trajectory_vs_oracle(model, cuda, unet_sd, case, T, kw, source):
     else:
         seed = d._seed()  # drawn after x_T, as the sampler does
         noise_of = lambda p: device_noise(d, seed, x.shape, tau[p - 1], cuda)  # noqa: E731
-    if mode is None:
-        _, a, ab = ref.schedule(T)
-    elif mode[0] == "ddim":
-        sched = d.ddim_tables(mode[1], mode[2], "cpu")
-    else:
-        sched = d.dpm_tables(mode[1], mode[2], "cpu")
-    hist = torch.full_like(x, float("nan"))
-    for p in range(len(tau), 0, -1):
-        t = torch.full((B,), tau[p - 1], dtype=torch.long)
-        pos = torch.full((B,), p, dtype=torch.long)
-        eps = eps_ref(unet_sd, x, t, comp, pt)
-        if mode is None:
-            x = ref.ddpm_update(x, eps, t, a, ab, noise_of(p))
-        elif mode[0] == "ddim":
-            x = ddim_update_ref(x, eps, pos, sched, noise_of(p))
-        else:
-            x, hist = dpm_update_ref(x, eps, pos, sched, hist)
+    x = rules.trajectory(x, *mode_tables(d, mode), lambda x, t, pos: composed_eps(unet_sd, x, t, comp, pt), noise_of)
     assert torch.isfinite(x).all()
     err = rel(out, x)
     print(f"[pag trajectory {case} {source}] B={B} {hw}x{hw}: rel-L2 vs oracle = {err:.3e}")
@@ -606,10 +482,7 @@ def test_entity_csv_sampler_passes_pag(model, cuda, vae_sd):
     import numpy as np
     from conftest import GOLDEN
     from entityCsvSampler import EntityCsvSampler
-    from models.vae import VAE
-    vae = VAE()
-    vae.load_state_dict(vae_sd)
-    vae = vae.to(cuda).eval()
+    vae = make_vae(cuda, vae_sd)
     csv = os.path.join(GOLDEN, "entities.csv")
     d = diff.Diffuser(1000, device=cuda)
     s = EntityCsvSampler(d, model, vae, class_id=1, base_wh=(400, 400), device=cuda)
@@ -780,23 +653,11 @@ print("[pag-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + WORKER, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_pag_step_reads_no_unwritten_workspace(cuda, tmp_path):
     """PAG steps and perturbed forwards (a range in the middle of the batch) in fresh processes, with
     and without DMX_POISON=1 / DMX_CHECK=1: finite and bit-identical."""
-    clean = _run(tmp_path, "clean")
-    diag = _run(tmp_path, "diag", DMX_POISON="1", DMX_CHECK="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    diag = run_worker(tmp_path, "diag", WORKER, DMX_POISON="1", DMX_CHECK="1")
     assert len(clean) == 8
     bad = [k for k in clean if not torch.isfinite(diag[k]).all() or not torch.equal(clean[k], diag[k])]
     assert bad == [], bad

@@ -12,16 +12,12 @@ import pytest
 import torch
 
 from oracle import ref
+from oracle.rules import rel
+from support import make_model, make_vae
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def u8_close(a, b, frac=1e-3):
@@ -31,18 +27,12 @@ def u8_close(a, b, frac=1e-3):
 
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
+    return make_vae(cuda, vae_sd)
 
 
 def test_library_is_native(cuda):

@@ -3,17 +3,12 @@ shards) and training forward / backward run in two fresh processes, one with eve
 filled with 0xFF bytes (fp32 NaN) before use (DMX_POISON=1, engine.hip poison()), one without.
 Outputs must be finite and bit-identical: a read of stale memory would turn them NaN (or make
 results depend on what a previous model left in reused device memory)."""
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from support import run_worker
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+pytestmark = pytest.mark.gpu
 
 WORKER = r'''
 import os, sys
@@ -72,26 +67,14 @@ print("[poison-worker] ok", flush=True)
 '''
 
 
-def _run(tmp_path, tag, worker=WORKER, **env_over):
-    path = str(tmp_path / f"out_{tag}.pt")
-    env = dict(os.environ, **env_over)
-    for k in ("DMX_POISON", "DMX_CHECK", "DMX_PRECISION"):
-        if k not in env_over:
-            env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + worker, path], env=env, capture_output=True,
-                       text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return torch.load(path, weights_only=True)
-
-
 def test_no_reads_of_unwritten_workspace(cuda, tmp_path):
-    clean = _run(tmp_path, "clean")
-    poisoned = _run(tmp_path, "poison", DMX_POISON="1")
+    clean = run_worker(tmp_path, "clean", WORKER)
+    poisoned = run_worker(tmp_path, "poison", WORKER, DMX_POISON="1")
     bad = [k for k in clean if not torch.isfinite(poisoned[k]).all() or not torch.equal(clean[k], poisoned[k])]
     assert bad == [], bad[:10]
     # DMX_CHECK=1 (operand-range and plan/run allocation checks before every GEMM launch) raises on
     # nothing and changes nothing
-    checked = _run(tmp_path, "check", DMX_CHECK="1")
+    checked = run_worker(tmp_path, "check", WORKER, DMX_CHECK="1")
     bad = [k for k in clean if not torch.equal(clean[k], checked[k])]
     assert bad == [], bad[:10]
     # shard consistency (same process, same kernels): B = 5 equals its 3 + 2 shards
@@ -142,7 +125,7 @@ torch.save(out, sys.argv[1])
 def test_precision_env_selects_the_default_mode(cuda, tmp_path, prec):
     """DMX_PRECISION sets the precision new native models start in: the default
     step equals the explicitly selected mode's step bit for bit."""
-    r = _run(tmp_path, "prec_" + prec, PREC_WORKER, DMX_PRECISION=prec)
+    r = run_worker(tmp_path, "prec_" + prec, PREC_WORKER, DMX_PRECISION=prec)
     assert int(r["prec"]) == ["fp32", "x3", "f16"].index(prec)
     assert torch.equal(r["default"], r[prec])
     assert not torch.equal(r["fp32"], r["f16"])  # (the modes do differ)

@@ -20,9 +20,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
-from test_gpu_parity import TOL, rel  # noqa: E402
+from test_gpu_parity import TOL  # noqa: E402
 from test_vae_train_oracle import GOLD, oracle_step, params_after_close, vae_grad_stats_close  # noqa: E402
 from oracle import ref  # noqa: E402
+from oracle.rules import rel  # noqa: E402
 
 GRAD_TOL = 1e-4
 

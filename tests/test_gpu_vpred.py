@@ -6,16 +6,17 @@ The v-rule of every step: oracle forward(s) -> the mix in output s
 perturbed branch, CFG rescale, geometry guidance) -> the conversion, once,
     eps = p_o[t-1] out + p_x[t-1] x_net      p_o = sqrt(ab), p_x = sqrt(1-ab), t the network timestep,
                                              x_net the latent the network was evaluated at
--> the eps-form update restated as in the rules' own test files.  Bounds are the project's: 2e-5 for one
+-> the eps-form update, all restated in oracle/rules.py.  Bounds are the project's: 2e-5 for one
 step, 1e-4 for a trajectory and for a gradient tensor, 2e-5 for the loss, rel-L2 against the fp32 oracle."""
-import contextlib
 import os
 
 import pytest
 import torch
-import torch.nn.functional as F
 
-from oracle import ref, train_ref
+from oracle import ref, rules, train_ref
+from oracle.rules import (Foreign, cfg_eps, cfg_rescaled, composed_eps, ddim_update, dpm_update, invert_update,
+                          known_blend, rel, row)
+from support import cond, device_noise, make_model, mode_tables, on, overflow_sd
 
 pytestmark = pytest.mark.gpu
 
@@ -25,19 +26,6 @@ GRAD_TOL = 1e-4   # a gradient tensor (the project's bound for the native backwa
 LOSS_TOL = 2e-5
 G = 3.0
 T = 1000
-
-
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-def make_model(cuda, sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(sd)
-    return m.to(cuda).eval()
 
 
 @pytest.fixture(scope="module")
@@ -70,141 +58,9 @@ def de(dev, T=T):
     return diff.Diffuser(T, device=dev)
 
 
-def on(dev, *ts):
-    return tuple(None if t is None else t.to(dev) for t in ts)
-
-
-class Foreign(torch.nn.Module):
-    """Not a dmx network (no .native()): the model-call + pred_to_eps + standalone-update path."""
-
-    def __init__(self, inner):
-        super().__init__()
-        self.inner = [inner]
-
-    def forward(self, x, t, y, cond_vals=None, cond_mask=None):
-        return self.inner[0](x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-
-
-# ---- the torch restatements (fp32 CPU, one rounding per op in torch's evaluation order) -----------------
-def row(k, i):
-    return k[i - 1].view(-1, 1, 1, 1)
-
-
-def to_eps_ref(d, out, x_net, t):
-    """The conversion at the network timesteps t (B,)."""
-    p_o, p_x = d.pred_tables("cpu")
-    return row(p_o, t) * out + row(p_x, t) * x_net
-
-
-def cfg_out_ref(sd, x, t, y, vals, mask, g=G, null_label=0):
-    """The network's mixed output at the timesteps t: CFG, or one conditional forward for g = 0."""
-    with torch.no_grad():
-        ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-        if not g > 0:
-            return ec
-        eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.full_like(y, null_label), vals, mask)
-    return eu + g * (ec - eu)
-
-
-def ddim_update_ref(x, eps, pos, sched, nz):
-    _, k_e, k_a, k_s, k_d, k_n = sched
-    x0 = (x - row(k_e, pos) * eps) / row(k_a, pos)
-    return row(k_s, pos) * x0 + row(k_d, pos) * eps + row(k_n, pos) * nz
-
-
-def dpm_update_ref(x, eps, pos, sched, hist):
-    _, k_e, k_a, k_x, k_c, k_p = sched
-    x0 = (x - row(k_e, pos) * eps) / row(k_a, pos)
-    y = row(k_x, pos) * x + row(k_c, pos) * x0
-    return torch.where(row(k_p, pos) != 0, y + row(k_p, pos) * hist, y), x0
-
-
-def invert_update_ref(src, eps, c, tables):
-    _, i_x, i_e, adv = tables
-    y = row(i_x, c) * src + row(i_e, c) * eps
-    return y, torch.where(row(adv, c) != 0, y, src)
-
-
-def known_blend_ref(xg, z0, e0, m, pos, tabs):
-    kn = row(tabs[0], pos) * z0 + row(tabs[1], pos) * e0
-    if m is None:
-        return kn
-    return torch.where(m == 0, kn, torch.where(m == 1, xg, m * xg + (1 - m) * kn))
-
-
-def rescale_ref(eu, ec, g, phi):
-    """CFG rescale on the network's outputs (here: on v) -> the rescaled mix."""
-    eg = eu + g * (ec - eu)
-    sg = eg.double().flatten(1).std(1)
-    sc = ec.double().flatten(1).std(1)
-    r = 1.0 + phi * (sc / sg - 1.0)
-    return eg * r.float().view(-1, 1, 1, 1)
-
-
-def mix_ref(es, w):
-    def col(k):
-        return w[k].view(-1, 1, 1, 1)
-    s = col(0) * (es[1] - es[0])
-    for k in range(2, len(es)):
-        s = s + col(k - 1) * (es[k] - es[0])
-    return es[0] + s
-
-
-ALL6 = ("sa1", "sa2", "sa3", "sa4", "sa5", "sa6")
-
-
-@contextlib.contextmanager
-def identity_attention(names):
-    """ref.attention with softmax(s) = I in the blocks `names` (unet_trunk looks it up at call time)."""
-    orig = ref.attention
-
-    def attention(sd, p, x):
-        if p not in names:
-            return orig(sd, p, x)
-        n, c, hh, ww = x.shape
-        tok = x.reshape(n, c, hh * ww).transpose(1, 2)
-        xl = F.layer_norm(tok, (c,), sd[f"{p}.ln.weight"], sd[f"{p}.ln.bias"], 1e-5)
-        qkv = F.linear(xl, sd[f"{p}.mha.in_proj_weight"], sd[f"{p}.mha.in_proj_bias"])
-        a = F.linear(qkv[..., 2 * c:], sd[f"{p}.mha.out_proj.weight"], sd[f"{p}.mha.out_proj.bias"]) + xl
-        f = F.layer_norm(a, (c,), sd[f"{p}.ff_self.0.weight"], sd[f"{p}.ff_self.0.bias"], 1e-5)
-        f = F.linear(f, sd[f"{p}.ff_self.1.weight"], sd[f"{p}.ff_self.1.bias"])
-        f = F.linear(F.gelu(f), sd[f"{p}.ff_self.3.weight"], sd[f"{p}.ff_self.3.bias"])
-        return (f + a).transpose(1, 2).reshape(n, c, hh, ww)
-
-    ref.attention = attention
-    try:
-        yield
-    finally:
-        ref.attention = orig
-
-
-def composed_out_ref(sd, x, t, comp, pt=None):
-    """The composed output: one oracle forward per branch (the branches of pt's mask perturbed), then the mix."""
-    y_rows, v_rows, m_rows, w = comp
-    es = []
-    for k in range(y_rows.shape[0]):
-        names = {n for i, n in enumerate(ALL6) if pt is not None and pt[0] >> i & 1 and pt[1] >> k & 1}
-        with identity_attention(names) if names else contextlib.nullcontext(), torch.no_grad():
-            es.append(ref.unet_cond_geom_forward(sd, x, t, y_rows[k], v_rows[k], m_rows[k])[0])
-    return mix_ref(es, w)
-
-
-def device_noise(d, seed, shape, t, cuda):
-    """The Philox normals a DDPM / DDIM step draws at timestep t: an eps-form update with x = eps = 0,
-    c2 = sd = 1 returns them unchanged (none at t = 1)."""
-    from dmx import engine
-    n = d.num_timesteps
-    z = torch.zeros(shape, device=cuda)
-    tabs = (torch.zeros(n, device=cuda), torch.ones(n, device=cuda), torch.ones(n, device=cuda))
-    return engine.ddpm_update(z, z, None, 0.0, torch.full((shape[0],), t, device=cuda), tabs, None, seed=seed).cpu()
-
-
-def cond(B, seed):
-    g = torch.Generator().manual_seed(seed)
-    y = torch.tensor([1 + i % 3 for i in range(B)])
-    vals = torch.rand((B, 12), generator=g)
-    mask = (torch.rand((B, 12), generator=g) > 0.3).float()
-    return y, vals, mask
+def to_eps_of(d, out, x_net, t):
+    """rules.to_eps at the network timesteps t (B,) with d's tables."""
+    return rules.to_eps(out, x_net, t, *d.pred_tables("cpu"))
 
 
 # ---- 1: the standalone conversion, bit for bit ---------------------------------------------------------
@@ -216,7 +72,7 @@ def test_pred_to_eps_bit_exact(cuda, shape):
     g = torch.Generator().manual_seed(11 + shape[1] + shape[2])
     out, x = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
     t = torch.tensor(([1, 2, 500, 999, 1000, 37] * 2)[:B])
-    exp = to_eps_ref(d, out, x, t)
+    exp = to_eps_of(d, out, x, t)
     tabs = d.pred_tables(cuda)
     assert torch.equal(tabs[0].cpu(), d.noise_tables("cpu")[0]) and torch.equal(tabs[1].cpu(), d.noise_tables("cpu")[1])
     got = engine.pred_to_eps(out.to(cuda), x.to(cuda), t.to(cuda), *tabs)
@@ -232,10 +88,10 @@ def test_pred_to_eps_bit_exact(cuda, shape):
     assert ts.stride(0) == 2
     assert torch.equal(engine.pred_to_eps(out.to(cuda), x.to(cuda), ts, *tabs).cpu(), exp)
     one = engine.pred_to_eps(out.to(cuda), x.to(cuda), torch.tensor([500], device=cuda), *tabs)
-    assert torch.equal(one.cpu(), to_eps_ref(d, out, x, torch.full((B,), 500)))
+    assert torch.equal(one.cpu(), to_eps_of(d, out, x, torch.full((B,), 500)))
     # timesteps outside [1, T] are clamped for the table reads
     far = engine.pred_to_eps(out.to(cuda), x.to(cuda), torch.tensor([-3, 5000] * 3, device=cuda)[:B], *tabs)
-    assert torch.equal(far.cpu(), to_eps_ref(d, out, x, torch.tensor([1, T] * 3)[:B]))
+    assert torch.equal(far.cpu(), to_eps_of(d, out, x, torch.tensor([1, T] * 3)[:B]))
     with pytest.raises(ValueError):
         engine.pred_to_eps(out.to(cuda), x.to(cuda)[:, :1], t.to(cuda), *tabs)
     with pytest.raises(ValueError):
@@ -344,16 +200,16 @@ def step_ref(sd, rule, g=G):
         x, other, y, vals, mask, nz = step_inputs()
         pos, t, sched = rule_case(d, rule)
         assert pos.tolist() != t.tolist() or rule == "ddpm"  # position differs from timestep
-        eps = to_eps_ref(d, cfg_out_ref(sd, x, t, y, vals, mask, g), x, t)
+        eps = to_eps_of(d, cfg_eps(sd, x, t, y, vals, mask, g), x, t)
         if rule == "ddpm":
             _, a, ab = ref.schedule(T)
             _STEP[key] = (ref.ddpm_update(x, eps, t, a, ab, nz), None)
         elif rule == "ddim":
-            _STEP[key] = (ddim_update_ref(x, eps, pos, sched, nz), None)
+            _STEP[key] = (ddim_update(x, eps, pos, sched, nz), None)
         elif rule == "dpm":
-            _STEP[key] = dpm_update_ref(x, eps, pos, sched, other)
+            _STEP[key] = dpm_update(x, eps, pos, sched, other)
         else:
-            _STEP[key] = invert_update_ref(other, eps, pos, sched)
+            _STEP[key] = invert_update(other, eps, pos, sched)
     return _STEP[key]
 
 
@@ -422,7 +278,7 @@ def test_unconditional_unet_denoise(unet3, unet3_sd, cuda, prec):
     with torch.no_grad():
         out_ref = ref.unet_forward(unet3_sd, x, t)
     _, a, ab = ref.schedule(T)
-    exp = ref.ddpm_update(x, to_eps_ref(d, out_ref, x, t), t, a, ab, nz, clamp_prev=False)
+    exp = ref.ddpm_update(x, to_eps_of(d, out_ref, x, t), t, a, ab, nz, clamp_prev=False)
 
     class Wrapped(torch.nn.Module):
         def forward(self, x, t):
@@ -438,30 +294,6 @@ def test_unconditional_unet_denoise(unet3, unet3_sd, cuda, prec):
 
 
 # ---- 4: trajectories -----------------------------------------------------------------------------------
-def trajectory_ref(sd, d, mode, x, y, vals, mask, noise_of, out_of=None):
-    tau = d._mode_timesteps(mode)
-    B = x.shape[0]
-    if mode is None:
-        _, a, ab = ref.schedule(d.num_timesteps)
-    elif mode[0] == "ddim":
-        sched = d.ddim_tables(mode[1], mode[2], "cpu")
-    else:
-        sched = d.dpm_tables(mode[1], mode[2], "cpu")
-    out_of = out_of or (lambda x, t: cfg_out_ref(sd, x, t, y, vals, mask))
-    hist = torch.full_like(x, float("nan"))
-    for p in range(len(tau), 0, -1):
-        t = torch.full((B,), tau[p - 1], dtype=torch.long)
-        pos = torch.full((B,), p, dtype=torch.long)
-        eps = to_eps_ref(d, out_of(x, t), x, t)
-        if mode is None:
-            x = ref.ddpm_update(x, eps, t, a, ab, noise_of(p))
-        elif mode[0] == "ddim":
-            x = ddim_update_ref(x, eps, pos, sched, noise_of(p))
-        else:
-            x, hist = dpm_update_ref(x, eps, pos, sched, hist)
-    return x
-
-
 def sample_vs_oracle(model, cuda, sd, Tn, hw, kw, source, seed, extra=None, out_of=None, tag=""):
     d = dv(cuda, Tn)
     d.noise_source = source
@@ -484,8 +316,8 @@ def sample_vs_oracle(model, cuda, sd, Tn, hw, kw, source, seed, extra=None, out_
     else:
         s = d._seed()  # drawn after x_T, as the sampler does
         noise_of = lambda p: device_noise(d, s, x.shape, tau[p - 1], cuda)  # noqa: E731
-    bound = out_of(d, y, vals, mask) if out_of is not None else None
-    exp = trajectory_ref(sd, d, mode, x, y, vals, mask, noise_of, bound)
+    out_of = out_of(d, y, vals, mask) if out_of is not None else (lambda x, t: cfg_eps(sd, x, t, y, vals, mask))
+    exp = rules.trajectory(x, *mode_tables(d, mode), lambda x, t, pos: to_eps_of(d, out_of(x, t), x, t), noise_of)
     err = rel(out, exp)
     print(f"[v trajectory {tag or kw} {hw}x{hw} {source}] rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -571,7 +403,7 @@ def test_rescale_measures_v(model, cuda, unet_sd):
             with torch.no_grad():
                 ec, _ = ref.unet_cond_geom_forward(unet_sd, x, t, y, vals, mask)
                 eu, _ = ref.unet_cond_geom_forward(unet_sd, x, t, torch.zeros_like(y), vals, mask)
-            return rescale_ref(eu, ec, G, 0.7)
+            return cfg_rescaled(eu, ec, G, 0.7)
         return f
     for kw in (dict(sampler="dpmpp_2m", steps=3), dict(sampler="ddim", steps=2, eta=0.0)):
         sample_vs_oracle(model, cuda, unet_sd, T, 16, kw, "device", 71, dict(guidance_rescale=0.7), out_of, "rescale")
@@ -587,7 +419,7 @@ def test_composed_k2(model, cuda, unet_sd):
     def out_of(d, y, vals, mask):
         comp = d._compose_args(y.tolist(), vals, mask, G, "null", also, device="cpu")
         assert comp[0].shape[0] == 3  # K = 2
-        return lambda x, t: composed_out_ref(unet_sd, x, t, comp)
+        return lambda x, t: composed_eps(unet_sd, x, t, comp)
     sample_vs_oracle(model, cuda, unet_sd, T, 16, dict(sampler="ddim", steps=3, eta=0.0), "device", 82,
                      dict(also=also), out_of, "also K=2")
     sample_vs_oracle(model, cuda, unet_sd, 4, 16, dict(), "host", 82, dict(also=also), out_of, "also K=2 ddpm")
@@ -598,7 +430,7 @@ def test_composed_k2(model, cuda, unet_sd):
 def test_pag(model, cuda, unet_sd):
     def out_of(d, y, vals, mask):
         comp, pt = d._pag_args(2.0, ("sa3",), y.tolist(), vals, mask, G)
-        return lambda x, t: composed_out_ref(unet_sd, x, t, comp, pt)
+        return lambda x, t: composed_eps(unet_sd, x, t, comp, pt)
     sample_vs_oracle(model, cuda, unet_sd, T, 16, dict(sampler="ddim", steps=2, eta=0.0), "device", 91,
                      dict(pag_scale=2.0), out_of, "pag")
 
@@ -620,13 +452,13 @@ def test_geom_step_shows_the_divided_sig(model, cuda, unet_sd, rule):
     e_sig = de(cuda)._plan(x.to(cuda), None if rule == "ddpm" else ("ddim", S3, 0.5), G, geom=scale).geom[1].cpu()
     # the eps-mode table over sqrt(ab): the tables' own roots (the strided rules': k_e over k_a)
     assert torch.equal(sig, e_sig / (p_o if rule == "ddpm" else sched[2]))
-    out_g = cfg_out_ref(unet_sd, x, t, y, vals, mask)
+    out_g = cfg_eps(unet_sd, x, t, y, vals, mask)
     mixed = out_g + (scale * sig[pos - 1]).view(-1, 1, 1, 1) * grad
     _, a, ab = ref.schedule(T)
 
     def upd(o):
-        eps = to_eps_ref(d, o, x, t)
-        return ref.ddpm_update(x, eps, t, a, ab, nz) if rule == "ddpm" else ddim_update_ref(x, eps, pos, sched, nz)
+        eps = to_eps_of(d, o, x, t)
+        return ref.ddpm_update(x, eps, t, a, ab, nz) if rule == "ddpm" else ddim_update(x, eps, pos, sched, nz)
 
     exp, plain = upd(mixed), upd(out_g)
     share = float((exp - plain).norm() / exp.norm())
@@ -665,12 +497,12 @@ def test_init_latent_and_mask(model, cuda, unet_sd):
     mode = ("ddim", S, 0.0)
     tau = d._mode_timesteps(mode)
     tabs, sched = d.known_tables(tau, "cpu"), d.ddim_tables(S, 0.0, "cpu")
-    x = known_blend_ref(None, z0, e0, None, torch.full((B,), p0 + 1), tabs)
+    x = known_blend(None, z0, e0, None, torch.full((B,), p0 + 1), tabs)
     for p in range(p0, 0, -1):
         pos = torch.full((B,), p, dtype=torch.long)
         t = sched[0][pos - 1]
-        eps = to_eps_ref(d, cfg_out_ref(unet_sd, x, t, y, vals, mask), x, t)
-        x = known_blend_ref(ddim_update_ref(x, eps, pos, sched, torch.zeros_like(x)), z0, e0, m, pos, tabs)
+        eps = to_eps_of(d, cfg_eps(unet_sd, x, t, y, vals, mask), x, t)
+        x = known_blend(ddim_update(x, eps, pos, sched, torch.zeros_like(x)), z0, e0, m, pos, tabs)
     err = rel(out, x)
     print(f"[v inpaint ddim S={S} p0={p0}] rel-L2 vs oracle = {err:.3e}")
     assert err <= TRAJ_TOL, err
@@ -690,7 +522,7 @@ def test_cache_refresh_steps_are_plain_v_steps(model, cuda, unet_sd):
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     t = sched[0][pos - 1].cpu()
     xc, yc, vc, mc = x.cpu(), y.cpu(), vals.cpu(), mask.cpu()
-    exp = ddim_update_ref(xc, to_eps_ref(d, cfg_out_ref(unet_sd, xc, t, yc, vc, mc), xc, t), pos.cpu(),
+    exp = ddim_update(xc, to_eps_of(d, cfg_eps(unet_sd, xc, t, yc, vc, mc), xc, t), pos.cpu(),
                           d.ddim_tables(S3, 0.5, "cpu"), nz.cpu())
     assert rel(outs[1], exp) <= TOL
     # a reuse step converts too: it runs, is finite and differs from the eps reading of the same step
@@ -725,14 +557,14 @@ def test_invert_then_start_latent_round_trip(model, cuda, unet_sd):
     for c in range(N, 0, -1):  # the conversion reads the latent the network saw: x, not src
         pos = torch.full((B,), c, dtype=torch.long)
         t = tables[0][pos - 1]
-        x, src = invert_update_ref(src, to_eps_ref(d, cfg_out_ref(unet_sd, x, t, y, vals, mask), x, t), pos, tables)
+        x, src = invert_update(src, to_eps_of(d, cfg_eps(unet_sd, x, t, y, vals, mask), x, t), pos, tables)
     e_inv = rel(lat, x)
     xb = x
     for p in range(S, 0, -1):
         pos = torch.full((B,), p, dtype=torch.long)
         t = sched[0][pos - 1]
-        eps = to_eps_ref(d, cfg_out_ref(unet_sd, xb, t, y, vals, mask), xb, t)
-        xb = ddim_update_ref(xb, eps, pos, sched, torch.zeros_like(xb))
+        eps = to_eps_of(d, cfg_eps(unet_sd, xb, t, y, vals, mask), xb, t)
+        xb = ddim_update(xb, eps, pos, sched, torch.zeros_like(xb))
     e_back = rel(back, xb)
     print(f"[v invert S={S} R={R}] rel-L2 vs restatement: inverted {e_inv:.3e}, sampled back {e_back:.3e}; "
           f"round trip vs z0 {rel(back, z0):.3e} (restatement {rel(xb, z0):.3e})")
@@ -821,11 +653,7 @@ def test_training_loss_vs_oracle(cuda, train_model, unet_sd, B, hw, weighting):
 # ---- 8: the range guard -----------------------------------------------------------------------------------
 @pytest.fixture
 def unet_sd_overflow():
-    """An overflowing GroupNorm gamma: the x3 split's hi plane leaves the f16 range in the first block."""
-    from dmx import synth
-    sd = synth.unet_cond_geom_weights(0)
-    sd["inc.double_conv.1.weight"] = sd["inc.double_conv.1.weight"] * 1e5
-    return sd
+    return overflow_sd()
 
 
 @pytest.mark.parametrize("source", ["host", "device"])

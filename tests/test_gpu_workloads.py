@@ -16,16 +16,12 @@ from PIL import Image
 
 from conftest import GOLDEN
 from oracle import ref
+from oracle.rules import rel
+from support import make_model, make_vae
 
 pytestmark = pytest.mark.gpu
 
 CSV = os.path.join(GOLDEN, "entities.csv")
-
-
-def rel(a, b):
-    a = torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)).double()
-    b = torch.as_tensor(np.asarray(b.cpu() if isinstance(b, torch.Tensor) else b)).double()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def u8_close(a, b, frac=1e-3, lsb=1):
@@ -35,18 +31,12 @@ def u8_close(a, b, frac=1e-3, lsb=1):
 
 @pytest.fixture(scope="module")
 def model(cuda, unet_sd):
-    from models.unet_cond_geom import UnetCondWithGeomHead
-    m = UnetCondWithGeomHead()
-    m.load_state_dict(unet_sd)
-    return m.to(cuda).eval()
+    return make_model(cuda, unet_sd)
 
 
 @pytest.fixture(scope="module")
 def vae(cuda, vae_sd):
-    from models.vae import VAE
-    v = VAE()
-    v.load_state_dict(vae_sd)
-    return v.to(cuda).eval()
+    return make_vae(cuda, vae_sd)
 
 
 # ---- config 5 / a16: generate_steps.py -----------------------------------------------------------

@@ -20,36 +20,11 @@ import torch
 
 import diff
 from conftest import REPO
-from oracle import ref
+from oracle import rules
+from oracle.rules import cfg_eps, invert_update, rel
 
 
-def rel(a, b):
-    a = torch.as_tensor(a).double().cpu()
-    b = torch.as_tensor(b).double().cpu()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
-# ---- the torch restatements (fp32, one rounding per op in torch's evaluation order) -----------------
-def invert_update_ref(src, eps, c, tables):
-    """Row c - 1 per sample (c: (B,) countdown positions): -> (y, src afterwards)."""
-    _, i_x, i_e, adv = tables
-
-    def row(k):
-        return k[c - 1].view(-1, 1, 1, 1)
-
-    y = row(i_x) * src + row(i_e) * eps
-    return y, torch.where(row(adv) != 0, y, src)
-
-
-def cfg_eps_ref(sd, x, t, y, vals, mask, guidance=3.0, null_label=0):
-    """The step's prediction at the network timestep t: the CFG mix, or one conditional forward for g = 0."""
-    ec, _ = ref.unet_cond_geom_forward(sd, x, t, y, vals, mask)
-    if not guidance > 0:
-        return ec
-    eu, _ = ref.unet_cond_geom_forward(sd, x, t, torch.full_like(y, null_label), vals, mask)
-    return eu + guidance * (ec - eu)
-
-
+# ---- the loops on the rules of oracle/rules.py --------------------------------------------------------
 def invert_ref(z0, tables, eps_of):
     """The whole loop from x == src == z0; eps_of(x, t) -> eps at the network timesteps t (B,)."""
     N = int(tables[0].numel())
@@ -57,20 +32,13 @@ def invert_ref(z0, tables, eps_of):
     with torch.no_grad():
         for c in range(N, 0, -1):
             pos = torch.full((z0.shape[0],), c, dtype=torch.long)
-            x, src = invert_update_ref(src, eps_of(x, tables[0][pos - 1]), pos, tables)
+            x, src = invert_update(src, eps_of(x, tables[0][pos - 1]), pos, tables)
     return x
 
 
 def ddim_back_ref(x, sched, p0, eps_of):
-    """DDIM eta = 0 from position p0 down to 1 (test_gpu_ddim.py's update without its noise term)."""
-    t_map, k_e, k_a, k_s, k_d, _ = sched
-    with torch.no_grad():
-        for p in range(p0, 0, -1):
-            pos = torch.full((x.shape[0],), p, dtype=torch.long)
-            eps = eps_of(x, t_map[pos - 1])
-            x0 = (x - k_e[p - 1] * eps) / k_a[p - 1]
-            x = k_s[p - 1] * x0 + k_d[p - 1] * eps
-    return x
+    """DDIM eta = 0 from position p0 down to 1."""
+    return rules.trajectory(x, "ddim", sched, lambda x, t, pos: eps_of(x, t), p0=p0)
 
 
 def round_trip_inputs():
@@ -255,7 +223,7 @@ def test_round_trip_of_the_restatement(unet_sd):
     sched = d.ddim_tables(20, 0.0)
 
     def eps_of(x, t):
-        return cfg_eps_ref(unet_sd, x, t, y, vals, mask, 3.0)
+        return cfg_eps(unet_sd, x, t, y, vals, mask, 3.0)
 
     errs = {}
     for R in (0, 3):

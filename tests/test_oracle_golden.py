@@ -9,12 +9,7 @@ import torch
 
 from conftest import GOLDEN
 from oracle import ref
-
-
-def rel(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+from oracle.rules import rel
 
 
 def test_weights_sha_match_golden():

@@ -15,14 +15,12 @@ for p in (os.path.join(REPO, "diffusion-model_amd"), REPO, os.path.join(REPO, "t
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from oracle.rules import rel  # noqa: E402
+
 
 def cmp_u8(a, b):
     d = np.abs(a.astype(np.int32) - b.astype(np.int32))
     return int(d.max()), float((d > 0).mean())
-
-
-def rel(a, b):
-    return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
 
 
 def decode_dep():

@@ -8,11 +8,8 @@ for p in (os.path.join(REPO, "diffusion-model_amd"), REPO, os.path.join(REPO, "t
     sys.path.insert(0, p)
 import torch  # noqa: E402
 
+from oracle.rules import rel  # noqa: E402
 from test_gpu_multi import _job, _run2  # noqa: E402
-
-
-def rel(a, b):
-    return float((a - b).norm() / b.norm())
 
 
 if __name__ == "__main__":

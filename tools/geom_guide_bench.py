@@ -35,7 +35,7 @@ def oracle_seeds(n_seeds: int, scale: float) -> None:
     import diff
     from dmx import synth
     from oracle import train_ref
-    from test_gpu_compose import ddim_update_ref
+    from oracle.rules import ddim_update
     from test_gpu_geom import G, final_loss, guide_inputs, mix_ref, oracle_grad
     sd = synth.unet_cond_geom_weights(0)
     d = diff.Diffuser(1000, device="cpu")
@@ -55,7 +55,7 @@ def oracle_seeds(n_seeds: int, scale: float) -> None:
                 with torch.no_grad():
                     eu = train_ref.forward(sd, x, t, torch.zeros_like(y), vals, mask)[0]
                     eps = mix_ref(eu + G * (ec - eu), grad, torch.full((4,), s), sched[1], pos)
-                    x = ddim_update_ref(x, eps, pos, sched, torch.zeros_like(x))
+                    x = ddim_update(x, eps, pos, sched, torch.zeros_like(x))
             losses.append(final_loss(sd, x, y, vals, mask))
         print(f"seed {seed}: masked loss {losses[0]:.5f} -> {losses[1]:.5f} "
               f"({100 * (1 - losses[1] / losses[0]):.1f} % lower)", flush=True)

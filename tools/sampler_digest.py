@@ -36,17 +36,6 @@ SAMPLERS = {"ddpm": {}, "ddim_eta0": dict(sampler="ddim", steps=6, eta=0.0),
             "ddim_eta0.5": dict(sampler="ddim", steps=6, eta=0.5), "dpmpp_2m": dict(sampler="dpmpp_2m", steps=6)}
 
 
-class Foreign(torch.nn.Module):
-    """The network as a duck-typed model: no .native(), so every step takes the foreign branch."""
-
-    def __init__(self, model):
-        super().__init__()
-        self.model = model
-
-    def forward(self, x, t, y, cond_vals=None, cond_mask=None):
-        return self.model(x, t, y, cond_vals=cond_vals, cond_mask=cond_mask)
-
-
 def sha(t):
     return hashlib.sha256(t.detach().to(torch.float32).cpu().contiguous().numpy().tobytes()).hexdigest()
 
@@ -75,6 +64,7 @@ def digests(emit):
     from dmx import synth
     from dmx.distributed import ShardedCondSampler
     from models.unet_cond_geom import UnetCondWithGeomHead
+    from oracle.rules import Foreign  # the network as a duck-typed model: every step takes the foreign branch
     dev = torch.device("cuda", 0)
     model = UnetCondWithGeomHead()
     model.load_state_dict(synth.unet_cond_geom_weights(0))

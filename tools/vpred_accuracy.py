@@ -28,7 +28,7 @@ for p in (os.path.join(REPO, "diffusion-model_amd"), REPO):
         sys.path.insert(0, p)
 
 
-def rel(a, b):
+def rel_rows(a, b):
     """per-row relative L2 of a against b (float64)."""
     a, b = a.double().flatten(1), b.double().flatten(1)
     return (a - b).norm(dim=1) / b.norm(dim=1)
@@ -76,9 +76,9 @@ def study(n, strides):
             # fp32, with the fp32 tables the kernels read
             eps32 = p_o.view(-1, 1) * v + p_x.view(-1, 1) * x
             x0_32 = p_o.view(-1, 1) * x - p_x.view(-1, 1) * v
-            res = {"v_via_eps": rel(via_eps(c32, x, eps32), truth),
-                   "v_direct_x0": rel(update(c32, x, eps32, x0_32), truth),
-                   "eps_mode": rel(via_eps(c32, x, e), via_eps(c64, xd, e.double()))}
+            res = {"v_via_eps": rel_rows(via_eps(c32, x, eps32), truth),
+                   "v_direct_x0": rel_rows(update(c32, x, eps32, x0_32), truth),
+                   "eps_mode": rel_rows(via_eps(c32, x, e), via_eps(c64, xd, e.double()))}
             out[f"{rule} stride {stride if stride else 't (to x0)'}"] = {k: r.tolist() for k, r in res.items()}
     return out
 
