@@ -37,6 +37,10 @@ What changes is where the work happens:
   velocity v = sqrt(ab_t) noise - sqrt(1 - ab_t) x0.  Every sampling entry mixes in output space, converts once
   (eps = sqrt(ab_t) v + sqrt(1 - ab_t) x_t, in the native tail; ``dmx_model_set_prediction`` /
   ``dmx_pred_to_eps``) and runs the eps-form update; ``training_loss`` regresses on v.
+* Zero-terminal-SNR schedules (not in the reference): ``Diffuser(prediction="v", zero_terminal_snr=True)`` rescales
+  the schedule so that ab_T = 0 (Lin et al. 2023) and runs every update in x0-form — the native tail converts to
+  x0 = sqrt(ab_t) x_t - sqrt(1 - ab_t) v and eps and updates without a division
+  (``dmx_model_set_prediction_x0``); ``x0_form=True`` does so on any v-schedule.
 """
 from __future__ import annotations
 
@@ -213,22 +217,62 @@ class _SamplerPlan:
 class Diffuser:
     PREDICTIONS = ("eps", "v")
 
-    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, device="cpu", *, prediction="eps"):
+    def __init__(self, num_timesteps=1000, beta_start=0.0001, beta_end=0.02, device="cpu", *, prediction="eps",
+                 zero_terminal_snr=False, x0_form=None):
         """prediction (not in the reference): what the network's output means.  "eps": the noise, as the
         reference trains it.  "v": the velocity v = sqrt(ab_t) noise - sqrt(1 - ab_t) x0 (Salimans & Ho
         2022).  A checkpoint does not record it, so the caller states it.  With "v" every sampling entry
         mixes in output space (CFG, composition, perturbed branch, CFG rescale — whose standard deviations
         are then v's — and geometry guidance), converts once, eps = sqrt(ab_t) out + sqrt(1 - ab_t) x_t,
-        and runs the eps-form update; training_loss regresses on v."""
+        and runs the eps-form update; training_loss regresses on v.
+
+        zero_terminal_snr (not in the reference): the linear schedule rescaled by Algorithm 1 of Lin et al.
+        2023 ("Common diffusion noise schedules and sample steps are flawed") so that ab_T = 0 exactly: the
+        last step is pure noise, in training as in sampling.  sqrt(ab) is shifted and scaled in fp32 on the
+        CPU so that its first entry keeps its bits and its last becomes 0; alphas = ab_t / ab_{t-1} and
+        betas = 1 - alphas follow from the rescaled ab, which is the table every other table is built from
+        (it is not re-multiplied from the alphas).  Needs num_timesteps >= 2 and prediction="v": an eps
+        prediction at pure noise carries no information.
+
+        x0_form: a v-model's updates written on (x0, eps), x0 = sqrt(ab_t) x_t - sqrt(1 - ab_t) out, with
+        no division (x0_tables; include/dmx.h dmx_model_set_prediction_x0) — the eps-form divides by
+        sqrt(ab_t), which is 0 at t = T of a zero-terminal-SNR schedule and already ill-conditioned just below
+        it.  None: equal to zero_terminal_snr.  True is allowed with any v-schedule; False with
+        zero_terminal_snr is refused.  The x0-form DDPM rule takes alpha_bar_prev = 1 at t = 1 in denoise too:
+        the wrap-around of the reference's unconditional denoise (coef_tables(clamp_prev=False)) is an
+        eps-mode parity quirk and is not carried over.  Only native models take the x0-form."""
         if not isinstance(prediction, str) or prediction not in self.PREDICTIONS:
             raise ValueError(f'prediction must be "eps" or "v" (got {prediction!r})')
+        zero_terminal_snr = bool(zero_terminal_snr)
+        if x0_form is None:
+            x0_form = zero_terminal_snr
+        x0_form = bool(x0_form)
+        if zero_terminal_snr and prediction != "v":
+            raise ValueError('zero_terminal_snr needs prediction="v": eps at pure noise carries no information')
+        if x0_form and prediction != "v":
+            raise ValueError('x0_form needs prediction="v"')
+        if zero_terminal_snr and not x0_form:
+            raise ValueError("zero_terminal_snr needs the x0-form: the eps-form update divides by sqrt(ab_T) = 0")
+        if zero_terminal_snr and int(num_timesteps) < 2:
+            raise ValueError(f"zero_terminal_snr needs num_timesteps >= 2 (got {num_timesteps})")
         self.prediction = prediction
+        self.zero_terminal_snr = zero_terminal_snr
+        self.x0_form = x0_form
         # diff.py:11-16, evaluated on the CPU (torch's CPU cumprod accumulates in double)
         self.num_timesteps = num_timesteps
         self.device = device
         betas = torch.linspace(beta_start, beta_end, num_timesteps)
         alphas = 1 - betas
         alpha_bars = torch.cumprod(alphas, dim=0)
+        if zero_terminal_snr:  # Lin et al. 2023, Algorithm 1, in fp32
+            s = torch.sqrt(alpha_bars)
+            s1, sT = s[0].clone(), s[-1].clone()
+            s = (s - sT) * s1 / (s1 - sT)
+            s[0] = s1  # ((s1 - sT) s1 / (s1 - sT) may round off s1: the first entry keeps its bits)
+            alpha_bars = s * s
+            alpha_bars[0] = torch.cumprod(alphas, dim=0)[0]
+            alphas = torch.cat([alpha_bars[:1], alpha_bars[1:] / alpha_bars[:-1]])
+            betas = 1 - alphas
         self.betas = betas.to(device)
         self.alphas = alphas.to(device)
         self.alpha_bars = alpha_bars.to(device)
@@ -297,7 +341,10 @@ class Diffuser:
         "uniform": ddim_timesteps(S).  "logsnr": uniform in lam[t] = 0.5 ln(ab[t] / (1 - ab[t])) between
         lam[1] and lam[T] — each grid point goes to the nearest timestep (ties to the smaller), then a
         forward pass makes the list strictly ascending from tau_1 and a backward pass fits it under
-        tau_S = T.  S = 1 gives [T] and S = T gives 1..T."""
+        tau_S = T.  S = 1 gives [T] and S = T gives 1..T.
+        On a zero-terminal-SNR schedule lam[T] = -inf: tau_S = T stays, and the other S - 1 points are placed
+        the same way between lam[1] and lam[T-1] (a single one at the middle of that range) and fitted under
+        T - 1."""
         if spacing not in self.DPM_SPACINGS:
             raise ValueError(f'spacing must be "logsnr" or "uniform" (got {spacing!r})')
         T, S = int(self.num_timesteps), int(steps)
@@ -309,9 +356,16 @@ class Diffuser:
             return [T]
         ab = self._host[1].double()
         lam = 0.5 * torch.log(ab / (1 - ab))  # lam[t] at index t - 1, strictly decreasing
-        grid = lam[0] + torch.arange(S, dtype=torch.float64) / (S - 1) * (lam[T - 1] - lam[0])
-        # argmin returns the first minimum: ties go to the smaller t
-        tau = [int(torch.argmin(torch.abs(lam - g))) + 1 for g in grid]
+        if float(ab[T - 1]) == 0.0:  # lam[T] = -inf: the grid spans lam[1] .. lam[T-1], and T is appended
+            lam = lam[:T - 1]
+            frac = (torch.arange(S - 1, dtype=torch.float64) / (S - 2) if S > 2
+                    else torch.full((1,), 0.5, dtype=torch.float64))
+            grid = lam[0] + frac * (lam[T - 2] - lam[0])
+            tau = [int(torch.argmin(torch.abs(lam - g))) + 1 for g in grid] + [T]
+        else:
+            grid = lam[0] + torch.arange(S, dtype=torch.float64) / (S - 1) * (lam[T - 1] - lam[0])
+            # argmin returns the first minimum: ties go to the smaller t
+            tau = [int(torch.argmin(torch.abs(lam - g))) + 1 for g in grid]
         for i in range(1, S):
             tau[i] = max(tau[i], tau[i - 1] + 1)
         tau[S - 1] = T
@@ -330,7 +384,9 @@ class Diffuser:
         once; cached per (steps, spacing, device, start).  The result is an engine.DpmSchedule (a tuple).
         start = p0 in [1, S): the schedule of a loop that enters at position p0 (img2img) — row p0 is
         first-order too, so no step reads a history that was never written; the other rows are those
-        of start=None.  start = S is start=None."""
+        of start=None.  start = S is start=None.
+        On a zero-terminal-SNR schedule the terminal row has k_a = 0, which is correct and which the x0-form
+        does not read; the row after it (u = T, lam[u] = -inf, r = inf) is first-order: k_c = m, k_p = +0.0."""
         if start is not None:
             start = int(start)
             if not 1 <= start <= int(steps):
@@ -357,6 +413,9 @@ class Diffuser:
                 r = (lt - lu) / (ls - lt)
                 k_c[mid] = m[mid] * (1 + 1 / (2 * r))
                 k_p[mid] = -m[mid] / (2 * r)
+                first = torch.isinf(lu)  # the step before started at pure noise: r = inf, first-order
+                k_c[mid] = torch.where(first, m[mid], k_c[mid])
+                k_p[mid] = torch.where(first, torch.zeros_like(lu), k_p[mid])  # (+0.0, not the -0.0 of -m / inf)
             if start is not None:  # the loop enters here: nothing has written the history yet
                 k_c[start - 1], k_p[start - 1] = m[start - 1], 0.0
             tabs = (k_e, k_a, k_x, k_c, k_p)
@@ -557,19 +616,25 @@ class Diffuser:
         """sqrt(1 - alpha_bar[t]) at index t - 1, fp32 from the fp32 alpha_bars: the sig table of a
         geometry-guided DDPM step (the strided rules use their schedule's k_e, the same quantity per position).
         A v-model's mix happens in output space, where eps += s sig dL/dx reads v += s (sig / sqrt(ab)) dL/dx:
-        the table is then sqrt(1 - ab) / sqrt(ab), one fp32 division of the two fp32 roots."""
+        the table is then sqrt(1 - ab) / sqrt(ab), one fp32 division of the two fp32 roots.  A row with
+        ab_t = 0 (the last of a zero-terminal-SNR schedule) gets sig = 0: that one step is not steered — at pure
+        noise the latent says nothing about x0, and an eps shift cannot move x0."""
         cache = self.__dict__.setdefault("_geom_sig", {})
         key = (str(device), self.prediction)
         if key not in cache:
             sig = torch.sqrt(1 - self._host[1])
             if self.prediction == "v":
-                sig = sig / torch.sqrt(self._host[1])
+                root = torch.sqrt(self._host[1])
+                sig = torch.where(root == 0, torch.zeros_like(sig), sig / root)
             cache[key] = sig.contiguous().to(device)
         return cache[key]
 
     def _sched_sig(self, sched):
-        """geom_sig per position of a strided schedule (t_map, k_e, k_a, ..): k_e, over k_a for a v-model."""
-        return sched[1] if self.prediction != "v" else (sched[1] / sched[2]).contiguous()
+        """geom_sig per position of a strided schedule (t_map, k_e, k_a, ..): k_e, over k_a for a v-model
+        (0 where k_a = 0, as in geom_sig)."""
+        if self.prediction != "v":
+            return sched[1]
+        return torch.where(sched[2] == 0, torch.zeros_like(sched[1]), sched[1] / sched[2]).contiguous()
 
     # ---- what the network predicts -------------------------------------------------------------
     def pred_tables(self, device):
@@ -582,6 +647,19 @@ class Diffuser:
         key = ("pred", str(device))
         if key not in self._tables:
             self._tables[key] = tuple(k.to(device) for k in host)
+        return self._tables[key]
+
+    def x0_tables(self, device):
+        """(d_s, d_d) per t-1: the DDPM posterior mean written on (x0, eps), mu = d_s x0 + d_d eps, with
+        d_s = sqrt(ab_prev), d_d = (1 - ab_prev) sqrt(a_t) / sqrt(1 - ab_t) and ab_prev = 1 at t = 1 (row 0 is
+        exactly (1, 0)); the posterior sd stays coef_tables' table.  Finite at ab_T = 0, where d_d = 0.
+        Computed in float64 from the fp32 alphas and alpha_bars and rounded to fp32 once; cached per device."""
+        key = ("x0", str(device))
+        if key not in self._tables:
+            a, ab = (v.double() for v in self._host)
+            abp = torch.cat([torch.ones(1, dtype=torch.float64), ab[:-1]])
+            tabs = (torch.sqrt(abp), (1 - abp) * torch.sqrt(a) / torch.sqrt(1 - ab))
+            self._tables[key] = tuple(v.float().contiguous().to(device) for v in tabs)
         return self._tables[key]
 
     def _native(self, model):
@@ -598,7 +676,11 @@ class Diffuser:
             if setter is None:
                 raise TypeError(f'prediction="v" needs a native model that can be told so ({type(nm).__name__} has '
                                 f"no set_prediction)")
-            setter("v", *self.pred_tables(nm.device))
+            if self.x0_form:  # the x0-form instances: the same conversion tables plus the posterior's
+                d_s, d_d = self.x0_tables(nm.device)
+                setter("v", *self.pred_tables(nm.device), d_s=d_s, d_d=d_d)
+            else:
+                setter("v", *self.pred_tables(nm.device))
         elif setter is not None:
             setter("eps")
 
@@ -608,6 +690,9 @@ class Diffuser:
         network timesteps t on the latent x the model saw (engine.pred_to_eps) -> (eps, None, 0.0)."""
         if self.prediction != "v":
             return eu, ec, g
+        if self.x0_form:
+            raise TypeError("x0_form needs a native dmx model on the GPU: the stand-alone updates of a foreign "
+                            "model are eps-form")
         out = eu if ec is None else eu + g * (ec - eu)
         return _engine.pred_to_eps(out, x, t, *self.pred_tables(x.device)), None, 0.0
 
@@ -958,7 +1043,8 @@ class Diffuser:
         F.mse_loss).  "min_snr": min(SNR_t, gamma) / SNR_t with SNR_t = ab_t / (1 - ab_t), the
         eps-prediction form of min-SNR-gamma (Hang et al. 2023, "Efficient diffusion training via min-SNR
         weighting strategy"), evaluated in float64 and rounded once.  A v-model (prediction="v") takes the
-        paper's v-prediction form min(SNR_t, gamma) / (SNR_t + 1), formed the same way."""
+        paper's v-prediction form min(SNR_t, gamma) / (SNR_t + 1), formed the same way; it is finite everywhere
+        and 0 at t = T of a zero-terminal-SNR schedule (SNR_T = 0): the pure-noise step then carries no weight."""
         try:
             gamma = float(snr_gamma)
         except (TypeError, ValueError):
@@ -1113,7 +1199,8 @@ class Diffuser:
         """Unconditional DDPM step (diff.py:32-56)."""
         T = self.num_timesteps
         assert (t >= 1).all() and (t <= T).all()
-        tables = self.coef_tables(x.device, clamp_prev=False)
+        # (the x0-form takes alpha_bar_prev = 1 at t = 1 here too: the wrap-around is an eps-mode parity quirk)
+        tables = self.coef_tables(x.device, clamp_prev=self.x0_form)
         model.eval()
         if _native_kind(model) and x.is_cuda and getattr(model, "_dmx_kind", 0) == 3:
             model.train()

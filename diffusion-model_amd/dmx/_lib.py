@@ -195,6 +195,8 @@ SIGNATURES = [
     ("dmx_model_set_prediction", _I, [_P, _I, _P, _P, _I, _P]),
     ("dmx_model_get_prediction", _I, [_P]),
     ("dmx_pred_to_eps", _I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    ("dmx_model_set_prediction_x0", _I, [_P, _P, _P, _P, _P, _I, _P]),
+    ("dmx_pred_split", _I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     ("dmx_model_range_check", _I, [_P, _I, ctypes.POINTER(_I), _P]),
     ("dmx_unet_forward", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     ("dmx_step", _I, [_P, ctypes.POINTER(StepArgs), _P]),

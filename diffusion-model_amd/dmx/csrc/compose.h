@@ -27,7 +27,7 @@ DMX_DEV float pick4(const float (&e)[4], int c) { return c == 0 ? e[0] : c == 1 
 // The lane's four products are accumulated with explicit FMAs from 0 in j order — what the plain
 // tail's `s += w * a` compiles to — so that no vectorisation of this longer body can split a
 // multiply from its add (tests/test_gpu_compose.py pins K = 1 against the plain step bit for bit).
-template <bool DDIM, bool DPM = false, bool VPRED = false>  // (VPRED: a v-model's instances, as in kernels.h)
+template <bool DDIM, bool DPM = false, int PRED = PRED_EPS>  // (PRED: a v-model's instances, as in kernels.h)
 static __global__ __launch_bounds__(256) void compose_tail4_kernel(const StepTailParams p, const ComposeParams q) {
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
@@ -68,8 +68,16 @@ static __global__ __launch_bounds__(256) void compose_tail4_kernel(const StepTai
     if (k <= K) s = rnd(s + rnd(q.weight[(size_t)(k - 1) * p.B + n] * rnd(e[k] - e[0])));
   float eps = rnd(e[0] + s);
   const size_t idx = ((size_t)n * 4 + c) * p.HW + pix;
-  if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t);  // a v-model
-  flag_nonfinite(p.range_flag, eps);
+  X0Eps xe{0.f, 0.f};
+  int r = 0;
+  if (PRED == PRED_X0) {  // a v-model in x0-form: the flag is raised on what the rule reads
+    xe = tail_x0(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t, r);
+    flag_nonfinite(p.range_flag, xe.x0);
+    if (!DPM) flag_nonfinite(p.range_flag, xe.eps);
+  } else {
+    if (PRED == PRED_V) eps = tail_eps(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t);  // a v-model
+    flag_nonfinite(p.range_flag, eps);
+  }
   float nz = 0.f, kn = 0.f;
   if (DDIM) kn = p.k_n[t - 1];
   const bool noisy = DPM ? false : DDIM ? kn != 0.f : t != 1;  // (see step_tail_kernel)
@@ -82,7 +90,11 @@ static __global__ __launch_bounds__(256) void compose_tail4_kernel(const StepTai
       nz = c == 0 ? r[0] : c == 1 ? r[1] : c == 2 ? r[2] : r[3];
     }
   }
-  if (DPM)
+  if (PRED == PRED_X0)
+    p.x_out[idx] = DPM    ? dpm_x0_elem(p.x[idx], xe.x0, p.k_x[t - 1], p.k_c[t - 1], p.k_p[t - 1], p.hist + idx)
+                   : DDIM ? ddim_x0_elem(xe.x0, xe.eps, p.k_s[t - 1], p.k_d[t - 1], kn, nz)
+                          : ddpm_x0_elem(xe.x0, xe.eps, p.d_s[r], p.d_d[r], p.sd[t - 1], nz);
+  else if (DPM)
     p.x_out[idx] = dpm_elem(p.x[idx], eps, p.k_e[t - 1], p.k_a[t - 1], p.k_x[t - 1], p.k_c[t - 1], p.k_p[t - 1],
                             p.hist + idx);
   else if (DDIM)

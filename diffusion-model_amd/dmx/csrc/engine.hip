@@ -334,7 +334,8 @@ struct dmx_model {
   int64_t weights_gen = 0;  // bumped by dmx_model_finalize / dmx_model_refresh
   // What the network's output means (include/dmx.h dmx_model_set_prediction): DMX_PRED_EPS, or
   // DMX_PRED_V with device copies of the caller's tables p_o | p_x in one allocation of 2 pred_T floats
-  // (captured graphs hold the pointer) and their values on the host, to tell a repeated call from a change.
+  // (captured graphs hold the pointer) and their values on the host, to tell a repeated call from a change;
+  // or DMX_PRED_V_X0 (dmx_model_set_prediction_x0) with p_o | p_x | d_s | d_d in 4 pred_T floats.
   int pred = DMX_PRED_EPS;
   int pred_T = 0;
   float* pred_tab = nullptr;
@@ -2462,13 +2463,43 @@ int dmx_model_set_precision(dmx_model* m, int prec) {
 
 int dmx_model_get_precision(const dmx_model* m) { return m ? m->prec : -1; }
 
+// The converting kinds' tables (DMX_PRED_V: p_o | p_x; DMX_PRED_V_X0: p_o | p_x | d_s | d_d, `rows` device
+// tables of T floats each) copied into the model's one allocation.  A repeated identical call is
+// recognised by the values; a change drops every captured graph and the cached deep feature.
+static void store_prediction(dmx_model* m, int kind, const float* const* tabs, int rows, int T, hipStream_t st) {
+  std::vector<float> host((size_t)rows * T);
+  for (int r = 0; r < rows; ++r)
+    HIPCHK(hipMemcpyAsync(host.data() + (size_t)r * T, tabs[r], (size_t)T * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));  // (also: no launch of st still reads the tables replaced below)
+  const bool same_tab = m->pred_tab != nullptr && m->pred_T == T && m->pred_host.size() == host.size() &&
+                        std::memcmp(host.data(), m->pred_host.data(), host.size() * sizeof(float)) == 0;
+  if (same_tab && m->pred == kind) return;
+  drop_graph(m);
+  m->dtag.valid = false;
+  if (!same_tab) {
+    m->pred = DMX_PRED_EPS;  // until the new tables stand
+    if (m->pred_tab != nullptr && m->pred_host.size() != host.size()) {
+      HIPCHK(hipDeviceSynchronize());  // (steps of other streams may still read the old allocation)
+      HIPCHK(hipFree(m->pred_tab));
+      m->pred_tab = nullptr;
+      m->pred_T = 0;
+      m->pred_host.clear();
+    }
+    if (m->pred_tab == nullptr) HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->pred_tab), host.size() * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(m->pred_tab, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // (host is this call's local)
+    m->pred_T = T;
+    m->pred_host.swap(host);
+  }
+  m->pred = kind;
+}
+
 int dmx_model_set_prediction(dmx_model* m, int kind, const float* p_o, const float* p_x, int T, void* stream) {
   return guarded([&] {
     REQUIRE(m != nullptr, "null model");
     const char* bad = set_prediction_error(kind, p_o, p_x, T);
     REQUIRE(bad == nullptr, bad);
-    hipStream_t st = (hipStream_t)stream;
-    if (kind == DMX_PRED_EPS) {  // (the tables stay allocated: a later V call may find them unchanged)
+    if (kind == DMX_PRED_EPS) {  // (the tables stay allocated: a later call may find them unchanged)
       if (m->pred != DMX_PRED_EPS) {
         drop_graph(m);
         m->dtag.valid = false;
@@ -2476,30 +2507,19 @@ int dmx_model_set_prediction(dmx_model* m, int kind, const float* p_o, const flo
       m->pred = DMX_PRED_EPS;
       return;
     }
-    std::vector<float> host((size_t)2 * T);
-    HIPCHK(hipMemcpyAsync(host.data(), p_o, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(host.data() + T, p_x, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));  // (also: no launch of st still reads the tables replaced below)
-    const bool same_tab = m->pred_tab != nullptr && m->pred_T == T &&
-                          std::memcmp(host.data(), m->pred_host.data(), host.size() * sizeof(float)) == 0;
-    if (same_tab && m->pred == DMX_PRED_V) return;
-    drop_graph(m);
-    m->dtag.valid = false;
-    if (!same_tab) {
-      m->pred = DMX_PRED_EPS;  // until the new tables stand
-      if (m->pred_tab != nullptr && m->pred_T != T) {
-        HIPCHK(hipDeviceSynchronize());  // (steps of other streams may still read the old allocation)
-        HIPCHK(hipFree(m->pred_tab));
-        m->pred_tab = nullptr;
-        m->pred_T = 0;
-      }
-      if (m->pred_tab == nullptr) HIPCHK(hipMalloc(reinterpret_cast<void**>(&m->pred_tab), host.size() * sizeof(float)));
-      HIPCHK(hipMemcpyAsync(m->pred_tab, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));  // (host is this call's local)
-      m->pred_T = T;
-      m->pred_host.swap(host);
-    }
-    m->pred = DMX_PRED_V;
+    const float* tabs[2] = {p_o, p_x};
+    store_prediction(m, DMX_PRED_V, tabs, 2, T, (hipStream_t)stream);
+  });
+}
+
+int dmx_model_set_prediction_x0(dmx_model* m, const float* p_o, const float* p_x, const float* d_s, const float* d_d,
+                                int T, void* stream) {
+  return guarded([&] {
+    REQUIRE(m != nullptr, "null model");
+    const char* bad = set_prediction_x0_error(p_o, p_x, d_s, d_d, T);
+    REQUIRE(bad == nullptr, bad);
+    const float* tabs[4] = {p_o, p_x, d_s, d_d};
+    store_prediction(m, DMX_PRED_V_X0, tabs, 4, T, (hipStream_t)stream);
   });
 }
 
@@ -2511,6 +2531,16 @@ int dmx_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_st
     const char* bad = pred_to_eps_error(out, x, t, t_stride, p_o, p_x, T, n, c, h, w, eps_out);
     REQUIRE(bad == nullptr, bad);
     launch_pred_to_eps(out, x, t, t_stride, p_o, p_x, T, n, (int64_t)c * h * w, eps_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int dmx_pred_split(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                   const float* p_x, int T, int n, int c, int h, int w, float* x0_out, float* eps_out, void* stream) {
+  return guarded([&] {
+    const char* bad = pred_split_error(out, x, t, t_stride, p_o, p_x, T, n, c, h, w, x0_out, eps_out);
+    REQUIRE(bad == nullptr, bad);
+    launch_pred_split(out, x, t, t_stride, p_o, p_x, T, n, (int64_t)c * h * w, x0_out, eps_out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
   });
 }

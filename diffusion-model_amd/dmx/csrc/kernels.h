@@ -715,10 +715,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* qkv, float*
 // (Philox noise, StepTailParams and the ddpm / ddim / dpm / invert element updates: tail_math.h, shared
 // with the composed tail of compose.h.)  INV: the DDIM-inversion instance — no noise; p.x is the
 // position's source latent (the engine passes the schedule's src), p.src receives y on adv rows.
-// VPRED: the instances of a v-model (p.p_o given) — the mixed output is converted to eps before the
-// update (tail_math.h tail_eps); the eps-model instances are the code they were before it existed.
-template <bool DDIM, bool DPM = false, bool INV = false, bool VPRED = false>
+// PRED (tail_math.h): PRED_V, the instances of a v-model (p.p_o given) — the mixed output is converted to
+// eps before the update (tail_eps); PRED_X0, its x0-form instances (p.d_s given too) — converted to
+// (x0, eps) and updated without a division (tail_x0; inversion has none and runs PRED_V).  The eps-model
+// instances are the code they were before either existed.
+template <bool DDIM, bool DPM = false, bool INV = false, int PRED = PRED_EPS>
 static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailParams p) {
+  static_assert(!(INV && PRED == PRED_X0), "inversion has no x0-form");
   const int pix = blockIdx.x * 256 + threadIdx.x;
   const int n = blockIdx.y;
   if (pix >= p.HW) return;
@@ -772,16 +775,29 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
   if (INV) {  // (ks / kd carry i_x / i_e)
     ks = p.i_x[t - 1], kd = p.i_e[t - 1], adv = p.adv[t - 1];
   } else if (DPM) {  // (ks / kd / kn carry k_x / k_c / k_p)
-    ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_x[t - 1], kd = p.k_c[t - 1], kn = p.k_p[t - 1];
+    if (PRED != PRED_X0) ke = p.k_e[t - 1], ka = p.k_a[t - 1];
+    ks = p.k_x[t - 1], kd = p.k_c[t - 1], kn = p.k_p[t - 1];
   } else if (DDIM) {
-    ke = p.k_e[t - 1], ka = p.k_a[t - 1], ks = p.k_s[t - 1], kd = p.k_d[t - 1];
+    if (PRED != PRED_X0) ke = p.k_e[t - 1], ka = p.k_a[t - 1];
+    ks = p.k_s[t - 1], kd = p.k_d[t - 1];
   } else {
-    c1 = p.c1[t - 1], c2 = p.c2[t - 1], sd = p.sd[t - 1];
+    if (PRED != PRED_X0) c1 = p.c1[t - 1], c2 = p.c2[t - 1];
+    sd = p.sd[t - 1];
   }
   for (int c = 0; c < Co; ++c) {
     float eps = p.cfg ? eu[c] + rnd(p.guidance * rnd(ec[c] - eu[c])) : eu[c];
     const size_t idx = ((size_t)n * Co + c) * p.HW + pix;
-    if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
+    if (PRED == PRED_X0) {  // a v-model in x0-form: the flag is raised on what the rule reads
+      int r;
+      const X0Eps q = tail_x0(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t, r);
+      flag_nonfinite(p.range_flag, q.x0);
+      if (!DPM) flag_nonfinite(p.range_flag, q.eps);
+      p.x_out[idx] = DPM    ? dpm_x0_elem(p.x[idx], q.x0, ks, kd, kn, p.hist + idx)
+                     : DDIM ? ddim_x0_elem(q.x0, q.eps, ks, kd, kn, nz[c])
+                            : ddpm_x0_elem(q.x0, q.eps, p.d_s[r], p.d_d[r], sd, nz[c]);
+      continue;
+    }
+    if (PRED == PRED_V) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
     flag_nonfinite(p.range_flag, eps);
     if (INV) {
       const float y = invert_elem(p.x[idx], eps, ks, kd);
@@ -800,8 +816,9 @@ static __global__ __launch_bounds__(256) void step_tail_kernel(const StepTailPar
 // coalesced, instead of 64 rows at a 256-byte lane stride); the 1x1-conv dot products are
 // reduced over the 16 lanes with DPP (fixed order), then lanes 0..3 of the group finish
 // channel c = lane (CFG mix, posterior mean, Philox noise, store).
-template <bool DDIM, bool DPM = false, bool INV = false, bool VPRED = false>
+template <bool DDIM, bool DPM = false, bool INV = false, int PRED = PRED_EPS>
 static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailParams p) {
+  static_assert(!(INV && PRED == PRED_X0), "inversion has no x0-form");
   const int sub = threadIdx.x & 15, pix = blockIdx.x * 16 + (threadIdx.x >> 4), n = blockIdx.y;
   const bool valid = pix < p.HW;
   const int pc = valid ? pix : 0;
@@ -841,7 +858,17 @@ static __global__ __launch_bounds__(256) void step_tail4_kernel(const StepTailPa
     }
   }
   float eps = p.cfg ? u + rnd(p.guidance * rnd(v - u)) : u;
-  if (VPRED) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
+  if (PRED == PRED_X0) {  // a v-model in x0-form (see step_tail_kernel)
+    int r;
+    const X0Eps q = tail_x0(p, eps, idx, (DDIM || DPM) ? p.t_map[t - 1] : t, r);
+    flag_nonfinite(p.range_flag, q.x0);
+    if (!DPM) flag_nonfinite(p.range_flag, q.eps);
+    p.x_out[idx] = DPM    ? dpm_x0_elem(p.x[idx], q.x0, p.k_x[t - 1], p.k_c[t - 1], p.k_p[t - 1], p.hist + idx)
+                   : DDIM ? ddim_x0_elem(q.x0, q.eps, p.k_s[t - 1], p.k_d[t - 1], kn, nz)
+                          : ddpm_x0_elem(q.x0, q.eps, p.d_s[r], p.d_d[r], p.sd[t - 1], nz);
+    return;
+  }
+  if (PRED == PRED_V) eps = tail_eps(p, eps, idx, (DDIM || DPM || INV) ? p.t_map[t - 1] : t);  // a v-model
   flag_nonfinite(p.range_flag, eps);
   if (INV) {
     const float y = invert_elem(p.x[idx], eps, p.i_x[t - 1], p.i_e[t - 1]);

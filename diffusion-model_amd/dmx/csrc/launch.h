@@ -122,5 +122,8 @@ void launch_objective_seed(const dmx_objective_args& a, const float* up, float* 
 // eps_out = p_o[t - 1] out + p_x[t - 1] x over [n][chw]; n * chw < 2^39; eps_out may alias out
 void launch_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
                         const float* p_x, int T, int n, int64_t chw, float* eps_out, hipStream_t st);
+// x0_out = p_o[t - 1] x - p_x[t - 1] out and eps_out as above, in one pass; eps_out may alias out
+void launch_pred_split(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                       const float* p_x, int T, int n, int64_t chw, float* x0_out, float* eps_out, hipStream_t st);
 
 }  // namespace dmx

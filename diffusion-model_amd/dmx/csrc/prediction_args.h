@@ -1,5 +1,6 @@
 // dmx — the argument checks of the v-prediction entries (include/dmx.h dmx_model_set_prediction,
-// dmx_pred_to_eps, and the timestep range of a v-model's step or loop).  Host C++ only (no HIP), so
+// dmx_model_set_prediction_x0, dmx_pred_to_eps, dmx_pred_split, and the timestep range of a v-model's
+// step or loop).  Host C++ only (no HIP), so
 // that tools/prediction_args_check.cpp can run them under the host sanitizers; engine.hip turns a
 // message into DMX_E_ARG.  Nothing here dereferences a tensor pointer.
 #pragma once
@@ -31,6 +32,28 @@ inline const char* pred_to_eps_error(const float* out, const float* x, const int
   if (n < 1 || c < 1 || h < 1 || w < 1) return "bad shape";
   if ((double)n * (double)c * (double)h * (double)w >= 549755813888.0) return "too many elements";
   if (eps_out == x) return "eps_out must not alias x";
+  return nullptr;
+}
+
+// dmx_model_set_prediction_x0: all four tables and T >= 1 (the kind is the entry's own)
+inline const char* set_prediction_x0_error(const float* p_o, const float* p_x, const float* d_s, const float* d_d,
+                                           int T) {
+  if (p_o == nullptr || p_x == nullptr) return "x0-form needs the p_o and p_x tables";
+  if (d_s == nullptr || d_d == nullptr) return "x0-form needs the d_s and d_d tables";
+  if (T < 1) return "T must be >= 1";
+  return nullptr;
+}
+
+// dmx_pred_split: pred_to_eps_error's rules for both outputs; eps_out may alias out, x0_out may not (the
+// thread that wrote it would have lost the operand of its eps), neither aliases x nor the other
+inline const char* pred_split_error(const float* out, const float* x, const int64_t* t, int t_stride,
+                                    const float* p_o, const float* p_x, int T, int n, int c, int h, int w,
+                                    const float* x0_out, const float* eps_out) {
+  if (x0_out == nullptr) return "null tensor";
+  if (const char* bad = pred_to_eps_error(out, x, t, t_stride, p_o, p_x, T, n, c, h, w, eps_out)) return bad;
+  if (x0_out == x) return "x0_out must not alias x";
+  if (x0_out == out) return "x0_out must not alias out";
+  if (x0_out == eps_out) return "x0_out must not alias eps_out";
   return nullptr;
 }
 

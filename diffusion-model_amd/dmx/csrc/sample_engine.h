@@ -67,24 +67,35 @@ static void set_sched(StepTailParams& p, const dmx_invert_sched& iv) {
 
 // The tail's launch: the instance of the update rule; head4 = the network head path with Co = 4
 // (16 pixels per block), else one pixel per thread; comp: the composed head4 tail (launch.h).
-// p.p_o given (a v-model): the VPRED instances of the same kernels.
+// p.p_o given (a v-model): the PRED_V instances of the same kernels; p.d_s too (its x0-form): the PRED_X0
+// instances, except in inversion, which has no x0 and no division and runs PRED_V.
 static void launch_step_tail(const StepTailParams& p, Rule rule, bool head4, dim3 grid, hipStream_t st,
                              const ComposeParams* comp = nullptr) {
   if (comp != nullptr) {
     if (!head4) throw Error(DMX_E_INTERNAL, "the composed tail is the Co = 4 head tail");
     if (rule == Rule::INVERT) throw Error(DMX_E_INTERNAL, "there is no composed inversion tail");
     launch_compose_tail4(p, *comp, rule == Rule::DDIM, rule == Rule::DPM, grid, st);
+  } else if (p.p_o != nullptr && p.d_s != nullptr && rule != Rule::INVERT) {  // a v-model in x0-form
+    if (!head4) {
+      if (rule == Rule::DPM) step_tail_kernel<false, true, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail_kernel<true, false, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+      else step_tail_kernel<false, false, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+    } else {
+      if (rule == Rule::DPM) step_tail4_kernel<false, true, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail4_kernel<true, false, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+      else step_tail4_kernel<false, false, false, PRED_X0><<<grid, 256, 0, st>>>(p);
+    }
   } else if (p.p_o != nullptr) {  // a v-model: the converting instances
     if (!head4) {
-      if (rule == Rule::INVERT) step_tail_kernel<false, false, true, true><<<grid, 256, 0, st>>>(p);
-      else if (rule == Rule::DPM) step_tail_kernel<false, true, false, true><<<grid, 256, 0, st>>>(p);
-      else if (rule == Rule::DDIM) step_tail_kernel<true, false, false, true><<<grid, 256, 0, st>>>(p);
-      else step_tail_kernel<false, false, false, true><<<grid, 256, 0, st>>>(p);
+      if (rule == Rule::INVERT) step_tail_kernel<false, false, true, PRED_V><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DPM) step_tail_kernel<false, true, false, PRED_V><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail_kernel<true, false, false, PRED_V><<<grid, 256, 0, st>>>(p);
+      else step_tail_kernel<false, false, false, PRED_V><<<grid, 256, 0, st>>>(p);
     } else {
-      if (rule == Rule::INVERT) step_tail4_kernel<false, false, true, true><<<grid, 256, 0, st>>>(p);
-      else if (rule == Rule::DPM) step_tail4_kernel<false, true, false, true><<<grid, 256, 0, st>>>(p);
-      else if (rule == Rule::DDIM) step_tail4_kernel<true, false, false, true><<<grid, 256, 0, st>>>(p);
-      else step_tail4_kernel<false, false, false, true><<<grid, 256, 0, st>>>(p);
+      if (rule == Rule::INVERT) step_tail4_kernel<false, false, true, PRED_V><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DPM) step_tail4_kernel<false, true, false, PRED_V><<<grid, 256, 0, st>>>(p);
+      else if (rule == Rule::DDIM) step_tail4_kernel<true, false, false, PRED_V><<<grid, 256, 0, st>>>(p);
+      else step_tail4_kernel<false, false, false, PRED_V><<<grid, 256, 0, st>>>(p);
     }
   } else if (!head4) {
     if (rule == Rule::INVERT) step_tail_kernel<false, false, true><<<grid, 256, 0, st>>>(p);
@@ -209,11 +220,15 @@ static void step_body(Run& R, const dmx_step_args& a, const StepMode& mode, Grap
   p.seed = a.seed;
   p.sample_offset = a.sample_offset;
   p.range_flag = m->range_flag;
-  if (m->pred == DMX_PRED_V) {  // every tail below converts its mixed output (tail_math.h tail_eps)
+  if (m->pred != DMX_PRED_EPS) {  // every tail below converts its mixed output (tail_math.h tail_eps / tail_x0)
     p.p_o = m->pred_tab;
     p.p_x = m->pred_tab + m->pred_T;
     p.pred_T = m->pred_T;
     p.x_net = a.x_in;  // the buffer the trunk read: in an inversion's refinement rows y, not the source latent
+    if (m->pred == DMX_PRED_V_X0) {
+      p.d_s = m->pred_tab + 2 * (size_t)m->pred_T;
+      p.d_d = m->pred_tab + 3 * (size_t)m->pred_T;
+    }
   }
   if (rule == Rule::INVERT) {
     set_sched(p, *mode.invert);
@@ -414,7 +429,7 @@ static void validate(dmx_model* m, const dmx_step_args* a, const StepMode& mode,
 // tables; a strided rule's timesteps are its t_map, device memory, read back here — one small copy
 // and a wait for st per call, in v-mode only.  Nothing has been launched when this throws.
 static void check_prediction(const dmx_model* m, const dmx_step_args& a, const StepMode& mode, hipStream_t st) {
-  if (m->pred != DMX_PRED_V) return;
+  if (m->pred == DMX_PRED_EPS) return;
   int64_t t_max = a.T;
   if (mode.rule() != Rule::DDPM) {
     std::vector<int64_t> tm((size_t)mode.positions(a));

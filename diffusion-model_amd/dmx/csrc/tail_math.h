@@ -120,23 +120,66 @@ struct StepTailParams {
   const float* i_x; const float* i_e; const int* adv;
   float* src;
   // v-prediction (include/dmx.h dmx_model_set_prediction): p_o null => the mixed output is eps and the
-  // launchers pick the plain instances; else their VPRED instances, which convert it:
+  // launchers pick the plain instances; else their PRED_V instances, which convert it:
   // p_o / p_x [pred_T], index = the row's network timestep - 1, and x_net (x's shape) is the latent the
   // network was evaluated at — p.x itself except in the inversion instance, whose p.x is the source latent
   const float* p_o; const float* p_x; const float* x_net;
   int pred_T;
+  // x0-form of a v-model (dmx_model_set_prediction_x0): d_s null => the PRED_V instances above; else the
+  // PRED_X0 instances, which convert the mixed output to (x0, eps) and update without a division.  d_s / d_d
+  // [pred_T], index = the network timestep - 1: the DDPM posterior mean on (x0, eps); the strided rules
+  // read the k_s / k_d / k_n and k_x / k_c / k_p their schedules already carry, never k_e / k_a.
+  const float* d_s; const float* d_d;
 };
+
+// What a tail instance takes the mixed network output for: the noise, a v-model's velocity converted to
+// eps ahead of the eps-form update, or a v-model's velocity converted to (x0, eps) ahead of the x0-form one.
+enum { PRED_EPS = 0, PRED_V = 1, PRED_X0 = 2 };
 
 // v-prediction -> eps (Salimans & Ho 2022, v = sqrt(ab) noise - sqrt(1-ab) x0, so with x = sqrt(ab) x0 +
 // sqrt(1-ab) noise: eps = sqrt(ab) v + sqrt(1-ab) x): two products and a sum, one rounding each.
 DMX_DEV float pred_to_eps_elem(float out, float x_net, float po, float px) { return rnd(po * out) + rnd(px * x_net); }
 
-// The tails' use of it, in their VPRED instances (launched where p.p_o is given): the mixed network
+// The tails' use of it, in their PRED_V instances (launched where p.p_o is given): the mixed network
 // output of element idx, converted once.  tnet: the row's network timestep — t itself in the DDPM rule,
 // t_map[pos - 1] in the strided ones — clamped to the tables like every table read.
 DMX_DEV float tail_eps(const StepTailParams& p, float out, size_t idx, int64_t tnet) {
   const int r = (int)(tnet < 1 ? 1 : (tnet > p.pred_T ? p.pred_T : tnet)) - 1;
   return pred_to_eps_elem(out, p.x_net[idx], p.p_o[r], p.p_x[r]);
+}
+
+// v-prediction -> x0 (the same two identities solved for x0: x0 = sqrt(ab) x - sqrt(1-ab) v): two products
+// and a difference, one rounding each.  No division: finite where ab_t = 0 (a zero-terminal-SNR schedule's
+// last step, where x0 = -v and eps = x).
+DMX_DEV float pred_to_x0_elem(float out, float x_net, float po, float px) { return rnd(po * x_net) - rnd(px * out); }
+
+struct X0Eps {
+  float x0, eps;
+};
+// The PRED_X0 instances' conversion of element idx (tnet as in tail_eps); r_out: the clamped table row.
+DMX_DEV X0Eps tail_x0(const StepTailParams& p, float out, size_t idx, int64_t tnet, int& r_out) {
+  const int r = (int)(tnet < 1 ? 1 : (tnet > p.pred_T ? p.pred_T : tnet)) - 1;
+  const float xn = p.x_net[idx], po = p.p_o[r], px = p.p_x[r];
+  r_out = r;
+  return X0Eps{pred_to_x0_elem(out, xn, po, px), pred_to_eps_elem(out, xn, po, px)};
+}
+
+// The x0-form updates: the rules below with x0 taken from the conversion, not from (x - k_e eps) / k_a.
+//   DDPM  mu = d_s*x0 + d_d*eps, d_s = sqrt(ab_prev), d_d = (1 - ab_prev) sqrt(a) / sqrt(1 - ab)  (ab_prev = 1 at t = 1)
+//   DDIM  x' = k_s*x0 + k_d*eps + k_n*nz
+//   DPM   x' = k_x*x + k_c*x0 + k_p*hist;  hist <- x0        (no eps)
+// one rounding per op.
+DMX_DEV float ddpm_x0_elem(float x0, float eps, float ds, float dd, float sd, float nz) {
+  return rnd(rnd(ds * x0) + rnd(dd * eps)) + rnd(nz * sd);
+}
+DMX_DEV float ddim_x0_elem(float x0, float eps, float ks, float kd, float kn, float nz) {
+  return rnd(rnd(ks * x0) + rnd(kd * eps)) + rnd(kn * nz);
+}
+DMX_DEV float dpm_x0_elem(float x, float x0, float kx, float kc, float kp, float* hist) {
+  const float y = rnd(kx * x) + rnd(kc * x0);
+  const float out = kp != 0.f ? y + rnd(kp * *hist) : y;
+  *hist = x0;
+  return out;
 }
 
 DMX_DEV float ddpm_elem(float x, float eps, float c1, float c2, float sd, float nz) {

@@ -121,16 +121,21 @@ class NativeModel:
 
     PREDICTIONS = {"eps": 0, "v": 1}
 
-    def set_prediction(self, kind, p_o=None, p_x=None) -> None:
+    def set_prediction(self, kind, p_o=None, p_x=None, *, d_s=None, d_d=None) -> None:
         """What the network predicts (include/dmx.h dmx_model_set_prediction): "eps" (the default), or "v"
         with the (T,) fp32 tables p_o = sqrt(ab), p_x = sqrt(1 - ab) (Diffuser.noise_tables) — every step
         and loop then converts its mixed output to eps before the update.  The library copies the tables;
         a change of kind or tables drops the captured graphs and the cached deep feature.  The pair last
-        given is remembered by identity, so repeating a call costs nothing."""
+        given is remembered by identity, so repeating a call costs nothing.
+        d_s, d_d (with "v"; both or neither): the (T,) fp32 tables of the x0-form (Diffuser.x0_tables;
+        include/dmx.h dmx_model_set_prediction_x0) — the steps then convert to (x0, eps) and update without a
+        division, as a zero-terminal-SNR schedule needs; `prediction` stays "v" and `x0_form` turns True."""
         if kind not in self.PREDICTIONS:
             raise ValueError(f'prediction must be "eps" or "v" (got {kind!r})')
-        last = getattr(self, "_prediction", ("eps", None, None))
-        if last[0] == kind and (kind == "eps" or (last[1] is p_o and last[2] is p_x)):
+        if (d_s is None) != (d_d is None) or (d_s is not None and kind != "v"):
+            raise ValueError('d_s and d_d are given together, and with prediction "v" only')
+        last = getattr(self, "_prediction", ("eps", None, None, None, None))
+        if last[0] == kind and (kind == "eps" or all(a is b for a, b in zip(last[1:], (p_o, p_x, d_s, d_d)))):
             return
         po_c = px_c = None
         T = 0
@@ -142,15 +147,31 @@ class NativeModel:
             T = int(po_c.numel())
             if T < 1 or px_c.numel() != T:
                 raise ValueError(f"p_o and p_x must be equal non-empty tables (got {po_c.numel()}, {px_c.numel()})")
+        ds_c = dd_c = None
+        if d_s is not None:
+            ds_c = d_s.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+            dd_c = d_d.to(device=self.device, dtype=torch.float32).contiguous().reshape(-1)
+            if ds_c.numel() != T or dd_c.numel() != T:
+                raise ValueError(f"d_s and d_d must have p_o's {T} entries (got {ds_c.numel()}, {dd_c.numel()})")
         with torch.cuda.device(self.device):
-            check(self.lib.dmx_model_set_prediction(self.handle, self.PREDICTIONS[kind], _ptr(po_c), _ptr(px_c), T,
-                                                    ctypes.c_void_p(_stream(self.device))))
-        self._prediction = (kind, p_o, p_x)  # (the tensors are kept: their identity stays valid)
+            if ds_c is not None:
+                check(self.lib.dmx_model_set_prediction_x0(self.handle, _ptr(po_c), _ptr(px_c), _ptr(ds_c), _ptr(dd_c),
+                                                           T, ctypes.c_void_p(_stream(self.device))))
+            else:
+                check(self.lib.dmx_model_set_prediction(self.handle, self.PREDICTIONS[kind], _ptr(po_c), _ptr(px_c),
+                                                        T, ctypes.c_void_p(_stream(self.device))))
+        self._prediction = (kind, p_o, p_x, d_s, d_d)  # (the tensors are kept: their identity stays valid)
+
+    PRED_V_X0 = 2  # (include/dmx.h DMX_PRED_V_X0: "v" in x0-form)
 
     @property
     def prediction(self) -> str:
         code = self.lib.dmx_model_get_prediction(self.handle)
-        return {v: k for k, v in self.PREDICTIONS.items()}[code]
+        return "v" if code == self.PRED_V_X0 else {v: k for k, v in self.PREDICTIONS.items()}[code]
+
+    @property
+    def x0_form(self) -> bool:
+        return self.lib.dmx_model_get_prediction(self.handle) == self.PRED_V_X0
 
     def range_tripped(self, reset: bool = True) -> bool:
         """True when an output kernel saw a non-finite value since the last reset (include/dmx.h
@@ -925,6 +946,40 @@ def pred_to_eps(out, x, t, p_o, p_x, inplace=False):
         check(lib.dmx_pred_to_eps(_ptr(o_c), _ptr(x_c), _ptr(t_c), stride, _ptr(po_c), _ptr(px_c), T, n, c, h, w,
                                   _ptr(eps), ctypes.c_void_p(_stream(dev))))
     return eps
+
+
+def pred_split(out, x, t, p_o, p_x, inplace=False):
+    """A v-model's (mixed) output as (x0, eps), the x0-form's conversion (include/dmx.h dmx_pred_split):
+        x0 = p_o[t - 1] x - p_x[t - 1] out;  eps = p_o[t - 1] out + p_x[t - 1] x
+    (torch's bits: two products and a sum or difference each, no FMA) in one pass.  Operands as in pred_to_eps;
+    inplace: eps is written over `out`, which is returned in its place; x0 is always a new tensor."""
+    lib = _lib.load()
+    require_cuda(out, "out")
+    dev = out.device
+    o_c = out.detach().to(dtype=torch.float32).contiguous()
+    x_c = x.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if o_c.dim() != 4 or tuple(x_c.shape) != tuple(o_c.shape) or min(o_c.shape) < 1:
+        raise ValueError(f"out / x must be equal non-empty (n,c,h,w) tensors (got {tuple(out.shape)}, {tuple(x.shape)})")
+    n, c, h, w = o_c.shape
+    po_c = p_o.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    px_c = p_x.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+    T = int(po_c.numel())
+    if T < 1 or px_c.numel() != T:
+        raise ValueError(f"p_o and p_x must be equal non-empty tables (got {po_c.numel()}, {px_c.numel()})")
+    t_c = torch.as_tensor(t).to(device=dev, dtype=torch.long).reshape(-1)
+    if t_c.numel() not in (1, n):
+        raise ValueError(f"t has {t_c.numel()} entries for a batch of {n}")
+    stride = 0 if t_c.numel() == 1 else int(t_c.stride(0))
+    if stride < 1 and t_c.numel() > 1:
+        t_c, stride = t_c.contiguous(), 1
+    if inplace and (o_c.data_ptr() != out.data_ptr() or out.requires_grad or o_c.data_ptr() == x_c.data_ptr()):
+        raise ValueError("inplace needs `out` to be a contiguous fp32 tensor without grad, and not x itself")
+    eps = out if inplace else torch.empty_like(o_c)
+    x0 = torch.empty_like(o_c)
+    with torch.cuda.device(dev):
+        check(lib.dmx_pred_split(_ptr(o_c), _ptr(x_c), _ptr(t_c), stride, _ptr(po_c), _ptr(px_c), T, n, c, h, w,
+                                 _ptr(x0), _ptr(eps), ctypes.c_void_p(_stream(dev))))
+    return x0, eps
 
 
 def train_noise(z, sa, s1, t=None, noise=None, drop=None, y=None, null_label=0, vals=None, mask=None,

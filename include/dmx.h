@@ -121,6 +121,32 @@ int dmx_model_get_prediction(const dmx_model* m);
  * [1, T]; out, x, eps_out NCHW (n,c,h,w), any c*h*w; eps_out may alias out (not x). */
 int dmx_pred_to_eps(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
                     const float* p_x, int T, int n, int c, int h, int w, float* eps_out, void* stream);
+/* The x0-form of a v-model, for schedules whose last step is pure noise (ab_T = 0, "zero terminal SNR",
+ * Lin et al. 2023), where the eps-form updates divide by sqrt(ab_T) = 0.  The mixed output is converted
+ * to both x0 and eps, with x_net and t as above,
+ *   x0  = p_o[t - 1] * x_net - p_x[t - 1] * out        eps = p_o[t - 1] * out + p_x[t - 1] * x_net
+ * and the rules update from them without a division (one IEEE rounding per operation, never contracted):
+ *   DDPM   x' = (d_s[t - 1] * x0 + d_d[t - 1] * eps) + nz * sd[t - 1]           nz = 0 at t == 1
+ *   DDIM   x' = (k_s * x0 + k_d * eps) + k_n * nz
+ *   DPM    y = k_x * x + k_c * x0;  x' = k_p != 0 ? y + k_p * hist : y;  hist <- x0
+ * d_s = sqrt(ab_prev), d_d = (1 - ab_prev) sqrt(a_t) / sqrt(1 - ab_t) with ab_prev = 1 at t = 1: the DDPM
+ * posterior mean on (x0, eps), [T] fp32 by network timestep like p_o / p_x; the step's c1 / c2 are not
+ * read.  The strided rules read the k_s / k_d / k_n and k_x / k_c / k_p of their schedules and never
+ * k_e / k_a.  Inversion has neither an x0 nor a division and converts as DMX_PRED_V does.  The range
+ * flag is raised on x0, and on eps where the rule reads it.  Same contract as dmx_model_set_prediction:
+ * device copies are kept, a repeated identical call is recognised, a change drops every captured graph
+ * and the cached deep feature, a schedule that names a timestep above T is DMX_E_ARG before any launch;
+ * dmx_model_get_prediction then returns DMX_PRED_V_X0, and dmx_model_set_prediction with DMX_PRED_EPS or
+ * DMX_PRED_V leaves the x0-form (DMX_PRED_V_X0 is not a kind of that entry).  DMX_E_ARG: a NULL table or
+ * T < 1. */
+#define DMX_PRED_V_X0 2
+int dmx_model_set_prediction_x0(dmx_model* m, const float* p_o, const float* p_x, const float* d_s,
+                                const float* d_d, int T, void* stream);
+/* The x0-form's conversion alone, both halves in one pass: dmx_pred_to_eps's operands and rules;
+ * eps_out may alias out; neither output may alias x, nor each other, and x0_out may not alias out. */
+int dmx_pred_split(const float* out, const float* x, const int64_t* t, int t_stride, const float* p_o,
+                   const float* p_x, int T, int n, int c, int h, int w, float* x0_out, float* eps_out,
+                   void* stream);
 /* Range guard of the split-precision modes (1, 2): an operand beyond the f16 range turns a
  * network output (eps / decoded pixel / encoder head) non-finite, and the output kernels then
  * raise a sticky per-model flag.  Reads it (synchronising `stream`), optionally clearing it;

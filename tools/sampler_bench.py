@@ -1,12 +1,14 @@
 """Few-step sampling (strided DDIM, DPM-Solver++(2M)) against the full DDPM walk on one MI355X: prints
 one JSON line.
 
-  python tools/sampler_bench.py [--rounds 5] [--prediction eps|v]
+  python tools/sampler_bench.py [--rounds 5] [--prediction eps|v|v_x0]
       [--groups loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end,cache]
 
 --prediction v runs every group with the model read as a v-predictor (Diffuser(prediction="v")): the same
 launches, each tail converting its mixed output to eps before the update.  Run it beside the default on
-one build for the cost of the conversion.
+one build for the cost of the conversion.  --prediction v_x0 reads it as a v-predictor in x0-form
+(Diffuser(prediction="v", x0_form=True), the form a zero-terminal-SNR schedule needs; the schedule itself stays
+the default one, so that the legs are those of --prediction v): beside v, the cost of the x0-form tails.
 
 Workload: bench.py's — B = 64, 32x32x4 latents, CFG 3.0, device (Philox) noise, synthetic weights.
 
@@ -419,6 +421,11 @@ def cache_legs(nm, d, dev, rounds):
     return out
 
 
+def pred_kw(prediction):
+    """--prediction as Diffuser keywords."""
+    return dict(prediction="v", x0_form=True) if prediction == "v_x0" else dict(prediction=prediction)
+
+
 def cache_end_to_end(model, dev, prediction="eps"):
     """sample_latent_cond(ddpm, T = 1000) with the decode: plain, cache_interval = 3, plain again."""
     import diff
@@ -433,7 +440,7 @@ def cache_end_to_end(model, dev, prediction="eps"):
     vals, mask = vals[order].contiguous(), mask[order].contiguous()
     kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
               cond_mask=mask)
-    d = diff.Diffuser(T, device=dev, prediction=prediction)
+    d = diff.Diffuser(T, device=dev, **pred_kw(prediction))
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
@@ -464,7 +471,7 @@ def end_to_end(model, dev, prediction="eps"):
     vals, mask = vals[order].contiguous(), mask[order].contiguous()
     kw = dict(z_shape=(4, HW, HW), vae=vae, to_pil=True, progress=False, guidance_scale=GUIDANCE, cond=vals,
               cond_mask=mask)
-    d = diff.Diffuser(T, device=dev, prediction=prediction)
+    d = diff.Diffuser(T, device=dev, **pred_kw(prediction))
     d.noise_source = "device"
     d._decode(vae, torch.randn((B, 4, HW, HW), device=dev), True)  # decode workspace
     out = {}
@@ -512,7 +519,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--groups", default="loops,known_loops,guidance_loops,composed_loops,pag_loops,end_to_end")
-    ap.add_argument("--prediction", default="eps", choices=["eps", "v"], help="what the network's output is read as")
+    ap.add_argument("--prediction", default="eps", choices=["eps", "v"] + ["v_x0"],  # (v_x0: v in x0-form)
+                    help="what the network's output is read as")
     args = ap.parse_args()
     groups = args.groups.split(",")
     if not torch.cuda.is_available():
@@ -529,7 +537,7 @@ def main():
            "device": torch.cuda.get_device_name(dev), "rounds": args.rounds, "prediction": args.prediction}
 
     def diffuser():  # (the loop legs drive the native model themselves: it is told the prediction here)
-        d = diff.Diffuser(T, device=dev, prediction=args.prediction)
+        d = diff.Diffuser(T, device=dev, **pred_kw(args.prediction))
         d._set_prediction(model.native())
         return d
     for name, fn in (("loops", loop_legs), ("known_loops", known_legs), ("guidance_loops", guidance_legs),
