@@ -14,13 +14,16 @@ namespace dmx {
 // Encoder tail of the training forward: vae_enc_tail_kernel (kernels.h, same arithmetic and launch
 // geometry) that also records what the backward reads — heads[row][8] = mu (0-3) and the unclamped
 // logvar (4-7) per latent pixel row = n HW + pix, and zin[row][4] = z / scale, the decoder's NHWC input.
+// The KL terms and their sums are taken in double (klp[n][block], summed in block order by
+// vae_train_kl_kernel), so that kl[n] is the fp32 rounding of the sum and not a neighbour of it: a
+// per-sample scalar has no other samples to average a summation ulp over.
 // ---------------------------------------------------------------------------
 static __global__ __launch_bounds__(256) void vae_train_heads_kernel(const float* in, const float* wmu, const float* bmu,
                                                                      const float* wlv, const float* blv, const float* eps,
-                                                                     float* z, float* klp, int HW, float scale,
+                                                                     float* z, double* klp, int HW, float scale,
                                                                      int* range_flag, float* heads, float* zin) {
   __shared__ __attribute__((aligned(16))) float ws[8][256];  // rows 0-3: to_mu, 4-7: to_logvar ([out][in])
-  __shared__ float red[4];
+  __shared__ double red[4];
   for (int i = threadIdx.x; i < 8 * 256; i += 256) ws[i / 256][i % 256] = i < 1024 ? wmu[i] : wlv[i - 1024];
   __syncthreads();
   const int n = blockIdx.y, l8 = threadIdx.x & 7, pix = blockIdx.x * 32 + (threadIdx.x >> 3);
@@ -46,7 +49,7 @@ static __global__ __launch_bounds__(256) void vae_train_heads_kernel(const float
     a[o] += __shfl_xor(a[o], 2, 64);
     a[o] += __shfl_xor(a[o], 4, 64);
   }
-  float kacc = 0.f;
+  double kacc = 0.0;
   if (l8 == 0 && pix < HW) {
     const size_t row = (size_t)n * HW + pix;
 #pragma unroll
@@ -60,7 +63,7 @@ static __global__ __launch_bounds__(256) void vae_train_heads_kernel(const float
       zin[row * 4 + o] = zz / scale;
       heads[row * 8 + o] = mu0;
       heads[row * 8 + 4 + o] = lv0;
-      kacc += ((expf(lv) + mu * mu) - 1.f) - lv;
+      kacc += ((exp((double)lv) + (double)mu * (double)mu) - 1.0) - (double)lv;
     }
   }
 #pragma unroll
@@ -68,6 +71,15 @@ static __global__ __launch_bounds__(256) void vae_train_heads_kernel(const float
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = kacc;
   __syncthreads();
   if (threadIdx.x == 0) klp[(size_t)n * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// kl[n] = 0.5 sum_b klp[n][b] / (h w): the block partials in block order, in double, rounded to fp32 once
+static __global__ void vae_train_kl_kernel(const double* klp, int nb, int N, double px, float* kl) {
+  for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
+    double sacc = 0.0;
+    for (int b = 0; b < nb; ++b) sacc += klp[(size_t)n * nb + b];
+    kl[n] = (float)(0.5 * sacc / px);
+  }
 }
 
 // Adjoint of the tail (models/vae.py:52-61).  With u = mu + eps std, z = u scale, zin = z / scale and

@@ -158,13 +158,13 @@ static void vae_train_fwd_body(Run& R, VaeTape& T, const float* x, const float* 
     W = T.enc[i].Wo;
   }
   const int nb = cdiv(HWl, 32);
-  float* klp = R.ws.get<float>((size_t)n * nb);
+  double* klp = R.ws.get<double>((size_t)n * nb);
   if (!R.plan) {
     R.layer = "vae.train.heads";
     R.begin("vae_train_heads_kernel", 2.0 * n * HWl * 8 * 256, 4.0 * (double)n * HWl * (256 + 4 + 4 + 12));
     vae_train_heads_kernel<<<dim3(nb, n), 256, 0, R.st>>>(cur, m->wmu, m->bmu, m->wlv, m->blv, T.eps, z, klp, HWl,
                                                            m->cfg.scale, m->range_flag, T.heads, T.zin);
-    vae_enc_kl_kernel<<<cdiv(n, 64), 64, 0, R.st>>>(klp, nb, n, 1.0f / ((float)h * (float)w), kl);
+    vae_train_kl_kernel<<<cdiv(n, 64), 64, 0, R.st>>>(klp, nb, n, (double)h * (double)w, kl);
     R.end();
     HIPCHK(hipGetLastError());
   }
